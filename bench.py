@@ -8,7 +8,7 @@ queries]) with the corpus and the queries already resident in HBM; for N > 1 GPU
 range-partitioned, weak scaling: 10M vectors PER GPU) the step also includes the RCCL all-gather of the
 per-shard top-k and the merge. value = vectors scanned per second = Q * N_total / step time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   N > 1: one process per GPU -- launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`, or, from a
   bare shell, by bench.py itself (it starts that launcher as a child before touching a GPU and relays rank 0's line).
 
@@ -86,6 +86,26 @@ def cpu_baseline(dim: int, k: int, budget_s: float = 20.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, idx, sc) -> None:
+    """--dump-outputs: what the timed path returned in its last step, as DIR/indices.npy (float64: every index < 2^53 is exact)
+    and DIR/scores.npy (float32), one row per query. Above DUMP_LIMIT_BYTES a fixed, seeded, sorted sample of query rows is
+    written instead, with its row numbers in DIR/query_rows.npy."""
+    import numpy as np
+    idx = np.asarray(idx.cpu() if hasattr(idx, "cpu") else idx).astype(np.float64)
+    sc = np.asarray(sc.cpu() if hasattr(sc, "cpu") else sc).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = idx.shape[1] * 8 + sc.shape[1] * 4 + 8
+    if idx.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(idx.shape[0], DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        idx, sc = idx[rows], sc[rows]
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "indices.npy"), idx)
+    np.save(os.path.join(out_dir, "scores.npy"), sc)
+
+
 def pmc_traffic(args):
     """HBM-side bytes per GEMM launch from the committed rocprofv3 PMC passes of THIS command (profiles/, collected
     in separate --pmc runs: a counter pass cannot share a run with the timed region). FETCH_SIZE/WRITE_SIZE are in
@@ -160,6 +180,8 @@ def rehearse_cpu(args) -> int:
         dt = float(t.item())
     want_sc, want_idx = torch.topk(queries @ corpus.T, min(args.k, n_total), dim=1)
     same = bool(torch.equal(idx, want_idx.to(torch.int64)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx, sc)
     if rank == 0:
         print(json.dumps({"metric": "vectors scanned/sec (batch_knn_dot f32 d=768 k=10)", "value": None, "unit": "vectors/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -227,7 +249,12 @@ def main() -> None:
                     help="f32: the MFMA GEMM filter on the f32 pipe (default, the judged configuration); bf16: the same "
                          "pipeline with the filter on the bf16 pipe (INNR_KNN_MFMA_BF16) -- identical results, reported "
                          "as a side measurement with its own roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the indices and scores the last timed step returned to DIR/*.npy "
+                         "(rank 0; float64 indices, float32 scores, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` from a bare shell: start the N ranks ourselves -- one fresh process per GPU under
@@ -339,6 +366,8 @@ def main() -> None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx, sc)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3

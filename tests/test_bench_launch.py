@@ -45,3 +45,22 @@ def test_bench_self_launch_reports_a_failing_rank():
     r = _run("--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--n-per-gpu", "1000")
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.lstrip().startswith("{")]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR writes what the last timed step returned (float64 indices, float32 scores); the inputs are seeded, so
+    two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = _run("--gpus", "1", "--steps", "3", "--warmup", "0", "--rehearse-cpu", "--n-per-gpu", "500", "--dim", "16", "--queries",
+                 "9", "--k", "4", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 3
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("indices", "scores")})
+    a, b = dumps
+    assert a["indices"].dtype == np.float64 and a["scores"].dtype == np.float32
+    assert a["indices"].shape == a["scores"].shape == (9, 4)
+    assert np.all((a["indices"] >= 0) & (a["indices"] < 500) & (a["indices"] == np.round(a["indices"])))
+    assert np.array_equal(a["indices"], b["indices"]) and np.array_equal(a["scores"].view(np.uint32), b["scores"].view(np.uint32))
