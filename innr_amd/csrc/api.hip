@@ -95,6 +95,8 @@ struct innr_tuning {
     long i8_no_small4 = 0;       // ... never its four-column-tile form (65 .. 128 queries)
     long i8_small_max_q = 0;     // ... its largest batch (groups of 128 queries beyond 128); 0 = the default
     long i8_small_free = 0;      // ... its query groups run free (no soft lockstep): A/B
+    long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
+    long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
 };
 struct TuneName { const char* name; long innr_tuning::*field; };
 static const TuneName kTuneNames[] = {
@@ -107,7 +109,8 @@ static const TuneName kTuneNames[] = {
     {"fail_local_search", &innr_tuning::fail_local_search}, {"no_completion", &innr_tuning::no_completion}, {"trace", &innr_tuning::trace}, {"no_rows_copy", &innr_tuning::no_rows_copy},
     {"i8_slices_per_cu", &innr_tuning::i8_slices_per_cu}, {"i8_no_small", &innr_tuning::i8_no_small},
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
-    {"i8_small_free", &innr_tuning::i8_small_free},
+    {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
+    {"split_min_q", &innr_tuning::split_min_q},
 };
 static void tuning_from_env(innr_tuning* t) {
     for (const TuneName& n : kTuneNames) {
@@ -174,6 +177,7 @@ struct innr_ctx {
     DevBuf q_one;      // full-sort path (k > INNR_MAX_K): one zero-padded query row
     DevBuf sort_keys;  // [2][N] composites: unsorted, sorted
     DevBuf sort_tmp;   // radix sort scratch
+    int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
 };
 
 namespace innr {
@@ -242,6 +246,11 @@ struct innr_batch {
     char* Abn = nullptr;  // the same with every row scaled by 1/||v||: the cosine filter (built on the first cosine call)
     char* Abl = nullptr;  // the squared-L2 filter's copy: six more K columns per row (|v|^2 in three limbs, three ones)
     uint32_t ab_nk = 0, abl_nk = 0;
+    // the split-bf16 filter of INNR_KNN_MFMA: the lo limbs x - rne_bf16(x) of Ab's (Abx) and Abn's (Abnx)
+    // values, in the same layout; built on first use when they fit, always owned
+    char* Abx = nullptr;
+    char* Abnx = nullptr;
+    bool split_refused = false, splitn_refused = false;  // a copy did not fit: do not try again on every call
     // int8 filter engine (kernels_gemm_i8.h): K-packed signed copy of the u8 codes, built on first use, always owned
     char* Ai8 = nullptr;
     uint32_t ai8_nk = 0;
@@ -1171,8 +1180,8 @@ static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nre
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
 #define INNR_BF16_LAUNCH(RR)                                                                                              \
-    gemm_bf16_filter_kernel<RR, 0><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                             \
-        variant == kBfCos ? b->Abn : (variant == kBfL2 ? b->Abl : b->Ab), c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N, \
+    gemm_bf16_filter_kernel<RR, 0, 1><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                          \
+        variant == kBfCos ? b->Abn : (variant == kBfL2 ? b->Abl : b->Ab), nullptr, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N, \
         variant == kBfL2 ? b->abl_nk : b->ab_nk, p.Qpad, p.nqt, p.qtg, p.tps,                                                  \
         c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, nullptr, 0)
     switch (p.cap) {
@@ -1182,6 +1191,92 @@ static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nre
         default: INNR_BF16_LAUNCH(20); break;
     }
 #undef INNR_BF16_LAUNCH
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
+// ---- split-bf16 filter of INNR_KNN_MFMA (kernels_gemm_bf16.h, LIMBS = 3) ---------------------------------
+// Which filter kernel the last first pass of knn_mfma launched (innr_ctx::last_filter; innrdbg_last_filter).
+enum LastFilter { kFilterNone = 0, kFilterF32 = 1, kFilterBf16 = 2, kFilterSplit = 3 };
+// Smallest batch the split filter serves by default: its 512-query tile against the f32 kernel's narrow tiles, measured at C2
+// (tools/split_ab.py, profiles/r04_split_ab.txt): 64 queries 13.9 ms split vs 9.2 f32 (one-wave tile), 128 queries 14.5 vs 15.7
+// (two-wave tile), 256 queries 15.5 vs 28.8.
+constexpr size_t kSplitMinQ = 65;
+
+// The hi (Ab / Abn) and lo (Abx / Abnx) limb copies of the dot / cosine kind. Each copy is built only with twice its size + 8 GiB
+// free (the rule of the other filter copies); *ok == false: one did not fit, the call filters on the f32 kernel instead.
+static innr_status ensure_split_corpus(innr_batch* b, bool cos, bool* ok) {
+    *ok = false;
+    bool& refused = cos ? b->splitn_refused : b->split_refused;
+    if (refused) return INNR_OK;
+    char*& hi = cos ? b->Abn : b->Ab;
+    char*& lo = cos ? b->Abnx : b->Abx;
+    const size_t bytes = bf16_copy_bytes(b, kBfDot);
+    for (int l = 0; l < 2; ++l) {
+        if ((l == 0 ? hi : lo) != nullptr) continue;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * bytes + ((size_t)8 << 30)) {
+            refused = true;
+            return INNR_OK;
+        }
+        if (l == 0) {
+            INNR_TRY(ensure_bf16_corpus(b, cos ? kBfCos : kBfDot));
+            continue;
+        }
+        if (hipMalloc((void**)&lo, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            lo = nullptr;
+            refused = true;
+            return INNR_OK;
+        }
+        const uint32_t nk = bf16_nk(b, kBfDot);
+        const size_t units = bytes / 16;
+        pack_corpus_bf16_kernel<<<(unsigned)((units + 255) / 256), 256, 0, b->ctx->stream>>>(
+            b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(lo), cos ? b->invn : nullptr, nullptr, 1);
+        INNR_HIP_CHECK(hipGetLastError());
+    }
+    *ok = true;
+    return INNR_OK;
+}
+
+// c->q_bf16: the queries' hi limbs (nk K-steps), then their lo limbs (cosine: of the normalised queries, qscale = 1/||q||)
+static innr_status pack_queries_split(innr_batch* b, const GemmPlan& p, const float* dQ, size_t Q, const float* qscale) {
+    innr_ctx* c = b->ctx;
+    const uint32_t nk = bf16_nk(b, kBfDot);
+    const size_t units = (size_t)nk * 4 * p.Qpad;
+    INNR_TRY(c->q_bf16.ensure(2 * units * 16));
+    for (int l = 0; l < 2; ++l) {
+        pack_queries_bf16_kernel<<<(unsigned)((units + 255) / 256), 256, 0, c->stream>>>(
+            dQ, (uint32_t)Q, (uint32_t)b->D, nk, (uint32_t)p.Qpad, reinterpret_cast<uint4*>(c->q_bf16.p) + l * units, qscale, nullptr, l);
+        INNR_HIP_CHECK(hipGetLastError());
+    }
+    return INNR_OK;
+}
+
+template <int MODE>
+static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nreal_q, bool cos, const uint32_t* seed,
+                                     const float* kmargin = nullptr, uint32_t kk = 0, float* dump = nullptr, size_t ld_dump = 0) {
+    innr_ctx* c = b->ctx;
+    uint32_t* gslots = nullptr;
+    size_t nslot = 0;
+    if (!kmargin) kk = 0;
+    INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
+#define INNR_SPLIT_LAUNCH(RR)                                                                                             \
+    gemm_bf16_filter_kernel<RR, MODE, 3><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                      \
+        cos ? b->Abn : b->Ab, cos ? b->Abnx : b->Abx, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N,          \
+        b->ab_nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk,                  \
+        c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump)
+    if constexpr (MODE == 1) {  // the dense-score dump: the list geometry plays no part
+        INNR_SPLIT_LAUNCH(6);
+    } else {
+        switch (p.cap) {
+            case 384: INNR_SPLIT_LAUNCH(6); break;
+            case 512: INNR_SPLIT_LAUNCH(8); break;
+            case 768: INNR_SPLIT_LAUNCH(12); break;
+            default: INNR_SPLIT_LAUNCH(20); break;
+        }
+    }
+#undef INNR_SPLIT_LAUNCH
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
@@ -1209,7 +1304,18 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     const bool use_bf16 = bf16 && pick_kp(4 * kout + 64, 0) <= 256 && b->max_norm >= 1e-12f &&
                           (b->max_norm - b->max_norm == 0.0f) && (!l2 || b->max_norm <= 1e15f);
     const int bfv = cos ? kBfCos : (l2 ? kBfL2 : kBfDot);
-    GemmPlan p = plan_gemm(b, Q, kout, use_bf16 ? 8 : 0, !cos && !l2);
+    // split-bf16 filter: dot and cosine from kSplitMinQ queries on, lists up to 256, a corpus whose norm keeps
+    // the limbs' flush-to-zero terms far below E (or a non-finite one: every query is redone exactly below either way)
+    const bool mfin = b->max_norm - b->max_norm == 0.0f;
+    const size_t split_q = c->tune.split_min_q > 0 ? (size_t)c->tune.split_min_q : kSplitMinQ;
+    bool use_split = !use_bf16 && !l2 && !c->tune.no_split_filter && Q >= split_q && pick_kp(kout, 16) <= 256 &&
+                     (!mfin || (b->max_norm >= 1e-12f && b->max_norm <= 1e18f));
+    if (use_split) {
+        if (cos) INNR_TRY(ensure_invnorms(b));
+        INNR_TRY(ensure_split_corpus(b, cos, &use_split));  // does not fit: the f32 kernel
+    }
+    if (level == 0) c->last_filter = use_bf16 ? kFilterBf16 : (use_split ? kFilterSplit : kFilterF32);
+    GemmPlan p = plan_gemm(b, Q, kout, (use_bf16 || use_split) ? 8 : 0, !cos && !l2);
     if (kp_force && !use_bf16 && kp_force >= p.KP && kp_force <= 256) {  // second attempt of redo_batch: longer lists
         p.KP = kp_force;
         p.cap = (uint32_t)cand_cap((int)p.KP);
@@ -1245,7 +1351,7 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
             cos ? c->misc.as<float>() : nullptr, l2 ? invq : nullptr);
         INNR_HIP_CHECK(hipGetLastError());
     }
-
+    if (use_split) INNR_TRY(pack_queries_split(b, p, dQ, Q, cos ? c->misc.as<float>() : nullptr));
 
     // dot / cosine: |approx - exact| <= (2D+8) u (1+eps) * sum|q_d v_d|: u = 2^-24, Cauchy-Schwarz for the sum.
     // L2: approx = C - (|v|^2 - 2 q.v + |q|^2) assembled from the MFMA dot (<= (2D+8) u |q||v|, doubled), the squared
@@ -1262,7 +1368,19 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     // inside (8D + 96) u C
     const float bf16_scale = l2 ? 1.05f * (0.00390625f * 1.004f + (8.0f * (float)b->D + 96.0f) * 5.9604645e-08f)
                                 : 1.05f * (0.0078125f * 1.004f + (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.02f) * (cos ? 1.0f : b->max_norm);
-    const float err_scale = use_bf16 ? bf16_scale
+    // split-bf16 filter, per dimension x = qh + ql + rq, y = vh + vl + rv (h = rne_bf16, l = rne_bf16 of the exact
+    // f32 difference; |h| <= (1 + 2^-8)|x|, |l| <= (1 + 2^-8) 2^-8 |x|, |r| <= 2^-16 |x|). The kernel sums qh vh + qh vl + ql vh; the
+    // dropped part xy - that = ql vl + qh rv + rq vh + ql rv + rq vl + rq rv is <= (3 (1 + 2^-7) 2^-16 + 2^-23 + 2^-32) |xy| <= 3.1 2^-16 |xy|.
+    // Every bf16 x bf16 product is exact in f32; their f32 accumulation on the matrix pipe -- the assumption the bf16 bound makes:
+    // n products accumulate within (2n + 8) u of the sum of their magnitudes -- with n = 3D products whose magnitudes sum to
+    // <= (1 + 2^-8)^2 (1 + 2^-7) sum|xy| <= 1.016 sum|xy|: (6D + 8) u 1.04 sum|xy|. Cauchy-Schwarz: sum|xy| <= |q| max|v|.
+    // Values at the bottom of the range: a limb or product below 2^-126 may be flushed to zero, at most 2^-126 per flushed
+    // operand times the other side (<= 2^-126 sqrt(D) (|q| + max|v|) over a row) plus 2^-126 per product or partial sum (6D of
+    // them). With max|v| and |q| both in [1e-12, 1e18] (the gates above and below; cosine: both normalised, <= 1.0), and E >= 3 2^-16
+    // |q| max|v|, that is below 1e-6 E -- inside the 1.05. A zero query is exact (every limb 0). Cosine: |q^||v^| <= (1 + D u)^2.
+    const float split_scale = 1.05f * (3.1f * 1.52587890625e-05f + (6.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.04f) *
+                              (cos ? 1.0f : b->max_norm);
+    const float err_scale = use_bf16 ? bf16_scale : use_split ? split_scale
                                      : (l2 ? 1.05f * (6.0f * (float)b->D + 40.0f) * 5.9604645e-08f : (cos ? cdu : cdu * b->max_norm));
 
     // threshold seeding from the exact top-KP of a corpus prefix (seed_thresholds_kernel)
@@ -1294,6 +1412,7 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     const uint32_t kk = (uint32_t)kout;
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     if (use_bf16) INNR_TRY(launch_gemm_bf16(b, p, Q, seed, bfv, kmargin, kk));
+    else if (use_split) INNR_TRY(launch_gemm_split<0>(b, p, Q, cos, seed, kmargin, kk));
     else if (cos) INNR_TRY((launch_gemm<kGemmCos, 0>(b, p, Q, c->q_kmajor.as<float>(), b->invn, invq, nullptr, 0, seed, kmargin, kk)));
     else if (l2) INNR_TRY((launch_gemm<kGemmL2, 0>(b, p, Q, c->q_kmajor.as<float>(), b->sqn, invq, nullptr, 0, seed, kmargin, kk)));
     // (A first pass of the same kernel over 1/16 of the corpus, only to harvest tighter bounds for the full pass, was
@@ -1322,13 +1441,15 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     INNR_HIP_CHECK(hipGetLastError());
 
     std::vector<uint32_t> fb(Q);
-    std::vector<float> qn_host(use_bf16 ? Q : 0);
+    std::vector<float> qn_host((use_bf16 || use_split) && !cos ? Q : 0);
     INNR_HIP_CHECK(copy_out(c, fb.data(), fallback, Q * sizeof(uint32_t)));
-    if (use_bf16) INNR_HIP_CHECK(copy_out(c, qn_host.data(), c->q_norm.p, Q * sizeof(float)));
+    if (!qn_host.empty()) INNR_HIP_CHECK(copy_out(c, qn_host.data(), c->q_norm.p, Q * sizeof(float)));
     INNR_HIP_CHECK(ctx_sync(c));
     // bf16 products / sums below the normal range may be flushed to zero: the bound E must dwarf that, else redo exactly
-    for (size_t q = 0; q < qn_host.size() && !cos; ++q)
-        if (!(qn_host[q] * b->max_norm >= 1e-25f)) fb[q] = 1;
+    // (split filter: the query-side gate of its bound, see split_scale)
+    for (size_t q = 0; q < qn_host.size(); ++q)
+        if (use_bf16 ? !(qn_host[q] * b->max_norm >= 1e-25f) : !(qn_host[q] == 0.0f || (qn_host[q] >= 1e-12f && qn_host[q] <= 1e18f)))
+            fb[q] = 1;
     // A non-finite corpus value (max_norm is then NaN or inf) voids every error bound -- for cosine too, whose bound does
     // not carry max_norm: NaN * 0 approximations can differ from the reference's 0.0 (batch.rs:722) by more than E.
     if (!(b->max_norm - b->max_norm == 0.0f))
@@ -1639,6 +1760,8 @@ void innr_batch_free(innr_batch* b) {
     if (b->Ab) (void)hipFree(b->Ab);
     if (b->Abn) (void)hipFree(b->Abn);
     if (b->Abl) (void)hipFree(b->Abl);
+    if (b->Abx) (void)hipFree(b->Abx);
+    if (b->Abnx) (void)hipFree(b->Abnx);
     if (b->Ai8) (void)hipFree(b->Ai8);
     if (b->Ai8n) (void)hipFree(b->Ai8n);
     if (b->Ai8l) (void)hipFree(b->Ai8l);
@@ -1687,6 +1810,40 @@ innr_status innrdbg_gemm_scores(innr_batch* b, int metric, const float* queries,
     INNR_HIP_CHECK(ctx_sync(c));
     return INNR_OK;
 }
+
+// Test hook: dense approximate score matrix of the split-bf16 filter (MODE 1), out[q*N + i]: dot, or cosine as the plain dot of
+// the normalised limbs -- what the filter compares, to check |approx - exact| <= E. INNR_E_UNSUPPORTED when the
+// limb copies do not fit.
+innr_status innrdbg_split_scores(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, float* out) {
+    if (b && !b->V) return INNR_E_BAD_ARG;
+    if (!b || !queries || !out || D != b->D || Q == 0 || b->N == 0 || metric == INNR_METRIC_L2SQ || !metric_ok(metric))
+        return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    const bool cos = metric == INNR_METRIC_COSINE;
+    const GemmPlan p = plan_gemm(b, Q, 1, /*waves=*/8);
+    INNR_TRY(ensure_norms(b));
+    if (cos) INNR_TRY(ensure_invnorms(b));
+    bool ok = false;
+    INNR_TRY(ensure_split_corpus(b, cos, &ok));
+    if (!ok) return INNR_E_UNSUPPORTED;
+    INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
+    INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
+    INNR_TRY(prep_queries(b, p, c->q_row.as<float>(), Q, cos));
+    INNR_TRY(pack_queries_split(b, p, c->q_row.as<float>(), Q, cos ? c->misc.as<float>() : nullptr));
+    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
+    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
+    INNR_TRY(c->scores.ensure(p.Qpad * b->ldN * sizeof(float)));
+    INNR_TRY(launch_gemm_split<1>(b, p, Q, cos, nullptr, nullptr, 0, c->scores.as<float>(), b->ldN));
+    INNR_HIP_CHECK(hipMemcpy2DAsync(out, b->N * sizeof(float), c->scores.p, b->ldN * sizeof(float),
+                                    b->N * sizeof(float), Q, hipMemcpyDeviceToHost, c->stream));
+    INNR_HIP_CHECK(ctx_sync(c));
+    return INNR_OK;
+}
+
+// Test hook: the filter kernel of the last INNR_KNN_MFMA / _BF16 first pass on this batch's context: 0 none yet, 1 the f32 kernel
+// (gemm_filter_kernel), 2 the bf16 filter, 3 the split-bf16 filter (LastFilter).
+int innrdbg_last_filter(const innr_batch* b) { return b && b->ctx ? b->ctx->last_filter : -1; }
 
 #endif  // INNR_TEST_HOOKS
 

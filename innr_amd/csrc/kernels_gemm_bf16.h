@@ -15,6 +15,12 @@
 // Block = 8 waves, tile 128 corpus rows x 512 queries; LDS ring of kBfStages stages, DMA kBfStages-2 steps ahead;
 // every step issues the same VMEM sequence (1 DMA, then 2 + 2 query loads), so all vmcnt waits are constants.
 // tools/bf16_filter_probe.hip is this K-loop without the epilogue: 8.9 ms for the C2 GEMM (1.77 PFLOP/s).
+//
+// LIMBS = 3: the f32 GEMM engine's TIGHT filter as a split-bf16 GEMM. Every value is written x = h + l + r with
+// h = rne_bf16(x), l = rne_bf16(x - h) (x - h is exact in f32, |r| <= 2^-16 |x|); the kernel accumulates qh.vh + qh.vl + ql.vh,
+// three bf16 products per dimension, each exact in f32. The corpus lo limbs live in a second copy Abx of Ab's exact layout, the
+// query lo limbs in a second Bb block right behind the first. A stage carries both 8-KiB corpus pieces (16 KiB, 8 stages =
+// 128 KiB of LDS); a step issues 2 DMA + 2 x 4 query loads (hi, hi, lo, lo per depth) -- still the same sequence every step.
 #pragma once
 
 #include "kernels_gemm.h"
@@ -47,6 +53,7 @@ __device__ __forceinline__ uint16_t bf16_limb(float x, int l) {
 constexpr uint32_t kBfL2Extra = 6;  // the squared-L2 copy's additional K columns
 
 // one thread per 16-byte output unit (8 dimensions of one corpus row)
+// limb: 0 = the rounded values (Ab, the hi limb), 1 = their lo limbs (Abx, the split filter; not with sqn)
 // rowscale (nullable): 1/||v|| per row (0 for zero-norm rows) -- the COSINE copy holds the normalised rows, so that the plain
 // dot of the filter kernel IS the approximate cosine (with the queries normalised the same way) and no norm is loaded per tile
 // sqn (nullable): |v|^2 per row -- the SQUARED-L2 copy carries six more K columns per row, [three bf16 limbs of |v|^2, 1, 1, 1],
@@ -56,7 +63,7 @@ constexpr uint32_t kBfL2Extra = 6;  // the squared-L2 copy's additional K column
 __global__ __launch_bounds__(256) void pack_corpus_bf16_kernel(const float* __restrict__ V, size_t ldN, uint32_t N, uint32_t D,
                                                                 uint32_t nk, size_t units, uint4* __restrict__ Ab,
                                                                 const float* __restrict__ rowscale = nullptr,
-                                                                const float* __restrict__ sqn = nullptr) {
+                                                                const float* __restrict__ sqn = nullptr, int limb = 0) {
     const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (u >= units) return;
     const uint32_t i = (uint32_t)(u & 31), rt = (uint32_t)((u >> 5) & 3), kg = (uint32_t)((u >> 7) & 3);
@@ -68,7 +75,7 @@ __global__ __launch_bounds__(256) void pack_corpus_bf16_kernel(const float* __re
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const uint32_t d = ks * 32 + kg * 8 + e;
-        h[e] = (row < N && d < D) ? f32_to_bf16_rne(V[(size_t)d * ldN + row] * rs) : (uint16_t)0;
+        h[e] = (row < N && d < D) ? bf16_limb(V[(size_t)d * ldN + row] * rs, limb) : (uint16_t)0;
         if (sqn && row < N && d >= D && d < D + kBfL2Extra)
             h[e] = (d - D < 3) ? bf16_limb(sqn[row], (int)(d - D)) : (uint16_t)0x3F80u;  // limbs of |v|^2, then 1.0 three times
     }
@@ -80,10 +87,11 @@ __global__ __launch_bounds__(256) void pack_corpus_bf16_kernel(const float* __re
 
 // queries row-major [Q][D] -> Bb; one thread per 16-byte unit
 // l2c (nullable; [Qpad] c_j = C_j - |q_j|^2): the squared-L2 packing, see pack_corpus_bf16_kernel
+// limb: 0 = the rounded values (hi limb), 1 = their lo limbs (the split filter; not with l2c)
 __global__ __launch_bounds__(256) void pack_queries_bf16_kernel(const float* __restrict__ Qm, uint32_t Q, uint32_t D, uint32_t nk,
                                                                  uint32_t Qpad, uint4* __restrict__ Bb,
                                                                  const float* __restrict__ qscale = nullptr,
-                                                                 const float* __restrict__ l2c = nullptr) {
+                                                                 const float* __restrict__ l2c = nullptr, int limb = 0) {
     const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (u >= (size_t)nk * 4 * Qpad) return;
     const uint32_t pos = (uint32_t)(u % Qpad);
@@ -94,7 +102,7 @@ __global__ __launch_bounds__(256) void pack_queries_bf16_kernel(const float* __r
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const uint32_t d = kk * 8 + e;
-        h[e] = (q < Q && d < D) ? f32_to_bf16_rne(Qm[(size_t)q * D + d] * qs) : (uint16_t)0;
+        h[e] = (q < Q && d < D) ? bf16_limb(Qm[(size_t)q * D + d] * qs, limb) : (uint16_t)0;
         if (l2c && q < Q && d >= D && d < D + kBfL2Extra)
             h[e] = (d - D < 3) ? (uint16_t)0xBF80u : bf16_limb(l2c[q], (int)(d - D - 3));  // -1.0 three times, then limbs of c_j
     }
@@ -117,16 +125,28 @@ template <int N> __device__ __forceinline__ void use_after(u32x4_t& a, u32x4_t& 
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
 }
 
+// per-step geometry of the K-loop: corpus pieces per stage (hi, + lo for the split filter), and the VMEM ops a wave issues per
+// step in their fixed order -- kDma LDS-DMA pieces, then kLoads query loads after each of the two depths' MFMAs
+template <int LIMBS> struct BfGeom {
+    static_assert(LIMBS == 1 || LIMBS == 3, "one bf16 limb (the bf16 filter) or the split hi.hi + hi.lo + lo.hi (the f32 engine's filter)");
+    static constexpr int kParts = LIMBS == 3 ? 2 : 1;
+    static constexpr int kStage = kParts * kBfStageBytes;
+    static constexpr int kDma = kParts, kLoads = 2 * kParts, kPerStep = kDma + 2 * kLoads;
+};
+
+template <int LIMBS>
 struct alignas(16) GemmBf16Lds {
-    alignas(16) char A[kBfStages * kBfStageBytes];
+    alignas(16) char A[kBfStages * BfGeom<LIMBS>::kStage];
     uint32_t cnt[64 * kBfWaves];
     uint32_t thr[64 * kBfWaves];
 };
 
 // MODE 0: fused top-k filter. MODE 1: dump the dense score matrix (layout test).
-template <int R, int MODE>
+// LIMBS 1: the bf16 filter (Abx unused). LIMBS 3: the split filter -- Abx the corpus lo limbs, Bb holds nk K-steps of query hi
+// limbs followed by nk K-steps of lo limbs.
+template <int R, int MODE, int LIMBS>
 __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
-    const char* __restrict__ Ab, const char* __restrict__ Bb, uint32_t ntiles, uint32_t N, uint32_t nk, size_t Qpad, uint32_t nqt,
+    const char* __restrict__ Ab, const char* __restrict__ Abx, const char* __restrict__ Bb, uint32_t ntiles, uint32_t N, uint32_t nk, size_t Qpad, uint32_t nqt,
     uint32_t qtg, uint32_t tiles_per_slice, uint64_t* __restrict__ lists, uint32_t* __restrict__ counts, uint32_t KP, uint32_t kk,
     uint32_t* __restrict__ errflag, uint32_t* gslots, uint32_t* gthr, float* __restrict__ dump, size_t ld_dump) {
     const float* const kmargin = reinterpret_cast<const float*>(gthr + Qpad);  // 2E per query: the k rule of topk_dev.h
@@ -136,8 +156,13 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     const float scale = 1.0f;
     const float iq_lane[2] = {1.0f, 1.0f};
     constexpr int kBQ = 64 * kBfWaves;
-    constexpr int kEpiTgWait = 5 * (kBfStages - 3) + 4 + 5;  // gemm_epilogue.inc: nothing this wave still prefetches is waited for
-    __shared__ GemmBf16Lds s;
+    using G = BfGeom<LIMBS>;
+    constexpr bool kSplit = LIMBS == 3;
+    // gemm_epilogue.inc: nothing this wave still prefetches is waited for. Split filter: the oldest op still needed at the epilogue
+    // (end of step s+1) is the DMA of step s+2, issued at the top of step s-4: six whole steps of ops from it on.
+    constexpr int kEpiTgWait = kSplit ? G::kPerStep * (kBfStages - 2) : 5 * (kBfStages - 3) + 4 + 5;
+    static_assert(kEpiTgWait <= 63 && G::kPerStep * (kBfStages - 4) + G::kPerStep - G::kDma <= 63, "vmcnt is 6 bits");
+    __shared__ GemmBf16Lds<LIMBS> s;
     constexpr uint32_t cap = 64 * R;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wu = __builtin_amdgcn_readfirstlane(w);
@@ -166,43 +191,50 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
 
     // operand addresses: wave-uniform base + constant lane offset
     const char* sa = Ab + (size_t)t0 * nk * kBfStageBytes + (size_t)wu * 1024;  // this wave's 1-KiB piece of step 0
+    const char* sx = kSplit ? Abx + (size_t)t0 * nk * kBfStageBytes + (size_t)wu * 1024 : nullptr;  // ... of the lo limbs
     const uint32_t va = (uint32_t)lane * 16u;
     const uint32_t lds0 = lds_addr_uniform(&s.A[0]) + (uint32_t)wu * 1024u;
-    const size_t b_step = (size_t)4 * Qpad * 16, b_depth = (size_t)2 * Qpad * 16, b_ct = 32 * 16;
+    const size_t b_step = (size_t)4 * Qpad * 16, b_depth = (size_t)2 * Qpad * 16, b_ct = 32 * 16, b_lo = (size_t)nk * b_step;
     const char* sb = Bb + (q0 + (size_t)wu * 64) * 16;
     const uint32_t vb = ((uint32_t)(lane >> 5) * (uint32_t)Qpad + (uint32_t)(lane & 31)) * 16u;
     uint32_t a_issued = 0, b_ks = 0;
     const uint32_t last = total ? total - 1 : 0;
     auto issue_a = [&]() {  // DMA of step a_issued; past the end of the slice: the last step again, into a stage nobody reads
         const uint32_t st = a_issued < total ? a_issued : last;
-        glds16(uniform_ptr(sa + (size_t)st * kBfStageBytes), va, lds0 + (a_issued % kBfStages) * kBfStageBytes);
+        const uint32_t slot = lds0 + (a_issued % kBfStages) * G::kStage;
+        glds16(uniform_ptr(sa + (size_t)st * kBfStageBytes), va, slot);
+        if (kSplit) glds16(uniform_ptr(sx + (size_t)st * kBfStageBytes), va, slot + kBfStageBytes);
         ++a_issued;
     };
-    auto issue_b = [&](u32x4_t& d0, u32x4_t& d1, int m) {
+    constexpr int kB = 2 * G::kParts;  // B fragment registers per depth: [hi ct 0, hi ct 1 (, lo ct 0, lo ct 1)]
+    auto issue_b = [&](u32x4_t* d, int m) {
         const char* p = uniform_ptr(sb + (size_t)b_ks * b_step + (size_t)m * b_depth);
-        gload4(d0, p, vb);
-        gload4(d1, uniform_ptr(p + b_ct), vb);
+        gload4(d[0], p, vb);
+        gload4(d[1], uniform_ptr(p + b_ct), vb);
+        if (kSplit) {
+            gload4(d[2], uniform_ptr(p + b_lo), vb);
+            gload4(d[3], uniform_ptr(p + b_lo + b_ct), vb);
+        }
     };
-    u32x4_t breg[kBfLead][4];  // [step % kBfLead][2 m + ct]
+    u32x4_t breg[kBfLead][2 * kB];  // [step % kBfLead][kB m + (lo ? 2 : 0) + ct]
 #pragma unroll
     for (int r = 0; r < kBfLead; ++r)
 #pragma unroll
-        for (int x = 0; x < 4; ++x) breg[r][x] = u32x4_t{0u, 0u, 0u, 0u};
+        for (int x = 0; x < 2 * kB; ++x) breg[r][x] = u32x4_t{0u, 0u, 0u, 0u};
     if (total) {
         for (int i = 0; i < kBfStages - 2; ++i) issue_a();
 #pragma unroll
         for (int r = 0; r < kBfLead; ++r) {
-            issue_b(breg[r][0], breg[r][1], 0);
-            issue_b(breg[r][2], breg[r][3], 1);
+            issue_b(&breg[r][0], 0);
+            issue_b(&breg[r][kB], 1);
             b_ks = (b_ks + 1 == nk) ? 0 : b_ks + 1;
         }
     }
     wait_all();
 #pragma unroll
-    for (int r = 0; r < kBfLead; ++r) {
-        use_after<0>(breg[r][0], breg[r][1]);
-        use_after<0>(breg[r][2], breg[r][3]);
-    }
+    for (int r = 0; r < kBfLead; ++r)
+#pragma unroll
+        for (int x = 0; x < 2 * kB; x += 2) use_after<0>(breg[r][x], breg[r][x + 1]);
     __syncthreads();
 
     uint32_t tg_next[2] = {0u, 0u};
@@ -215,26 +247,45 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
 #pragma unroll
         for (int r = 0; r < kBfLead; ++r) {  // register ring position = step % kBfLead: static. nk is even, so total is too.
             const uint32_t step = step0 + r;
-            const char* stage = s.A + (step % kBfStages) * kBfStageBytes;
+            const char* stage = s.A + (step % kBfStages) * G::kStage;
             issue_a();  // step + kBfStages - 2
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
-                bf16x8_t a[4];
+                bf16x8_t a[4], al[4];
 #pragma unroll
-                for (int rt = 0; rt < 4; ++rt)
-                    a[rt] = *reinterpret_cast<const bf16x8_t*>(stage + ((2 * m + (lane >> 5)) * 128 + rt * 32 + (lane & 31)) * 16);
+                for (int rt = 0; rt < 4; ++rt) {
+                    const int off = ((2 * m + (lane >> 5)) * 128 + rt * 32 + (lane & 31)) * 16;
+                    a[rt] = *reinterpret_cast<const bf16x8_t*>(stage + off);
+                    if (kSplit) al[rt] = *reinterpret_cast<const bf16x8_t*>(stage + kBfStageBytes + off);
+                }
                 // ops younger than this depth's operands (loaded kBfLead steps ago, right after the same depth's MFMAs):
-                // the rest of that step, kBfLead - 1 whole steps of 5, this step's DMA and (depth 1) depth 0's reload
-                constexpr int kYounger = 5 * kBfLead - 2;
-                if (m == 0) use_after<kYounger>(breg[r][0], breg[r][1]);
-                else use_after<kYounger>(breg[r][2], breg[r][3]);
-                const bf16x8_t b0 = __builtin_bit_cast(bf16x8_t, breg[r][2 * m]), b1 = __builtin_bit_cast(bf16x8_t, breg[r][2 * m + 1]);
+                // the rest of that step, kBfLead - 1 whole steps, this step's DMA and (depth 1) depth 0's reload --
+                // 8 of the 5 per step (bf16 filter), 16 of the 10 per step (split filter)
+                constexpr int kYounger = G::kPerStep * (kBfLead - 1) + G::kDma + G::kLoads;
+                u32x4_t* bm = &breg[r][kB * m];
+                use_after<kYounger>(bm[0], bm[1]);
+                if (kSplit) use_after<kYounger>(bm[2], bm[3]);
+                const bf16x8_t b0 = __builtin_bit_cast(bf16x8_t, bm[0]), b1 = __builtin_bit_cast(bf16x8_t, bm[1]);
+                if (kSplit) {
+                    // the two small products first; eight independent MFMAs between two that feed the same accumulator
+                    const bf16x8_t bl0 = __builtin_bit_cast(bf16x8_t, bm[2]), bl1 = __builtin_bit_cast(bf16x8_t, bm[3]);
+#pragma unroll
+                    for (int rt = 0; rt < 4; ++rt) {
+                        acc[rt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rt], bl0, acc[rt][0], 0, 0, 0);
+                        acc[rt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rt], bl1, acc[rt][1], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < 4; ++rt) {
+                        acc[rt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rt], b0, acc[rt][0], 0, 0, 0);
+                        acc[rt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rt], b1, acc[rt][1], 0, 0, 0);
+                    }
+                }
 #pragma unroll
                 for (int rt = 0; rt < 4; ++rt) {
                     acc[rt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rt], b0, acc[rt][0], 0, 0, 0);
                     acc[rt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rt], b1, acc[rt][1], 0, 0, 0);
                 }
-                issue_b(breg[r][2 * m], breg[r][2 * m + 1], m);  // the same registers, kBfLead steps ahead
+                issue_b(bm, m);  // the same registers, kBfLead steps ahead
                 __builtin_amdgcn_sched_barrier(0);
             }
             b_ks = (b_ks + 1 == nk) ? 0 : b_ks + 1;
@@ -254,11 +305,11 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
             // ONE barrier per kLead = 2 K-steps: between two barriers the block reads stages s, s + 1 and its DMAs write the
             // stages of steps s + 6, s + 7 -- last read two steps before the previous barrier, never one of the two in use.
             // At the barrier this wave's pieces of steps s + 2 and s + 3 must have landed: the younger one was issued at the
-            // top of step s - 3, with 4 + 5 (STAGES - 4) VMEM ops of this wave behind it (more after an epilogue: the wait
-            // is then only stricter). The waves of a SIMD drift apart inside the two-step window instead of meeting at a
+            // top of step s - 3, with 4 + 5 (STAGES - 4) VMEM ops of this wave behind it (split filter: the lo piece, with
+            // 8 + 10 (STAGES - 4); more after an epilogue: the wait is then only stricter). The waves of a SIMD drift apart inside the two-step window instead of meeting at a
             // barrier every 16 MFMAs.
             if (r == kBfLead - 1) {
-                wait_but_youngest<5 * (kBfStages - 4) + 4>();
+                wait_but_youngest<G::kPerStep * (kBfStages - 4) + G::kPerStep - G::kDma>();
                 __syncthreads();
             }
         }

@@ -47,7 +47,7 @@ int main(int argc, char** argv) {
         if (it == 0) CK(hipMemset(gs, 0, (Qpad * kSlotMul * KP + 2 * Qpad) * 4 /* slots, bounds, k-rule margins */));
         CK(hipMemset(err, 0, 4096));
         hipEventRecord(a);
-        gemm_bf16_filter_kernel<PROBE_R, 0><<<nqt * ns, 64 * kBfWaves>>>(Ab, Bb, ntiles, (uint32_t)N, nk, Qpad, nqt, 1, tps, lists, counts, KP, 0u /* k rule off */, err, gs,
+        gemm_bf16_filter_kernel<PROBE_R, 0, 1><<<nqt * ns, 64 * kBfWaves>>>(Ab, nullptr, Bb, ntiles, (uint32_t)N, nk, Qpad, nqt, 1, tps, lists, counts, KP, 0u /* k rule off */, err, gs,
                                                                       gs + Qpad * kSlotMul * KP, nullptr, 0);
         hipEventRecord(b); CK(hipEventSynchronize(b));
         float ms; hipEventElapsedTime(&ms, a, b);
