@@ -451,6 +451,34 @@ static innr_status launch_scan_filter(innr_batch* b, int metric, const float* dQ
     }
 }
 
+// A ragged group of an exact scan: rows [nreal, nql) of *q (row stride ldq) are zero queries, with a zero per-query value (*aux,
+// nullable: the norm / the code sum), whose results are dropped; *q and *aux then point at the padded copy
+static innr_status pad_queries(innr_ctx* c, size_t ldq, size_t D, uint32_t nql, uint32_t nreal, const float** q, const float** aux) {
+    const size_t row_bytes = ldq * sizeof(float);
+    INNR_TRY(c->q_pad.ensure(nql * row_bytes + nql * sizeof(float) + 16));
+    INNR_HIP_CHECK(hipMemsetAsync(c->q_pad.p, 0, nql * row_bytes + nql * sizeof(float), c->stream));
+    if (D)
+        INNR_HIP_CHECK(hipMemcpy2DAsync(c->q_pad.p, row_bytes, *q, row_bytes, D * sizeof(float), nreal, hipMemcpyDeviceToDevice, c->stream));
+    float* aux_pad = reinterpret_cast<float*>(c->q_pad.as<char>() + nql * row_bytes);
+    if (*aux) {
+        INNR_HIP_CHECK(hipMemcpyAsync(aux_pad, *aux, nreal * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        *aux = aux_pad;
+    }
+    *q = c->q_pad.as<float>();
+    return INNR_OK;
+}
+// ... and its end: the best KP per query slot over the scan's lists, the first kout of the nreal real queries written out
+static innr_status select_and_emit(innr_batch* b, uint32_t nslots, uint32_t nql, uint32_t cap, uint32_t KP, uint32_t nreal, size_t kout,
+                                   bool l2, uint64_t* d_out_idx, float* d_out_score) {
+    innr_ctx* c = b->ctx;
+    INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), nslots, nql, cap, KP, nql));
+    const uint32_t total = nreal * (uint32_t)kout;
+    emit_results_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(c->sel.as<uint64_t>(), KP, nreal, (uint32_t)kout, l2, b->index_base,
+                                                                    d_out_idx, d_out_score);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
 // Exact kNN for queries [q0, q0+nq) (row-major on device, stride ldq): results to d_out_* at row q0.
 // limit_n != 0: only the first limit_n vectors of the batch take part (the GEMM engine's threshold seeding).
 static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* dQ, size_t ldq, const float* dQn,
@@ -503,20 +531,7 @@ static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* 
         INNR_TRY(c->counts.ensure(nslots * nql * sizeof(uint32_t)));
         const float* q = dQ + (q0 + done) * ldq;
         const float* qn = dQn ? dQn + q0 + done : nullptr;
-        if (nreal < nql) {  // pad: rows [nreal, nql) are zero queries (and zero norms) whose results are dropped
-            const size_t row_bytes = ldq * sizeof(float);
-            INNR_TRY(c->q_pad.ensure(nql * row_bytes + nql * sizeof(float) + 16));
-            INNR_HIP_CHECK(hipMemsetAsync(c->q_pad.p, 0, nql * row_bytes + nql * sizeof(float), c->stream));
-            if (b->D)
-                INNR_HIP_CHECK(hipMemcpy2DAsync(c->q_pad.p, row_bytes, q, row_bytes, b->D * sizeof(float), nreal,
-                                                hipMemcpyDeviceToDevice, c->stream));
-            float* qn_pad = reinterpret_cast<float*>(c->q_pad.as<char>() + nql * row_bytes);
-            if (qn) {
-                INNR_HIP_CHECK(hipMemcpyAsync(qn_pad, qn, nreal * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-                qn = qn_pad;
-            }
-            q = c->q_pad.as<float>();
-        }
+        if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qn));
         ScanExt ext2 = ext;
         if (nreal < nql) ext2.nvalid = nreal;
         switch (qb) {
@@ -524,12 +539,8 @@ static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* 
             case 4: INNR_TRY(launch_scan_filter<4>(b, metric, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2)); break;
             default: INNR_TRY(launch_scan_filter<1>(b, metric, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2)); break;
         }
-        INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), (uint32_t)nslots, nql, cap, KP, nql));
-        const uint32_t total = nreal * (uint32_t)kout;
-        emit_results_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(
-            c->sel.as<uint64_t>(), KP, nreal, (uint32_t)kout, l2, b->index_base, d_out_idx + (q0 + done) * kout,
-            d_out_score + (q0 + done) * kout);
-        INNR_HIP_CHECK(hipGetLastError());
+        INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, l2, d_out_idx + (q0 + done) * kout,
+                                 d_out_score + (q0 + done) * kout));
         done += nreal;
     }
     return INNR_OK;
@@ -564,6 +575,12 @@ static innr_status prep_gthr(innr_ctx* c, size_t Qpad, uint32_t KP, const uint32
 // the final bounds of the last launch's queries (what the re-score proves against)
 static const uint32_t* gthr_bounds(const innr_ctx* c, size_t Qpad, uint32_t KP) { return c->gthr.as<uint32_t>() + Qpad * (size_t)kSlotMul * KP; }
 
+// The score space of a proof: rescore_kernel's MET, seed_thresholds_kernel's and kmargin_kernel's kind.
+enum ScoreSpace : int { kSpaceDot = 0, kSpaceCos = 1, kSpaceL2 = 2, kSpaceEq = 3, kSpaceCode = 4 };
+static ScoreSpace metric_space(int metric) {
+    return metric == INNR_METRIC_L2SQ ? kSpaceL2 : (metric == INNR_METRIC_COSINE ? kSpaceCos : kSpaceDot);
+}
+
 // E per query by kind -> the k rule's margin 2E (+ rounding room); +inf where E is not finite and for padding queries.
 // kind 0: err_scale * qnorm[j] (dot), 1: err_scale (cosine), 2: err_scale * aux[j] (squared L2 in score space, aux = C_j),
 // 3: eq[j] (int8 filter of an f32 corpus), 4: err_scale * qnorm[j] + 4.8e-7 |offset * qsum[j]| + eq[j] (code corpus; eq nullable)
@@ -585,7 +602,7 @@ __global__ void kmargin_kernel(int kind, float err_scale, const float* __restric
     }
     out[j] = m;
 }
-static innr_status make_kmargin(innr_ctx* c, int kind, float err_scale, const float* qnorm, const float* aux, const float* eq,
+static innr_status make_kmargin(innr_ctx* c, ScoreSpace kind, float err_scale, const float* qnorm, const float* aux, const float* eq,
                                 float offset, const float* qsum, size_t Q, size_t Qpad, const float** out) {
     *out = nullptr;
     if (c->tune.no_k_rule) return INNR_OK;
@@ -595,6 +612,82 @@ static innr_status make_kmargin(innr_ctx* c, int kind, float err_scale, const fl
     INNR_HIP_CHECK(hipGetLastError());
     *out = c->kmargin.as<float>();
     return INNR_OK;
+}
+
+// ---- exact re-score + proof of the selected lists (c->sel [Q][KP], c->sel_cnt [Q]) ----
+// the template arguments of the exact kernels: MET of a metric's score space, RK (rounds of candidates) of lists of KP
+template <int N> using IntC = std::integral_constant<int, N>;
+template <class F>
+static void with_space(ScoreSpace space, F&& f) {
+    if (space == kSpaceCos) f(IntC<kSpaceCos>());
+    else if (space == kSpaceL2) f(IntC<kSpaceL2>());
+    else f(IntC<kSpaceDot>());
+}
+template <class F>
+static void with_rk(uint32_t KP, F&& f) {
+    if (KP <= 64) f(IntC<1>());
+    else if (KP <= 128) f(IntC<2>());
+    else f(IntC<4>());
+}
+// f32 corpus (rescore_kernel); qaux: C_j in the squared-L2 space, eq: per-query bounds instead of err_scale (int8 filter)
+static innr_status launch_rescore(innr_batch* b, ScoreSpace space, const float* dQ, size_t Q, const float* qaux, uint32_t KP,
+                                  size_t kout, float err_scale, uint64_t* d_out_idx, float* d_out_score, uint32_t* fallback,
+                                  const float* eq, bool early, const uint32_t* gthr) {
+    innr_ctx* c = b->ctx;
+    const auto launch = [&](auto met) {
+        with_rk(KP, [&](auto rk) {
+            rescore_kernel<decltype(met)::value, decltype(rk)::value><<<(unsigned)Q, 64, 0, c->stream>>>(
+                b->V, b->ldN, (uint32_t)b->D, dQ, b->norms, c->q_norm.as<float>(), qaux, c->sel.as<uint64_t>(),
+                c->sel_cnt.as<uint32_t>(), KP, (uint32_t)kout, err_scale, b->index_base, d_out_idx, d_out_score, fallback, eq, early,
+                gthr);
+        });
+    };
+    with_space(space, launch);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+// u8 code corpus (rescore_u8_kernel); Ai8 / nk: the int8 filter's copy, eq its per-query quantisation share
+static innr_status launch_rescore_u8(innr_batch* b, const float* dQ, size_t Q, const float* qsum, const float* qnorm, uint32_t KP,
+                                     size_t kout, float err_scale, uint64_t* d_out_idx, float* d_out_score, uint32_t* fallback,
+                                     const float* eq, const uint4* Ai8, uint32_t nk, const uint32_t* gthr) {
+    innr_ctx* c = b->ctx;
+    with_rk(KP, [&](auto rk) {
+        rescore_u8_kernel<decltype(rk)::value><<<(unsigned)Q, 64, 0, c->stream>>>(
+            b->C8, b->ldN, (uint32_t)b->D, dQ, qsum, qnorm, b->alpha / 255.0f, b->offset, c->sel.as<uint64_t>(),
+            c->sel_cnt.as<uint32_t>(), KP, (uint32_t)kout, err_scale, b->index_base, d_out_idx, d_out_score, fallback, eq,
+            !c->tune.rescore_all, Ai8, nk, gthr);
+    });
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
+// The proof's harvest, after the re-score: the fallback flags come back on ONE synchronise (together with whatever else the caller
+// copied out before), *gemm_ms = the filter's time (ev[2] .. ev[3]). *redo: the queries whose proof failed or that the caller's
+// `unprovable(q)` names, ascending; *nfallback = their count, *kept = KP.
+struct NoGate {
+    bool operator()(size_t) const { return false; }
+};
+template <class Gate = NoGate>
+static innr_status harvest_proof(innr_ctx* c, const uint32_t* fallback, size_t Q, uint32_t KP, std::vector<uint32_t>* redo,
+                                 uint32_t* nfallback, uint32_t* kept, float* gemm_ms, Gate unprovable = Gate()) {
+    std::vector<uint32_t> fb(Q);
+    INNR_HIP_CHECK(copy_out(c, fb.data(), fallback, Q * sizeof(uint32_t)));
+    INNR_HIP_CHECK(ctx_sync(c));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms = ms;
+    redo->clear();
+    for (size_t q = 0; q < Q; ++q)
+        if (fb[q] || unprovable(q)) redo->push_back((uint32_t)q);
+    *nfallback = (uint32_t)redo->size();
+    *kept = KP;
+    return INNR_OK;
+}
+
+// the candidate lists of a GEMM-type launch: [nslices][Qpad][cap] entries, [nslices][Qpad] lengths (GemmPlan or I8Plan)
+template <class Plan>
+static innr_status ensure_lists(innr_ctx* c, const Plan& p) {
+    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
+    return c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t));
 }
 
 struct GemmPlan {
@@ -756,6 +849,26 @@ static innr_status knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t
                               float* d_out_score, uint32_t* nfallback, uint32_t* kept, float* gemm_ms, bool* served,
                               const float* collect_kth = nullptr, uint32_t* d_unresolved = nullptr);
 
+// A redo set's workspace, sized for its queries' rows, norms and results; the query map `redo` uploaded (a pageable host vector)
+static innr_status upload_redo(innr_ctx* c, innr_ctx::RedoBufs& rb, const std::vector<uint32_t>& redo, size_t D, size_t kout) {
+    const size_t nr = redo.size();
+    INNR_TRY(rb.map.ensure(nr * sizeof(uint32_t)));
+    INNR_TRY(rb.q.ensure(std::max<size_t>(nr * D, 1) * sizeof(float)));
+    INNR_TRY(rb.qn.ensure(nr * sizeof(float)));
+    INNR_TRY(rb.idx.ensure(nr * kout * sizeof(uint64_t)));
+    INNR_TRY(rb.sc.ensure(nr * kout * sizeof(float)));
+    INNR_HIP_CHECK(hipMemcpyAsync(rb.map.p, redo.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    INNR_HIP_CHECK(hipStreamSynchronize(c->stream));  // redo is a pageable host vector
+    return INNR_OK;
+}
+// ... and the way back: the set's results [nr][kout] scattered to the rows of the queries they belong to
+static innr_status scatter_redo(innr_ctx* c, innr_ctx::RedoBufs& rb, size_t nr, size_t kout, uint64_t* d_out_idx, float* d_out_score) {
+    scatter_results_kernel<<<(unsigned)((nr * kout + 255) / 256), 256, 0, c->stream>>>(
+        rb.idx.as<uint64_t>(), rb.sc.as<float>(), rb.map.as<uint32_t>(), (uint32_t)nr, (uint32_t)kout, d_out_idx, d_out_score);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
 // Queries whose margin proof failed (`redo`: their indices, ascending): gathered into ONE contiguous block and redone
 // together -- on the exact engine, 8 queries per corpus pass (via_gemm_kp == 0), or once more on the f32 GEMM engine
 // with lists of via_gemm_kp candidates (whose own unproven queries then take the exact engine) -- and scattered back.
@@ -772,13 +885,7 @@ static innr_status redo_batch(innr_batch* b, int metric, const float* dQ, const 
         return INNR_E_HIP;
     }
     innr_ctx::RedoBufs& rb = c->redo[level];  // the nested GEMM pass (level + 1) reads these while filling its own set
-    INNR_TRY(rb.map.ensure(nr * sizeof(uint32_t)));
-    INNR_TRY(rb.q.ensure(std::max<size_t>(nr * D, 1) * sizeof(float)));
-    INNR_TRY(rb.qn.ensure(nr * sizeof(float)));
-    INNR_TRY(rb.idx.ensure(nr * kout * sizeof(uint64_t)));
-    INNR_TRY(rb.sc.ensure(nr * kout * sizeof(float)));
-    INNR_HIP_CHECK(hipMemcpyAsync(rb.map.p, redo.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    INNR_HIP_CHECK(hipStreamSynchronize(c->stream));  // redo is a pageable host vector
+    INNR_TRY(upload_redo(c, rb, redo, D, kout));
     const uint32_t* map = rb.map.as<uint32_t>();
     if (D) {
         gather_rows_kernel<<<(unsigned)((nr * D + 255) / 256), 256, 0, c->stream>>>(dQ, map, (uint32_t)nr, (uint32_t)D,
@@ -799,10 +906,7 @@ static innr_status redo_batch(innr_batch* b, int metric, const float* dQ, const 
     } else {
         INNR_TRY(knn_exact_range(b, metric, rb.q.as<float>(), D, qn, 0, nr, kout, rb.idx.as<uint64_t>(), rb.sc.as<float>()));
     }
-    scatter_results_kernel<<<(unsigned)((nr * kout + 255) / 256), 256, 0, c->stream>>>(
-        rb.idx.as<uint64_t>(), rb.sc.as<float>(), map, (uint32_t)nr, (uint32_t)kout, d_out_idx, d_out_score);
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
+    return scatter_redo(c, rb, nr, kout, d_out_idx, d_out_score);
 }
 
 // ---- completion pass for queries whose margin proof failed (f32 GEMM engine) ------------------------------------------------
@@ -1037,13 +1141,7 @@ static innr_status collect_gather(innr_batch* b, const float* dQ, const std::vec
     innr_ctx* c = b->ctx;
     const size_t nr = redo.size(), D = b->D;
     innr_ctx::RedoBufs& rb = c->cmpl;  // its own set: a nested pass (redo_batch -> knn_mfma) runs while redo[level] is live
-    INNR_TRY(rb.map.ensure(nr * sizeof(uint32_t)));
-    INNR_TRY(rb.q.ensure(std::max<size_t>(nr * D, 1) * sizeof(float)));
-    INNR_TRY(rb.qn.ensure(nr * sizeof(float)));
-    INNR_TRY(rb.idx.ensure(nr * kout * sizeof(uint64_t)));
-    INNR_TRY(rb.sc.ensure(nr * kout * sizeof(float)));
-    INNR_HIP_CHECK(hipMemcpyAsync(rb.map.p, redo.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    INNR_HIP_CHECK(hipStreamSynchronize(c->stream));  // redo is a pageable host vector
+    INNR_TRY(upload_redo(c, rb, redo, D, kout));
     const uint32_t* map = rb.map.as<uint32_t>();
     gather_rows_kernel<<<(unsigned)((nr * D + 255) / 256), 256, 0, c->stream>>>(dQ, map, (uint32_t)nr, (uint32_t)D, rb.q.as<float>());
     INNR_HIP_CHECK(hipGetLastError());
@@ -1053,16 +1151,16 @@ static innr_status collect_gather(innr_batch* b, const float* dQ, const std::vec
 }
 // resolved rows back to their places; the unresolved ones (rewritten by the next engine afterwards) are listed
 static innr_status collect_scatter(innr_batch* b, const std::vector<uint32_t>& redo, size_t kout, uint64_t* d_out_idx, float* d_out_score,
-                                   const uint32_t* d_unres, std::vector<uint32_t>* unresolved) {
+                                   const uint32_t* d_unres, std::vector<uint32_t>* unresolved, float* gemm_ms) {
     innr_ctx* c = b->ctx;
     const size_t nr = redo.size();
     innr_ctx::RedoBufs& rb = c->cmpl;
     std::vector<uint32_t> un(nr);
     INNR_HIP_CHECK(copy_out(c, un.data(), d_unres, nr * sizeof(uint32_t)));
     INNR_HIP_CHECK(ctx_sync(c));
-    scatter_results_kernel<<<(unsigned)((nr * kout + 255) / 256), 256, 0, c->stream>>>(rb.idx.as<uint64_t>(), rb.sc.as<float>(), rb.map.as<uint32_t>(),
-                                                                                   (uint32_t)nr, (uint32_t)kout, d_out_idx, d_out_score);
-    INNR_HIP_CHECK(hipGetLastError());
+    float ms = 0.0f;  // the collect pass' filter time (ev[2] .. ev[3])
+    if (gemm_ms && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms += ms;
+    INNR_TRY(scatter_redo(c, rb, nr, kout, d_out_idx, d_out_score));
     unresolved->clear();
     for (size_t r = 0; r < nr; ++r)
         if (un[r]) unresolved->push_back(redo[r]);
@@ -1087,10 +1185,59 @@ static innr_status knn_complete_i8(innr_batch* b, int metric, const float* dQ, c
         *unresolved = redo;
         return INNR_OK;
     }
-    INNR_TRY(collect_scatter(b, redo, kout, d_out_idx, d_out_score, c->sel_cnt.as<uint32_t>(), unresolved));  // (synchronises)
-    float ms = 0.0f;
-    if (gemm_ms && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms += ms;
+    return collect_scatter(b, redo, kout, d_out_idx, d_out_score, c->sel_cnt.as<uint32_t>(), unresolved, gemm_ms);  // (synchronises)
+}
+
+// Squared L2 on the f32 engine, from the exact query norms (c->q_norm): the epilogue constants C_j - |q_j|^2 (in invq's place) and
+// *Cj = C_j (for the proof), at c->tmp_norms
+static innr_status l2_query_consts(innr_batch* b, size_t Qpad, size_t Q, float* invq, float** Cj) {
+    innr_ctx* c = b->ctx;
+    INNR_TRY(c->tmp_norms.ensure(Qpad * sizeof(float)));
+    *Cj = c->tmp_norms.as<float>();
+    l2_query_consts_kernel<<<(unsigned)((Qpad + 255) / 256), 256, 0, c->stream>>>(c->q_norm.as<float>(), Qpad, Q, b->max_norm, invq, *Cj);
+    INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
+}
+
+// ---- error bounds of the filters of an f32 corpus: err_scale, E = err_scale * |q| (dot), err_scale (cosine), err_scale * C_j (squared L2)
+// dot / cosine: |approx - exact| <= (2D+8) u (1+eps) * sum|q_d v_d|: u = 2^-24, Cauchy-Schwarz for the sum.
+// L2: approx = C - (|v|^2 - 2 q.v + |q|^2) assembled from the MFMA dot (<= (2D+8) u |q||v|, doubled), the squared
+// cached norms and the query norm (<= (D+4) u each, relative to their own size), three epilogue roundings, and the
+// reference's own direct-difference sum is within (D+2) u of the true distance: every term is <= C = (|q|+max|v|)^2,
+// so |(C - approx) - exact| <= (6D+40) u C with room to spare.
+static float f32_cdu(const innr_batch* b) { return 1.05f * (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f; }
+static float f32_filter_scale(const innr_batch* b, int metric) {
+    const float cdu = f32_cdu(b);
+    return metric == INNR_METRIC_L2SQ ? 1.05f * (6.0f * (float)b->D + 40.0f) * 5.9604645e-08f
+                                      : (metric == INNR_METRIC_COSINE ? cdu : cdu * b->max_norm);
+}
+// bf16 filter: both operands rounded to 8 significant bits (|delta| <= 2^-8 each): |q'v' - qv| <= (2^-7 + 2^-16) |qv|,
+// plus the f32 accumulation of the rounded products
+// (cosine: both sides normalised before the rounding, |q^||v^| <= (1 + D u)^2 -- inside the 1.05)
+// squared L2 on the bf16 filter, as a multiple of C = (|q| + max|v|)^2: the doubled bf16 dot is off by <= 2 (2^-7 + 2^-16) |q||v|
+// <= (2^-7 + 2^-16) C / 2; the f32 accumulation of D + 6 products whose absolute values sum to <= 2 C, the limbs' residuals,
+// the cached norms and c_j, and the reference's own direct-difference sum (within (D+2) u of the true distance) stay
+// inside (8D + 96) u C
+static float bf16_filter_scale(const innr_batch* b, int metric) {
+    return metric == INNR_METRIC_L2SQ
+               ? 1.05f * (0.00390625f * 1.004f + (8.0f * (float)b->D + 96.0f) * 5.9604645e-08f)
+               : 1.05f * (0.0078125f * 1.004f + (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.02f) *
+                     (metric == INNR_METRIC_COSINE ? 1.0f : b->max_norm);
+}
+// split-bf16 filter, per dimension x = qh + ql + rq, y = vh + vl + rv (h = rne_bf16, l = rne_bf16 of the exact
+// f32 difference; |h| <= (1 + 2^-8)|x|, |l| <= (1 + 2^-8) 2^-8 |x|, |r| <= 2^-16 |x|). The kernel sums qh vh + qh vl + ql vh; the
+// dropped part xy - that = ql vl + qh rv + rq vh + ql rv + rq vl + rq rv is <= (3 (1 + 2^-7) 2^-16 + 2^-23 + 2^-32) |xy| <= 3.1 2^-16 |xy|.
+// Every bf16 x bf16 product is exact in f32; their f32 accumulation on the matrix pipe -- the assumption the bf16 bound makes:
+// n products accumulate within (2n + 8) u of the sum of their magnitudes -- with n = 3D products whose magnitudes sum to
+// <= (1 + 2^-8)^2 (1 + 2^-7) sum|xy| <= 1.016 sum|xy|: (6D + 8) u 1.04 sum|xy|. Cauchy-Schwarz: sum|xy| <= |q| max|v|.
+// Values at the bottom of the range: a limb or product below 2^-126 may be flushed to zero, at most 2^-126 per flushed
+// operand times the other side (<= 2^-126 sqrt(D) (|q| + max|v|) over a row) plus 2^-126 per product or partial sum (6D of
+// them). With max|v| and |q| both in [1e-12, 1e18] (the gates of choose_f32_filter and of knn_mfma's proof; cosine: both
+// normalised, <= 1.0), and E >= 3 2^-16 |q| max|v|, that is below 1e-6 E -- inside the 1.05. A zero query is exact (every limb 0).
+// Cosine: |q^||v^| <= (1 + D u)^2.
+static float split_filter_scale(const innr_batch* b, int metric) {
+    return 1.05f * (3.1f * 1.52587890625e-05f + (6.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.04f) *
+           (metric == INNR_METRIC_COSINE ? 1.0f : b->max_norm);
 }
 
 // redo: the unproven queries (ascending), d_out_*: the first pass' output (its k-th score per query is read, the resolved
@@ -1112,18 +1259,12 @@ static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, cons
     INNR_TRY(prep_queries(b, p, Qr, nr, cos));  // K-major queries, exact norms (c->q_norm), cosine: 1/|q| at c->misc
     float* invq = c->misc.as<float>();
     float* Cj = nullptr;
-    if (l2) {
-        INNR_TRY(c->tmp_norms.ensure(p.Qpad * sizeof(float)));
-        Cj = c->tmp_norms.as<float>();
-        l2_query_consts_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(c->q_norm.as<float>(), p.Qpad, nr, b->max_norm, invq, Cj);
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    const float cdu = 1.05f * (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f;  // the f32 engine's bounds (knn_mfma)
-    const float err_scale = l2 ? 1.05f * (6.0f * (float)b->D + 40.0f) * 5.9604645e-08f : (cos ? cdu : cdu * b->max_norm);
+    if (l2) INNR_TRY(l2_query_consts(b, p.Qpad, nr, invq, &Cj));
+    const float err_scale = f32_filter_scale(b, metric);
     // fixed thresholds: x_k - E (one key lower), in the kind's score space; 0 = "no bound" where that is not finite
     INNR_TRY(c->seed_score.ensure(p.Qpad * sizeof(uint32_t)));
     uint32_t* thr = c->seed_score.as<uint32_t>();
-    seed_thresholds_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(kth, (uint32_t)nr, 1u, l2 ? 2 : (cos ? 1 : 0), err_scale,
+    seed_thresholds_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(kth, (uint32_t)nr, 1u, metric_space(metric), err_scale,
                                                                                     c->q_norm.as<float>(), Cj, thr, (uint32_t)p.Qpad, 0u);
     INNR_HIP_CHECK(hipGetLastError());
     // global lists: [Qpad][kCollectCap] indices, [Qpad] lengths
@@ -1139,10 +1280,7 @@ static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, cons
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_TRY(c->sel_cnt.ensure(nr * sizeof(uint32_t)));
     INNR_TRY(collect_finish(b, metric, Qr, c->q_norm.as<float>(), nr, kout, rb.idx.as<uint64_t>(), rb.sc.as<float>(), c->sel_cnt.as<uint32_t>()));
-    INNR_TRY(collect_scatter(b, redo, kout, d_out_idx, d_out_score, c->sel_cnt.as<uint32_t>(), unresolved));  // (synchronises)
-    float ms = 0.0f;
-    if (gemm_ms && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms += ms;
-    return INNR_OK;
+    return collect_scatter(b, redo, kout, d_out_idx, d_out_score, c->sel_cnt.as<uint32_t>(), unresolved, gemm_ms);  // (synchronises)
 }
 
 enum { kBfDot = 0, kBfCos = 1, kBfL2 = 2 };  // which bf16 copy of the corpus a call filters on
@@ -1291,19 +1429,37 @@ static size_t seed_prefix_rows(const innr_ctx* c, bool fast_pipe, size_t Q) {
     return v >= 256 ? (size_t)v : (size_t)((fast_pipe && Q <= 2048) ? 4096 : 2048);
 }
 
-static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q, size_t kout, const float* /*dQn*/,
-                            uint64_t* d_out_idx, float* d_out_score, uint32_t* nfallback, uint32_t* kept,
-                            float* gemm_ms, bool bf16, uint32_t kp_force, int level) {
+// threshold seeding from the exact top-k of a corpus prefix (seed_thresholds_*kernel): corpora of 32 prefixes or more, lists <= 128
+static bool seeding_on(const innr_batch* b, bool fast_pipe, size_t Q, uint32_t KP) {
+    return b->N >= 32 * seed_prefix_rows(b->ctx, fast_pipe, Q) && KP <= 128 && !b->ctx->tune.gemm_no_seed;
+}
+// The prefix's exact top-kseed per query at c->seed_score [Q][kseed], best first, by exact(kseed, idx, score, rows) (the caller's
+// exact engine over the first `rows` vectors); *sd: room for the [Qpad] thresholds the caller's kernel derives from them.
+template <class ExactTopK>
+static innr_status seed_prefix(innr_batch* b, bool fast_pipe, size_t Q, size_t Qpad, uint32_t KP, size_t kout, uint32_t* kseed,
+                               uint32_t** sd, ExactTopK&& exact) {
+    innr_ctx* c = b->ctx;
+    // k rule (topk_dev.h): the prefix's k-th best exact score, less E, already bounds the corpus' top k; KP rule: its KP-th
+    const uint32_t ks = c->tune.no_k_rule ? KP : (uint32_t)kout;
+    INNR_TRY(c->seed_idx.ensure(Q * ks * sizeof(uint64_t)));
+    INNR_TRY(c->seed_score.ensure(Q * ks * sizeof(float) + Qpad * sizeof(uint32_t)));
+    INNR_TRY(exact(ks, c->seed_idx.as<uint64_t>(), c->seed_score.as<float>(), seed_prefix_rows(c, fast_pipe, Q)));
+    *kseed = ks;
+    *sd = reinterpret_cast<uint32_t*>(c->seed_score.as<float>() + Q * ks);
+    return INNR_OK;
+}
+
+// knn_mfma's filter (kFilterBf16 / kFilterSplit / kFilterF32), its plan (list length included) and its bound err_scale
+static innr_status choose_f32_filter(innr_batch* b, int metric, size_t Q, size_t kout, bool bf16, uint32_t kp_force, int level,
+                                     int* filter, GemmPlan* plan, float* err_scale) {
     innr_ctx* c = b->ctx;
     const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
-    INNR_TRY(ensure_norms(b));  // exact norms: cosine epilogue + max norm for the dot / L2 error bounds
     // bf16 filter: every kind as the plain dot of bf16 copies (cosine: corpus and queries NORMALISED before the rounding;
     // squared L2: six more K columns carry |v|^2 and the query's constant, pack_corpus_bf16_kernel) -- no norm is loaded in
     // the kernel; candidate lists of 4k + 64 (its bound E is ~2^-7 |q||v|, so the k-th exact score must clear the KP-th
     // approximate one by a visible margin), a corpus whose scores are far from the denormal range (L2: and from overflow)
     const bool use_bf16 = bf16 && pick_kp(4 * kout + 64, 0) <= 256 && b->max_norm >= 1e-12f &&
                           (b->max_norm - b->max_norm == 0.0f) && (!l2 || b->max_norm <= 1e15f);
-    const int bfv = cos ? kBfCos : (l2 ? kBfL2 : kBfDot);
     // split-bf16 filter: dot and cosine from kSplitMinQ queries on, lists up to 256, a corpus whose norm keeps
     // the limbs' flush-to-zero terms far below E (or a non-finite one: every query is redone exactly below either way)
     const bool mfin = b->max_norm - b->max_norm == 0.0f;
@@ -1314,7 +1470,8 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
         if (cos) INNR_TRY(ensure_invnorms(b));
         INNR_TRY(ensure_split_corpus(b, cos, &use_split));  // does not fit: the f32 kernel
     }
-    if (level == 0) c->last_filter = use_bf16 ? kFilterBf16 : (use_split ? kFilterSplit : kFilterF32);
+    *filter = use_bf16 ? kFilterBf16 : (use_split ? kFilterSplit : kFilterF32);
+    if (level == 0) c->last_filter = *filter;
     GemmPlan p = plan_gemm(b, Q, kout, (use_bf16 || use_split) ? 8 : 0, !cos && !l2);
     if (kp_force && !use_bf16 && kp_force >= p.KP && kp_force <= 256) {  // second attempt of redo_batch: longer lists
         p.KP = kp_force;
@@ -1324,25 +1481,33 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
         p.KP = pick_kp(4 * kout + 64, 0);
         p.cap = (uint32_t)cand_cap((int)p.KP);
     }
+    *plan = p;
+    *err_scale = use_bf16 ? bf16_filter_scale(b, metric) : use_split ? split_filter_scale(b, metric) : f32_filter_scale(b, metric);
+    return INNR_OK;
+}
+
+static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q, size_t kout, const float* /*dQn*/,
+                            uint64_t* d_out_idx, float* d_out_score, uint32_t* nfallback, uint32_t* kept,
+                            float* gemm_ms, bool bf16, uint32_t kp_force, int level) {
+    innr_ctx* c = b->ctx;
+    const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
+    INNR_TRY(ensure_norms(b));  // exact norms: cosine epilogue + max norm for the dot / L2 error bounds
+    int filter;
+    GemmPlan p;
+    float err_scale;
+    INNR_TRY(choose_f32_filter(b, metric, Q, kout, bf16, kp_force, level, &filter, &p, &err_scale));
+    const bool use_bf16 = filter == kFilterBf16, use_split = filter == kFilterSplit;
+    const int bfv = cos ? kBfCos : (l2 ? kBfL2 : kBfDot);
     if (cos) INNR_TRY(ensure_invnorms(b));
     if (l2) INNR_TRY(ensure_sqnorms(b));
     INNR_TRY(prep_queries(b, p, dQ, Q, cos));  // K-major queries, exact query norms (c->q_norm), cosine: 1/||q|| at c->misc
     if (use_bf16) INNR_TRY(ensure_bf16_corpus(b, bfv));
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
-    INNR_TRY(c->sel.ensure(Q * p.KP * sizeof(uint64_t)));
-    INNR_TRY(c->sel_cnt.ensure(Q * sizeof(uint32_t)));
+    INNR_TRY(ensure_lists(c, p));
     float* invq = c->misc.as<float>();
     uint32_t* fallback = reinterpret_cast<uint32_t*>(c->misc.as<char>() + p.Qpad * sizeof(float));
     INNR_HIP_CHECK(hipMemsetAsync(fallback, 0, Q * sizeof(uint32_t), c->stream));
     float* Cj = nullptr;
-    if (l2) {  // epilogue constants C_j - |q_j|^2 (in invq's place) and C_j (for the proof)
-        INNR_TRY(c->tmp_norms.ensure(p.Qpad * sizeof(float)));
-        Cj = c->tmp_norms.as<float>();
-        l2_query_consts_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(c->q_norm.as<float>(), p.Qpad, Q,
-                                                                                       b->max_norm, invq, Cj);
-        INNR_HIP_CHECK(hipGetLastError());
-    }
+    if (l2) INNR_TRY(l2_query_consts(b, p.Qpad, Q, invq, &Cj));
     if (use_bf16) {  // (after the L2 constants: the squared-L2 packing carries c_j = C_j - |q_j|^2 in three K columns)
         const uint32_t nk = bf16_nk(b, bfv);
         INNR_TRY(c->q_bf16.ensure((size_t)nk * 4 * p.Qpad * 16));
@@ -1353,62 +1518,24 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     }
     if (use_split) INNR_TRY(pack_queries_split(b, p, dQ, Q, cos ? c->misc.as<float>() : nullptr));
 
-    // dot / cosine: |approx - exact| <= (2D+8) u (1+eps) * sum|q_d v_d|: u = 2^-24, Cauchy-Schwarz for the sum.
-    // L2: approx = C - (|v|^2 - 2 q.v + |q|^2) assembled from the MFMA dot (<= (2D+8) u |q||v|, doubled), the squared
-    // cached norms and the query norm (<= (D+4) u each, relative to their own size), three epilogue roundings, and the
-    // reference's own direct-difference sum is within (D+2) u of the true distance: every term is <= C = (|q|+max|v|)^2,
-    // so |(C - approx) - exact| <= (6D+40) u C with room to spare.
-    const float cdu = 1.05f * (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f;
-    // bf16 filter: both operands rounded to 8 significant bits (|delta| <= 2^-8 each): |q'v' - qv| <= (2^-7 + 2^-16) |qv|,
-    // plus the f32 accumulation of the rounded products
-    // (cosine: both sides normalised before the rounding, |q^||v^| <= (1 + D u)^2 -- inside the 1.05)
-    // squared L2 on the bf16 filter, as a multiple of C = (|q| + max|v|)^2: the doubled bf16 dot is off by <= 2 (2^-7 + 2^-16) |q||v|
-    // <= (2^-7 + 2^-16) C / 2; the f32 accumulation of D + 6 products whose absolute values sum to <= 2 C, the limbs' residuals,
-    // the cached norms and c_j, and the reference's own direct-difference sum (within (D+2) u of the true distance) stay
-    // inside (8D + 96) u C
-    const float bf16_scale = l2 ? 1.05f * (0.00390625f * 1.004f + (8.0f * (float)b->D + 96.0f) * 5.9604645e-08f)
-                                : 1.05f * (0.0078125f * 1.004f + (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.02f) * (cos ? 1.0f : b->max_norm);
-    // split-bf16 filter, per dimension x = qh + ql + rq, y = vh + vl + rv (h = rne_bf16, l = rne_bf16 of the exact
-    // f32 difference; |h| <= (1 + 2^-8)|x|, |l| <= (1 + 2^-8) 2^-8 |x|, |r| <= 2^-16 |x|). The kernel sums qh vh + qh vl + ql vh; the
-    // dropped part xy - that = ql vl + qh rv + rq vh + ql rv + rq vl + rq rv is <= (3 (1 + 2^-7) 2^-16 + 2^-23 + 2^-32) |xy| <= 3.1 2^-16 |xy|.
-    // Every bf16 x bf16 product is exact in f32; their f32 accumulation on the matrix pipe -- the assumption the bf16 bound makes:
-    // n products accumulate within (2n + 8) u of the sum of their magnitudes -- with n = 3D products whose magnitudes sum to
-    // <= (1 + 2^-8)^2 (1 + 2^-7) sum|xy| <= 1.016 sum|xy|: (6D + 8) u 1.04 sum|xy|. Cauchy-Schwarz: sum|xy| <= |q| max|v|.
-    // Values at the bottom of the range: a limb or product below 2^-126 may be flushed to zero, at most 2^-126 per flushed
-    // operand times the other side (<= 2^-126 sqrt(D) (|q| + max|v|) over a row) plus 2^-126 per product or partial sum (6D of
-    // them). With max|v| and |q| both in [1e-12, 1e18] (the gates above and below; cosine: both normalised, <= 1.0), and E >= 3 2^-16
-    // |q| max|v|, that is below 1e-6 E -- inside the 1.05. A zero query is exact (every limb 0). Cosine: |q^||v^| <= (1 + D u)^2.
-    const float split_scale = 1.05f * (3.1f * 1.52587890625e-05f + (6.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.04f) *
-                              (cos ? 1.0f : b->max_norm);
-    const float err_scale = use_bf16 ? bf16_scale : use_split ? split_scale
-                                     : (l2 ? 1.05f * (6.0f * (float)b->D + 40.0f) * 5.9604645e-08f : (cos ? cdu : cdu * b->max_norm));
-
-    // threshold seeding from the exact top-KP of a corpus prefix (seed_thresholds_kernel)
     const uint32_t* seed = nullptr;
-    const size_t kSeedN = seed_prefix_rows(c, use_bf16, Q);
-    if (b->N >= 32 * kSeedN && p.KP <= 128 && !c->tune.gemm_no_seed) {
-        // k rule (topk_dev.h): the prefix's k-th best exact score, less E, already bounds the corpus' top k; KP rule: its KP-th
-        const uint32_t kseed = c->tune.no_k_rule ? p.KP : (uint32_t)kout;
-        INNR_TRY(c->seed_idx.ensure(Q * kseed * sizeof(uint64_t)));
-        INNR_TRY(c->seed_score.ensure(Q * kseed * sizeof(float) + p.Qpad * sizeof(uint32_t)));
-        INNR_TRY(knn_exact_range(b, metric, dQ, b->D, c->q_norm.as<float>(), 0, Q, kseed, c->seed_idx.as<uint64_t>(),
-                                 c->seed_score.as<float>(), ScanExt(), kSeedN));
-        uint32_t* sd = reinterpret_cast<uint32_t*>(c->seed_score.as<float>() + Q * kseed);
+    if (seeding_on(b, use_bf16, Q, p.KP)) {
+        uint32_t kseed, *sd;
+        INNR_TRY(seed_prefix(b, use_bf16, Q, p.Qpad, p.KP, kout, &kseed, &sd, [&](uint32_t ks, uint64_t* idx, float* sc, size_t rows) {
+            return knn_exact_range(b, metric, dQ, b->D, c->q_norm.as<float>(), 0, Q, ks, idx, sc, ScanExt(), rows);
+        }));
         seed_thresholds_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(
-            c->seed_score.as<float>(), (uint32_t)Q, kseed, l2 ? 2 : (cos ? 1 : 0), err_scale, c->q_norm.as<float>(), Cj, sd,
+            c->seed_score.as<float>(), (uint32_t)Q, kseed, metric_space(metric), err_scale, c->q_norm.as<float>(), Cj, sd,
             (uint32_t)p.Qpad, kseed - 1);
         INNR_HIP_CHECK(hipGetLastError());
         seed = sd;
-        // the exact engine used the shared list / selection workspace: size it for the GEMM pass again
-        INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-        INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
-        INNR_TRY(c->sel.ensure(Q * p.KP * sizeof(uint64_t)));
-        INNR_TRY(c->sel_cnt.ensure(Q * sizeof(uint32_t)));
+        // the exact engine used the shared list workspace: size it for the GEMM pass again
+        INNR_TRY(ensure_lists(c, p));
     }
 
     // the k rule of topk_dev.h: 2E per query, in the score space of the kind
     const float* kmargin = nullptr;
-    INNR_TRY(make_kmargin(c, l2 ? 2 : (cos ? 1 : 0), err_scale, c->q_norm.as<float>(), Cj, nullptr, 0.0f, nullptr, Q, p.Qpad, &kmargin));
+    INNR_TRY(make_kmargin(c, metric_space(metric), err_scale, c->q_norm.as<float>(), Cj, nullptr, 0.0f, nullptr, Q, p.Qpad, &kmargin));
     const uint32_t kk = (uint32_t)kout;
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     if (use_bf16) INNR_TRY(launch_gemm_bf16(b, p, Q, seed, bfv, kmargin, kk));
@@ -1422,45 +1549,23 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
 
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP,
                         (uint32_t)Q));
+    INNR_TRY(launch_rescore(b, metric_space(metric), dQ, Q, Cj, p.KP, kout, err_scale, d_out_idx, d_out_score, fallback, nullptr,
+                            !c->tune.rescore_all, gthr_bounds(c, p.Qpad, p.KP)));
 
-#define INNR_RESCORE(METV, RKV)                                                                                     \
-    rescore_kernel<METV, RKV><<<(unsigned)Q, 64, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->D, dQ, b->norms,          \
-                                                                 c->q_norm.as<float>(), Cj, c->sel.as<uint64_t>(),  \
-                                                                 c->sel_cnt.as<uint32_t>(), p.KP, (uint32_t)kout,   \
-                                                                 err_scale, b->index_base, d_out_idx, d_out_score,  \
-                                                                 fallback, nullptr, !c->tune.rescore_all, gthr_bounds(c, p.Qpad, p.KP))
-    const int rk = p.KP <= 64 ? 1 : (p.KP <= 128 ? 2 : 4);
-    if (cos) {
-        if (rk == 1) INNR_RESCORE(1, 1); else if (rk == 2) INNR_RESCORE(1, 2); else INNR_RESCORE(1, 4);
-    } else if (l2) {
-        if (rk == 1) INNR_RESCORE(2, 1); else if (rk == 2) INNR_RESCORE(2, 2); else INNR_RESCORE(2, 4);
-    } else {
-        if (rk == 1) INNR_RESCORE(0, 1); else if (rk == 2) INNR_RESCORE(0, 2); else INNR_RESCORE(0, 4);
-    }
-#undef INNR_RESCORE
-    INNR_HIP_CHECK(hipGetLastError());
-
-    std::vector<uint32_t> fb(Q);
     std::vector<float> qn_host((use_bf16 || use_split) && !cos ? Q : 0);
-    INNR_HIP_CHECK(copy_out(c, fb.data(), fallback, Q * sizeof(uint32_t)));
-    if (!qn_host.empty()) INNR_HIP_CHECK(copy_out(c, qn_host.data(), c->q_norm.p, Q * sizeof(float)));
-    INNR_HIP_CHECK(ctx_sync(c));
+    if (!qn_host.empty()) INNR_HIP_CHECK(copy_out(c, qn_host.data(), c->q_norm.p, Q * sizeof(float)));  // (the harvest synchronises)
     // bf16 products / sums below the normal range may be flushed to zero: the bound E must dwarf that, else redo exactly
-    // (split filter: the query-side gate of its bound, see split_scale)
-    for (size_t q = 0; q < qn_host.size(); ++q)
-        if (use_bf16 ? !(qn_host[q] * b->max_norm >= 1e-25f) : !(qn_host[q] == 0.0f || (qn_host[q] >= 1e-12f && qn_host[q] <= 1e18f)))
-            fb[q] = 1;
+    // (split filter: the query-side gate of its bound, see split_filter_scale).
     // A non-finite corpus value (max_norm is then NaN or inf) voids every error bound -- for cosine too, whose bound does
     // not carry max_norm: NaN * 0 approximations can differ from the reference's 0.0 (batch.rs:722) by more than E.
-    if (!(b->max_norm - b->max_norm == 0.0f))
-        for (size_t q = 0; q < Q; ++q) fb[q] = 1;
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms = ms;
-    std::vector<uint32_t> redo;
-    for (size_t q = 0; q < Q; ++q)
-        if (fb[q]) redo.push_back((uint32_t)q);  // margin proof failed (near-tie at the cut, or non-finite scores)
-    *nfallback = (uint32_t)redo.size();
-    *kept = p.KP;
+    const bool mfin = b->max_norm - b->max_norm == 0.0f;
+    const auto unprovable = [&](size_t q) {
+        if (!mfin) return true;
+        if (q >= qn_host.size()) return false;
+        return use_bf16 ? !(qn_host[q] * b->max_norm >= 1e-25f) : !(qn_host[q] == 0.0f || (qn_host[q] >= 1e-12f && qn_host[q] <= 1e18f));
+    };
+    std::vector<uint32_t> redo;  // margin proof failed (near-tie at the cut, or non-finite scores)
+    INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms, unprovable));
     // f32 engine: ONE completion pass resolves what the first pass could not prove (knn_complete); a handful of queries is
     // cheaper on the exact engine (one 8-query corpus pass costs less than a GEMM pass over a 256-query tile)
     bool completed = false;
@@ -1799,8 +1904,7 @@ innr_status innrdbg_gemm_scores(innr_batch* b, int metric, const float* queries,
     INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
     INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
     INNR_TRY(prep_queries(b, p, c->q_row.as<float>(), Q, cos));
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
+    INNR_TRY(ensure_lists(c, p));
     INNR_TRY(c->scores.ensure(p.Qpad * b->ldN * sizeof(float)));
     if (cos) INNR_TRY((launch_gemm<kGemmCos, 1>(b, p, Q, c->q_kmajor.as<float>(), b->invn, c->misc.as<float>(),
                                             c->scores.as<float>(), b->ldN)));
@@ -1831,8 +1935,7 @@ innr_status innrdbg_split_scores(innr_batch* b, int metric, const float* queries
     INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
     INNR_TRY(prep_queries(b, p, c->q_row.as<float>(), Q, cos));
     INNR_TRY(pack_queries_split(b, p, c->q_row.as<float>(), Q, cos ? c->misc.as<float>() : nullptr));
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
+    INNR_TRY(ensure_lists(c, p));
     INNR_TRY(c->scores.ensure(p.Qpad * b->ldN * sizeof(float)));
     INNR_TRY(launch_gemm_split<1>(b, p, Q, cos, nullptr, nullptr, 0, c->scores.as<float>(), b->ldN));
     INNR_HIP_CHECK(hipMemcpy2DAsync(out, b->N * sizeof(float), c->scores.p, b->ldN * sizeof(float),
@@ -1868,6 +1971,19 @@ innr_status innr_batch_rerank_dev(innr_batch* b, int metric, const float* d_quer
     const size_t kout = std::min(k, kc);
     innr_ctx* c = b->ctx;
     INNR_ENTER(c);
+    uint32_t* bad = c->flags.as<uint32_t>() + 65;  // set by the kernels for a candidate outside the batch
+    const auto finish = [&]() -> innr_status {
+        uint32_t hbad = 0;
+        INNR_HIP_CHECK(copy_out(c, &hbad, bad, 4));
+        INNR_HIP_CHECK(ctx_sync(c));
+        if (hbad) {
+            set_error("rerank: a candidate index lies outside this batch's range [%llu, %llu)",
+                      (unsigned long long)b->index_base, (unsigned long long)(b->index_base + b->N));
+            return INNR_E_BAD_ARG;
+        }
+        *out_k = kout;
+        return INNR_OK;
+    };
     if (kc > 256) {
         // More candidates per query than a candidate list holds: exact scores of all of them (one thread per candidate,
         // the reference's arithmetic order), then the best k of every query's kc composites, best first (radix select + sort per
@@ -1887,38 +2003,20 @@ innr_status innr_batch_rerank_dev(innr_batch* b, int metric, const float* d_quer
         query_norms_kernel<<<(unsigned)Q, 64, 0, c->stream>>>(d_queries, (uint32_t)Q, (uint32_t)D, D,
                                                                            c->q_norm.as<float>());
         INNR_HIP_CHECK(hipGetLastError());
-        uint32_t* bad = c->flags.as<uint32_t>() + 65;
         uint64_t* keys = c->sort_keys.as<uint64_t>();
         const unsigned nb = (unsigned)((Q * kc + 255) / 256);
-        const int met = metric == INNR_METRIC_COSINE ? 1 : (metric == INNR_METRIC_L2SQ ? 2 : 0);
-        if (met == 1)
-            rerank_scores_kernel<1><<<nb, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)D, d_queries, b->norms,
-                                                              c->q_norm.as<float>(), d_cand, (uint32_t)Q, (uint32_t)kc,
-                                                              b->index_base, keys, bad);
-        else if (met == 2)
-            rerank_scores_kernel<2><<<nb, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)D, d_queries, b->norms,
-                                                              c->q_norm.as<float>(), d_cand, (uint32_t)Q, (uint32_t)kc,
-                                                              b->index_base, keys, bad);
-        else
-            rerank_scores_kernel<0><<<nb, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)D, d_queries, b->norms,
-                                                              c->q_norm.as<float>(), d_cand, (uint32_t)Q, (uint32_t)kc,
-                                                              b->index_base, keys, bad);
+        with_space(metric_space(metric), [&](auto met) {
+            rerank_scores_kernel<decltype(met)::value><<<nb, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)D, d_queries,
+                                                                                  b->norms, c->q_norm.as<float>(), d_cand, (uint32_t)Q,
+                                                                                  (uint32_t)kc, b->index_base, keys, bad);
+        });
         INNR_HIP_CHECK(hipGetLastError());
         INNR_HIP_CHECK(segmented_topk_keys(keys, keys + Q * kc, Q, kc, kout, keys + 2 * Q * kc, c->sort_tmp.p, c->stream));
         const uint32_t total = (uint32_t)(Q * kout);
         emit_results_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(keys + Q * kc, (uint32_t)kc, (uint32_t)Q, (uint32_t)kout,
-                                                                        met == 2, b->index_base, d_out_idx, d_out_score);
+                                                                        metric == INNR_METRIC_L2SQ, b->index_base, d_out_idx, d_out_score);
         INNR_HIP_CHECK(hipGetLastError());
-        uint32_t hbad = 0;
-        INNR_HIP_CHECK(copy_out(c, &hbad, bad, 4));
-        INNR_HIP_CHECK(ctx_sync(c));
-        if (hbad) {
-            set_error("rerank: a candidate index lies outside this batch's range [%llu, %llu)",
-                      (unsigned long long)b->index_base, (unsigned long long)(b->index_base + b->N));
-            return INNR_E_BAD_ARG;
-        }
-        *out_k = kout;
-        return INNR_OK;
+        return finish();
     }
     const uint32_t KP = pick_kp(kc, 0);  // 32..256
     INNR_TRY(c->sel.ensure(Q * KP * sizeof(uint64_t)));
@@ -1930,40 +2028,15 @@ innr_status innr_batch_rerank_dev(innr_batch* b, int metric, const float* d_quer
     query_norms_kernel<<<(unsigned)Q, 64, 0, c->stream>>>(d_queries, (uint32_t)Q, (uint32_t)D, D,
                                                                        c->q_norm.as<float>());
     INNR_HIP_CHECK(hipGetLastError());
-    uint32_t* bad = c->flags.as<uint32_t>() + 65;
     rerank_prepare_kernel<<<(unsigned)((Q * KP + 255) / 256), 256, 0, c->stream>>>(d_cand, (uint32_t)Q, (uint32_t)kc, KP,
                                                                                   (uint32_t)b->N, b->index_base,
                                                                                   c->sel.as<uint64_t>(),
                                                                                   c->sel_cnt.as<uint32_t>(), bad);
     INNR_HIP_CHECK(hipGetLastError());
     uint32_t* unused = c->misc.as<uint32_t>();  // the proof flags of the kNN path: no proof to make here (cnt < KP or moot)
-#define INNR_RERANK(METV, RKV)                                                                                       \
-    rescore_kernel<METV, RKV><<<(unsigned)Q, 64, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->D, d_queries, b->norms,   \
-                                                                 c->q_norm.as<float>(), c->q_norm.as<float>(),       \
-                                                                 c->sel.as<uint64_t>(), c->sel_cnt.as<uint32_t>(), KP, \
-                                                                 (uint32_t)kout, 0.0f, b->index_base, d_out_idx,     \
-                                                                 d_out_score, unused)
-    const int rk = KP <= 64 ? 1 : (KP <= 128 ? 2 : 4);
-    const int met = metric == INNR_METRIC_COSINE ? 1 : (metric == INNR_METRIC_L2SQ ? 2 : 0);
-    if (met == 1) {
-        if (rk == 1) INNR_RERANK(1, 1); else if (rk == 2) INNR_RERANK(1, 2); else INNR_RERANK(1, 4);
-    } else if (met == 2) {
-        if (rk == 1) INNR_RERANK(2, 1); else if (rk == 2) INNR_RERANK(2, 2); else INNR_RERANK(2, 4);
-    } else {
-        if (rk == 1) INNR_RERANK(0, 1); else if (rk == 2) INNR_RERANK(0, 2); else INNR_RERANK(0, 4);
-    }
-#undef INNR_RERANK
-    INNR_HIP_CHECK(hipGetLastError());
-    uint32_t hbad = 0;
-    INNR_HIP_CHECK(copy_out(c, &hbad, bad, 4));
-    INNR_HIP_CHECK(ctx_sync(c));
-    if (hbad) {
-        set_error("rerank: a candidate index lies outside this batch's range [%llu, %llu)",
-                  (unsigned long long)b->index_base, (unsigned long long)(b->index_base + b->N));
-        return INNR_E_BAD_ARG;
-    }
-    *out_k = kout;
-    return INNR_OK;
+    INNR_TRY(launch_rescore(b, metric_space(metric), d_queries, Q, c->q_norm.as<float>(), KP, kout, 0.0f, d_out_idx, d_out_score, unused,
+                            nullptr, false, nullptr));
+    return finish();
 }
 
 innr_status innr_batch_rerank(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const uint64_t* cand,
@@ -2160,6 +2233,45 @@ static innr_status knn_full_sort(innr_batch* b, int metric, const float* dQ, siz
 static bool f32_i8_eligible(const innr_batch* b, int metric, size_t Q, size_t kout);
 static size_t f32_i8_copy_bytes(const innr_batch* b, int metric);
 
+// The end of a kNN call (ev[0] was recorded at its start): the device error flag, *out_k and the stats
+static innr_status finish_knn(innr_ctx* c, int engine, size_t kout, uint32_t nfallback, uint32_t kept, float gemm_ms, size_t* out_k,
+                              innr_knn_stats* stats) {
+    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
+    INNR_TRY(check_errflag(c));
+    *out_k = kout;
+    if (stats) {
+        stats->engine = engine;
+        stats->queries_fallback = nfallback;
+        stats->candidates_kept = kept;
+        stats->gemm_ms = gemm_ms;
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
+    }
+    if (engine == INNR_KNN_MFMA_I8 && i8h_probe_skips_visits()) {
+        set_error("this library is a timing build (-DINNR_I8H_PROBE): the int8 filter kernel skipped its visits, the call's results are not valid");
+        return INNR_E_UNSUPPORTED;
+    }
+    return INNR_OK;
+}
+
+// A kNN call on host memory: the queries staged on the device, dev(d_queries, d_out_idx, d_out_score) (a *_dev entry point, room
+// for `cap` results per query), then *out_k results per query copied back
+template <class Dev>
+static innr_status knn_from_host(innr_ctx* c, const float* queries, size_t Q, size_t D, size_t cap, uint64_t* out_idx,
+                                 float* out_score, const size_t* out_k, Dev&& dev) {
+    INNR_ENTER(c);
+    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
+    INNR_TRY(c->out_idx.ensure(Q * cap * sizeof(uint64_t)));
+    INNR_TRY(c->out_score.ensure(Q * cap * sizeof(float)));
+    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
+    INNR_TRY(dev(c->q_row.as<float>(), c->out_idx.as<uint64_t>(), c->out_score.as<float>()));
+    if (*out_k) {
+        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, Q * *out_k * sizeof(uint64_t)));
+        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * *out_k * sizeof(float)));
+        INNR_HIP_CHECK(ctx_sync(c));
+    }
+    return INNR_OK;
+}
 
 extern "C" {
 
@@ -2255,22 +2367,7 @@ innr_status innr_batch_knn_dev(innr_batch* b, int metric, const float* d_queries
         INNR_TRY(knn_exact_range(b, metric, d_queries, D, dQn, 0, Q, kout, d_out_idx, d_out_score));
         kept = pick_kp(kout, 0);
     }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
-    INNR_TRY(check_errflag(c));
-    *out_k = kout;
-    if (stats) {
-        stats->engine = engine;
-        stats->queries_fallback = nfallback;
-        stats->candidates_kept = kept;
-        stats->gemm_ms = gemm_ms;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
-    }
-    if (engine == INNR_KNN_MFMA_I8 && i8h_probe_skips_visits()) {
-        set_error("this library is a timing build (-DINNR_I8H_PROBE): the int8 filter kernel skipped its visits, the call's results are not valid");
-        return INNR_E_UNSUPPORTED;
-    }
-    return INNR_OK;
+    return finish_knn(c, engine, kout, nfallback, kept, gemm_ms, out_k, stats);
 }
 
 innr_status innr_batch_knn(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, size_t k, int engine,
@@ -2288,21 +2385,9 @@ innr_status innr_batch_knn(innr_batch* b, int metric, const float* queries, size
     *out_k = 0;
     if (b->N == 0 || k == 0 || Q == 0) return INNR_OK;
     if (!queries && D) return INNR_E_BAD_ARG;
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    const size_t kout = std::min(k, b->N);
-    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
-    INNR_TRY(c->out_idx.ensure(Q * kout * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(Q * kout * sizeof(float)));
-    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
-    INNR_TRY(innr_batch_knn_dev(b, metric, c->q_row.as<float>(), Q, D, k, engine, c->out_idx.as<uint64_t>(),
-                                c->out_score.as<float>(), out_k, stats));
-    if (*out_k) {
-        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, Q * kout * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * kout * sizeof(float)));
-        INNR_HIP_CHECK(ctx_sync(c));
-    }
-    return INNR_OK;
+    return knn_from_host(b->ctx, queries, Q, D, std::min(k, b->N), out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
+        return innr_batch_knn_dev(b, metric, dQ, Q, D, k, engine, di, ds, out_k, stats);
+    });
 }
 
 }  // extern "C"  (the u8 section has templates and static helpers; its entry points get C linkage from the header)
@@ -2650,27 +2735,12 @@ static innr_status knn_u8_exact_range(innr_batch* b, const float* dQ, size_t ldq
         INNR_TRY(c->counts.ensure(nslots * nql * sizeof(uint32_t)));
         const float* q = dQ + (q0 + done) * ldq;
         const float* qs = qsum + q0 + done;
-        if (nreal < nql) {
-            const size_t row_bytes = ldq * sizeof(float);
-            INNR_TRY(c->q_pad.ensure(nql * row_bytes + nql * sizeof(float) + 16));
-            INNR_HIP_CHECK(hipMemsetAsync(c->q_pad.p, 0, nql * row_bytes + nql * sizeof(float), c->stream));
-            if (b->D)
-                INNR_HIP_CHECK(hipMemcpy2DAsync(c->q_pad.p, row_bytes, q, row_bytes, b->D * sizeof(float), nreal,
-                                                hipMemcpyDeviceToDevice, c->stream));
-            float* qs_pad = reinterpret_cast<float*>(c->q_pad.as<char>() + nql * row_bytes);
-            INNR_HIP_CHECK(hipMemcpyAsync(qs_pad, qs, nreal * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            q = c->q_pad.as<float>();
-            qs = qs_pad;
-        }
+        if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qs));
         if (qb == 8) INNR_TRY(launch_scan_u8<8>(b, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu));
         else if (qb == 4) INNR_TRY(launch_scan_u8<4>(b, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu));
         else INNR_TRY(launch_scan_u8<1>(b, q, ldq, qs, nblocks, KP, cap, cps, 1, limit_n));
-        INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), (uint32_t)nslots, nql, cap, KP, nql));
-        const uint32_t total = nreal * (uint32_t)kout;
-        emit_results_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(c->sel.as<uint64_t>(), KP, nreal, (uint32_t)kout, false,
-                                                                        b->index_base, d_out_idx + (q0 + done) * kout,
-                                                                        d_out_score + (q0 + done) * kout);
-        INNR_HIP_CHECK(hipGetLastError());
+        INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, false, d_out_idx + (q0 + done) * kout,
+                                 d_out_score + (q0 + done) * kout));
         done += nreal;
     }
     return INNR_OK;
@@ -2684,13 +2754,7 @@ static innr_status redo_batch_u8(innr_batch* b, const float* dQ, const float* qs
     if (nr == 0) return INNR_OK;
     if (nr == 1) return knn_u8_exact_range(b, dQ, D, qsum, redo[0], 1, kout, d_out_idx, d_out_score);
     innr_ctx::RedoBufs& rb = c->redo[0];
-    INNR_TRY(rb.map.ensure(nr * sizeof(uint32_t)));
-    INNR_TRY(rb.q.ensure(std::max<size_t>(nr * D, 1) * sizeof(float)));
-    INNR_TRY(rb.qn.ensure(nr * sizeof(float)));
-    INNR_TRY(rb.idx.ensure(nr * kout * sizeof(uint64_t)));
-    INNR_TRY(rb.sc.ensure(nr * kout * sizeof(float)));
-    INNR_HIP_CHECK(hipMemcpyAsync(rb.map.p, redo.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    INNR_HIP_CHECK(hipStreamSynchronize(c->stream));  // redo is a pageable host vector
+    INNR_TRY(upload_redo(c, rb, redo, D, kout));
     const uint32_t* map = rb.map.as<uint32_t>();
     if (D) {
         gather_rows_kernel<<<(unsigned)((nr * D + 255) / 256), 256, 0, c->stream>>>(dQ, map, (uint32_t)nr, (uint32_t)D,
@@ -2700,10 +2764,13 @@ static innr_status redo_batch_u8(innr_batch* b, const float* dQ, const float* qs
     gather_f32_kernel<<<(unsigned)((nr + 255) / 256), 256, 0, c->stream>>>(qsum, map, (uint32_t)nr, rb.qn.as<float>());
     INNR_HIP_CHECK(hipGetLastError());
     INNR_TRY(knn_u8_exact_range(b, rb.q.as<float>(), D, rb.qn.as<float>(), 0, nr, kout, rb.idx.as<uint64_t>(), rb.sc.as<float>()));
-    scatter_results_kernel<<<(unsigned)((nr * kout + 255) / 256), 256, 0, c->stream>>>(
-        rb.idx.as<uint64_t>(), rb.sc.as<float>(), map, (uint32_t)nr, (uint32_t)kout, d_out_idx, d_out_score);
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
+    return scatter_redo(c, rb, nr, kout, d_out_idx, d_out_score);
+}
+
+// error bound of the filters of a u8 corpus: |approx - exact| <= a255 * (2D+12) u * ||q|| * max||c||, with ||c|| <= 255 sqrt(D)
+static float u8_filter_scale(const innr_batch* b) {
+    const float a255 = b->alpha / 255.0f;
+    return 1.05f * fabsf(a255) * (2.0f * (float)b->D + 12.0f) * 5.9604645e-08f * 255.0f * sqrtf((float)b->D);
 }
 
 // GEMM engine on a u8 corpus ("path B": codes widened to f32 in registers, f32 MFMA), same structure as knn_mfma
@@ -2723,39 +2790,19 @@ static innr_status knn_u8_mfma(innr_batch* b, const float* dQ, size_t Q, size_t 
     INNR_HIP_CHECK(hipGetLastError());
     uint32_t* fallback = reinterpret_cast<uint32_t*>(c->misc.as<char>() + p.Qpad * sizeof(float));
     INNR_HIP_CHECK(hipMemsetAsync(fallback, 0, Q * sizeof(uint32_t), c->stream));
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
-    const float a255 = b->alpha / 255.0f;
-    // |approx - exact| <= a255 * (2D+12) u * ||q|| * max||c||, with ||c|| <= 255 sqrt(D)
-    const float err_scale = 1.05f * fabsf(a255) * (2.0f * (float)b->D + 12.0f) * 5.9604645e-08f * 255.0f * sqrtf((float)b->D);
+    INNR_TRY(ensure_lists(c, p));
+    const float err_scale = u8_filter_scale(b);
     const float* kmargin = nullptr;
-    INNR_TRY(make_kmargin(c, 4, err_scale, qnorm, nullptr, nullptr, b->offset, qsum, Q, p.Qpad, &kmargin));
+    INNR_TRY(make_kmargin(c, kSpaceCode, err_scale, qnorm, nullptr, nullptr, b->offset, qsum, Q, p.Qpad, &kmargin));
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     INNR_TRY((launch_gemm<kGemmU8, 0>(b, p, Q, c->q_kmajor.as<float>(), nullptr, oq, nullptr, 0, nullptr, kmargin, (uint32_t)kout)));
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP,
                         (uint32_t)Q));
-#define INNR_RESCORE_U8(RKV)                                                                                          \
-    rescore_u8_kernel<RKV><<<(unsigned)Q, 64, 0, c->stream>>>(b->C8, b->ldN, (uint32_t)b->D, dQ, qsum, qnorm, a255, b->offset, \
-                                                              c->sel.as<uint64_t>(), c->sel_cnt.as<uint32_t>(), p.KP,   \
-                                                              (uint32_t)kout, err_scale, b->index_base, d_out_idx,      \
-                                                              d_out_score, fallback, nullptr, !c->tune.rescore_all, nullptr, 0, \
-                                                              gthr_bounds(c, p.Qpad, p.KP))
-    if (p.KP <= 64) INNR_RESCORE_U8(1);
-    else if (p.KP <= 128) INNR_RESCORE_U8(2);
-    else INNR_RESCORE_U8(4);
-#undef INNR_RESCORE_U8
-    INNR_HIP_CHECK(hipGetLastError());
-    std::vector<uint32_t> fb(Q);
-    INNR_HIP_CHECK(copy_out(c, fb.data(), fallback, Q * sizeof(uint32_t)));
-    INNR_HIP_CHECK(ctx_sync(c));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms = ms;
+    INNR_TRY(launch_rescore_u8(b, dQ, Q, qsum, qnorm, p.KP, kout, err_scale, d_out_idx, d_out_score, fallback, nullptr, nullptr, 0,
+                               gthr_bounds(c, p.Qpad, p.KP)));
     std::vector<uint32_t> redo;
-    for (size_t q = 0; q < Q; ++q)
-        if (fb[q]) redo.push_back((uint32_t)q);
-    *nfallback = (uint32_t)redo.size();
-    *kept = p.KP;
+    INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms));
     return redo_batch_u8(b, dQ, qsum, redo, kout, d_out_idx, d_out_score);
 }
 
@@ -2957,8 +3004,7 @@ static innr_status knn_u8_i8(innr_batch* b, const float* dQ, size_t Q, size_t ko
     innr_ctx* c = b->ctx;
     INNR_TRY(ensure_i8_corpus(b));
     I8Plan p = plan_i8(b, Q, kout);
-    const size_t kSeedN = seed_prefix_rows(c, true, Q);
-    const bool seeded = b->N >= 32 * kSeedN && p.KP <= 128 && !c->tune.gemm_no_seed;
+    const bool seeded = seeding_on(b, true, Q, p.KP);
     if (!plan_i8_small(b, &p, Q, seeded) && seeded && p.KP < 128 && Q <= 1024) {
         // the small-batch kernel is instantiated for lists of 128: a small k takes them too (a capacity, not a threshold -- the k
         // rule sets the bounds) rather than the 512-query tile
@@ -2969,54 +3015,34 @@ static innr_status knn_u8_i8(innr_batch* b, const float* dQ, size_t Q, size_t ko
     const float* qc = c->misc.as<float>();
     uint32_t* fallback = reinterpret_cast<uint32_t*>(c->misc.as<char>() + 5 * p.Qpad * sizeof(float));
     INNR_HIP_CHECK(hipMemsetAsync(fallback, 0, Q * sizeof(uint32_t), c->stream));
-    const float a255 = b->alpha / 255.0f;
     // the reference's own f32 accumulation against the true sum: (D + 2) u ||q|| max||c||, ||c|| <= 255 sqrt(D) (the bound of
     // knn_u8_mfma, whose MFMA-chain half is simply unused here); the query's quantisation share comes per query (qc[3])
-    const float err_scale = 1.05f * fabsf(a255) * (2.0f * (float)b->D + 12.0f) * 5.9604645e-08f * 255.0f * sqrtf((float)b->D);
-    // threshold seeding (cf. knn_mfma): the exact top-KP of a 2048-document prefix per query; their KP-th exact score
-    // lowered by the query's error bound is a valid chip-wide bound from the first tile on
+    const float err_scale = u8_filter_scale(b);
+    // threshold seeding: the prefix's k-th (KP-th) exact score lowered by the query's error bound is a valid chip-wide bound
+    // from the first tile on
     const uint32_t* seed = nullptr;
     if (seeded) {
-        const uint32_t kseed = c->tune.no_k_rule ? p.KP : (uint32_t)kout;  // (see knn_mfma)
-        INNR_TRY(c->seed_idx.ensure(Q * kseed * sizeof(uint64_t)));
-        INNR_TRY(c->seed_score.ensure(Q * kseed * sizeof(float) + p.Qpad * sizeof(uint32_t)));
-        INNR_TRY(knn_u8_exact_range(b, dQ, b->D, qsum, 0, Q, kseed, c->seed_idx.as<uint64_t>(), c->seed_score.as<float>(), kSeedN));
-        uint32_t* sd = reinterpret_cast<uint32_t*>(c->seed_score.as<float>() + Q * kseed);
+        uint32_t kseed, *sd;
+        INNR_TRY(seed_prefix(b, true, Q, p.Qpad, p.KP, kout, &kseed, &sd, [&](uint32_t ks, uint64_t* idx, float* sc, size_t rows) {
+            return knn_u8_exact_range(b, dQ, b->D, qsum, 0, Q, ks, idx, sc, rows);
+        }));
         seed_thresholds_u8_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(
             c->seed_score.as<float>(), (uint32_t)Q, kseed, err_scale, qnorm, qsum, b->offset, qc + 3 * p.Qpad, sd, (uint32_t)p.Qpad,
             kseed - 1);
         INNR_HIP_CHECK(hipGetLastError());
         seed = sd;
     }
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
+    INNR_TRY(ensure_lists(c, p));
     const float* kmargin = nullptr;
-    INNR_TRY(make_kmargin(c, 4, err_scale, qnorm, nullptr, qc + 3 * p.Qpad, b->offset, qsum, Q, p.Qpad, &kmargin));
+    INNR_TRY(make_kmargin(c, kSpaceCode, err_scale, qnorm, nullptr, qc + 3 * p.Qpad, b->offset, qsum, Q, p.Qpad, &kmargin));
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     INNR_TRY(launch_gemm_i8<0>(b, p, Q, qc, nullptr, 0, seed, nullptr, kmargin, (uint32_t)kout));
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP, (uint32_t)Q));
-#define INNR_RESCORE_U8(RKV)                                                                                          \
-    rescore_u8_kernel<RKV><<<(unsigned)Q, 64, 0, c->stream>>>(b->C8, b->ldN, (uint32_t)b->D, dQ, qsum, qnorm, a255, b->offset, \
-                                                              c->sel.as<uint64_t>(), c->sel_cnt.as<uint32_t>(), p.KP,   \
-                                                              (uint32_t)kout, err_scale, b->index_base, d_out_idx,      \
-                                                              d_out_score, fallback, qc + 3 * p.Qpad, !c->tune.rescore_all,  \
-                                                              reinterpret_cast<const uint4*>(b->Ai8), b->ai8_nk, gthr_bounds(c, p.Qpad, p.KP))
-    if (p.KP <= 64) INNR_RESCORE_U8(1);
-    else if (p.KP <= 128) INNR_RESCORE_U8(2);
-    else INNR_RESCORE_U8(4);
-#undef INNR_RESCORE_U8
-    INNR_HIP_CHECK(hipGetLastError());
-    std::vector<uint32_t> fb(Q);
-    INNR_HIP_CHECK(copy_out(c, fb.data(), fallback, Q * sizeof(uint32_t)));
-    INNR_HIP_CHECK(ctx_sync(c));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms = ms;
+    INNR_TRY(launch_rescore_u8(b, dQ, Q, qsum, qnorm, p.KP, kout, err_scale, d_out_idx, d_out_score, fallback, qc + 3 * p.Qpad,
+                               reinterpret_cast<const uint4*>(b->Ai8), b->ai8_nk, gthr_bounds(c, p.Qpad, p.KP)));
     std::vector<uint32_t> redo;
-    for (size_t q = 0; q < Q; ++q)
-        if (fb[q]) redo.push_back((uint32_t)q);
-    *nfallback = (uint32_t)redo.size();
-    *kept = p.KP;
+    INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms));
     return redo_batch_u8(b, dQ, qsum, redo, kout, d_out_idx, d_out_score);
 }
 
@@ -3037,8 +3063,7 @@ extern "C" innr_status innrdbg_i8_scores(innr_batch* b, const float* queries, si
     float* qsum = c->q_norm.as<float>();
     query_sums_kernel<<<(unsigned)((Q + 63) / 64), 64, 0, c->stream>>>(c->q_row.as<float>(), (uint32_t)Q, (uint32_t)D, D, qsum, qsum + p.Qpad);
     INNR_TRY(prep_queries_i8(b, p, c->q_row.as<float>(), Q, qsum, b->alpha, b->offset));
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
+    INNR_TRY(ensure_lists(c, p));
     INNR_TRY(c->scores.ensure(p.Qpad * b->ldN * sizeof(float)));
     INNR_TRY(launch_gemm_i8<1>(b, p, Q, c->misc.as<float>(), c->scores.as<float>(), b->ldN));
     INNR_HIP_CHECK(hipMemcpy2DAsync(out, b->N * sizeof(float), c->scores.p, b->ldN * sizeof(float), b->N * sizeof(float), Q,
@@ -3165,8 +3190,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     const bool direct = direct_kp <= 128;
     I8Plan p = plan_i8(b, Q, kout, collect_kth ? 32u : (direct ? direct_kp : std::max(128u, pick_kp(kout, 16))), collect_kth != nullptr);
     if (l2) p.nk = b->ai8l_nk;
-    const size_t kSeedN = seed_prefix_rows(c, true, Q);
-    const bool seeded = b->N >= 32 * kSeedN && p.KP <= 128 && !c->tune.gemm_no_seed;
+    const bool seeded = seeding_on(b, true, Q, p.KP);
     (void)plan_i8_small(b, &p, Q, seeded, collect_kth != nullptr);
     // exact query norms; cosine: 1/||q|| and the normalised copy the filter multiplies; sum and L1 norm of what it multiplies
     INNR_TRY(c->q_norm.ensure(p.Qpad * sizeof(float)));
@@ -3204,7 +3228,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     INNR_TRY(prep_queries_i8(b, p, Qp, Q, qsum, alpha, offset, Dq));
     float* qc = c->misc.as<float>();
     // the reference's own accumulation against the true dot: (D + 2) u |q||v| (half of the f32 GEMM engine's cdu)
-    const float cdu = 1.05f * (2.0f * (float)b->D + 8.0f) * 5.9604645e-08f;
+    const float cdu = f32_cdu(b);
     // (squared L2: the corpus' quantisation touches the 2 q_d only -- the |v|^2 limbs are exact integers, their encoding error and
     //  the f32 terms are f32i8_l2_finish_kernel's)
     f32i8_finish_bound_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, c->stream>>>(qc, (uint32_t)p.Qpad, (uint32_t)Q, l2 ? ql1q : ql1, c->q_norm.as<float>(),
@@ -3218,7 +3242,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
         const float K0 = W * offset + w2 * (offset + 0.5f * alpha);
         const float enc_err = b->i8l_nmax * (1.1f / 130050.0f + 3.0e-7f * (fabsf(offset) / alpha + 1.0f));
         f32i8_l2_finish_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, c->stream>>>(qc, (uint32_t)p.Qpad, (uint32_t)Q, cq, Cj, K0, enc_err,
-                                                                                1.05f * (6.0f * (float)b->D + 40.0f) * 5.9604645e-08f);
+                                                                                f32_filter_scale(b, metric));
         INNR_HIP_CHECK(hipGetLastError());
     }
     const float* eq = qc + 3 * p.Qpad;
@@ -3244,53 +3268,26 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     }
     const uint32_t* seed = nullptr;
     if (seeded) {
-        const uint32_t kseed = c->tune.no_k_rule ? p.KP : (uint32_t)kout;  // (see knn_mfma)
-        INNR_TRY(c->seed_idx.ensure(Q * kseed * sizeof(uint64_t)));
-        INNR_TRY(c->seed_score.ensure(Q * kseed * sizeof(float) + p.Qpad * sizeof(uint32_t)));
-        INNR_TRY(knn_exact_range(b, metric, dQ, b->D, c->q_norm.as<float>(), 0, Q, kseed, c->seed_idx.as<uint64_t>(),
-                                 c->seed_score.as<float>(), ScanExt(), kSeedN));
-        uint32_t* sd = reinterpret_cast<uint32_t*>(c->seed_score.as<float>() + Q * kseed);
+        uint32_t kseed, *sd;
+        INNR_TRY(seed_prefix(b, true, Q, p.Qpad, p.KP, kout, &kseed, &sd, [&](uint32_t ks, uint64_t* idx, float* sc, size_t rows) {
+            return knn_exact_range(b, metric, dQ, b->D, c->q_norm.as<float>(), 0, Q, ks, idx, sc, ScanExt(), rows);
+        }));
         seed_thresholds_eq_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(c->seed_score.as<float>(), (uint32_t)Q, kseed, eq, sd,
                                                                                        (uint32_t)p.Qpad, kseed - 1, l2 ? Cj : nullptr);
         INNR_HIP_CHECK(hipGetLastError());
         seed = sd;
     }
-    INNR_TRY(c->lists.ensure((size_t)p.nslices * p.Qpad * p.cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure((size_t)p.nslices * p.Qpad * sizeof(uint32_t)));
-    INNR_TRY(c->sel.ensure(Q * p.KP * sizeof(uint64_t)));
-    INNR_TRY(c->sel_cnt.ensure(Q * sizeof(uint32_t)));
+    INNR_TRY(ensure_lists(c, p));
     const float* kmargin = nullptr;
-    INNR_TRY(make_kmargin(c, 3, 0.0f, nullptr, nullptr, eq, 0.0f, nullptr, Q, p.Qpad, &kmargin));
+    INNR_TRY(make_kmargin(c, kSpaceEq, 0.0f, nullptr, nullptr, eq, 0.0f, nullptr, Q, p.Qpad, &kmargin));
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     INNR_TRY(launch_gemm_i8<0>(b, p, Q, qc, nullptr, 0, seed, copy, kmargin, (uint32_t)kout));
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP, (uint32_t)Q));
-#define INNR_RESCORE_EQ(METV, RKV)                                                                                   \
-    rescore_kernel<METV, RKV><<<(unsigned)Q, 64, 0, c->stream>>>(b->V, b->ldN, (uint32_t)b->D, dQ, b->norms,           \
-                                                                 c->q_norm.as<float>(), l2 ? Cj : nullptr, c->sel.as<uint64_t>(), \
-                                                                 c->sel_cnt.as<uint32_t>(), p.KP, (uint32_t)kout, 0.0f, \
-                                                                 b->index_base, d_out_idx, d_out_score, fallback, eq,   \
-                                                                 !c->tune.rescore_all, gthr_bounds(c, p.Qpad, p.KP))
-    const int rk = p.KP <= 64 ? 1 : (p.KP <= 128 ? 2 : 4);
-    if (cos) {
-        if (rk == 1) INNR_RESCORE_EQ(1, 1); else if (rk == 2) INNR_RESCORE_EQ(1, 2); else INNR_RESCORE_EQ(1, 4);
-    } else if (l2) {
-        if (rk == 1) INNR_RESCORE_EQ(2, 1); else if (rk == 2) INNR_RESCORE_EQ(2, 2); else INNR_RESCORE_EQ(2, 4);
-    } else {
-        if (rk == 1) INNR_RESCORE_EQ(0, 1); else if (rk == 2) INNR_RESCORE_EQ(0, 2); else INNR_RESCORE_EQ(0, 4);
-    }
-#undef INNR_RESCORE_EQ
-    INNR_HIP_CHECK(hipGetLastError());
-    std::vector<uint32_t> fb(Q);
-    INNR_HIP_CHECK(copy_out(c, fb.data(), fallback, Q * sizeof(uint32_t)));
-    INNR_HIP_CHECK(ctx_sync(c));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) *gemm_ms = ms;
+    INNR_TRY(launch_rescore(b, metric_space(metric), dQ, Q, l2 ? Cj : nullptr, p.KP, kout, 0.0f, d_out_idx, d_out_score, fallback, eq,
+                            !c->tune.rescore_all, gthr_bounds(c, p.Qpad, p.KP)));
     std::vector<uint32_t> redo;
-    for (size_t q = 0; q < Q; ++q)
-        if (fb[q]) redo.push_back((uint32_t)q);
-    *nfallback = (uint32_t)redo.size();
-    *kept = p.KP;
+    INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms));
     // (lists sized for a direct proof that mostly fail: the corpus' range is blown up by outliers; AUTO takes the bf16 filter,
     //  whose error is relative, on this corpus from now on -- and looks at the int8 one again every 64th call, innr_batch_knn_dev)
     if (direct && Q >= 16) (cos ? b->i8n_weak : (l2 ? b->i8l_weak : b->i8_weak)) = redo.size() * 2 > Q;
@@ -3360,22 +3357,7 @@ innr_status innr_batch_knn_u8_dev(innr_batch* b, const float* d_queries, size_t 
     } else {
         INNR_TRY(knn_u8_exact_range(b, d_queries, D, qsum, 0, Q, kout, d_out_idx, d_out_score));
     }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
-    INNR_TRY(check_errflag(c));
-    *out_k = kout;
-    if (stats) {
-        stats->engine = engine;
-        stats->queries_fallback = nfallback;
-        stats->candidates_kept = kept;
-        stats->gemm_ms = gemm_ms;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
-    }
-    if (engine == INNR_KNN_MFMA_I8 && i8h_probe_skips_visits()) {
-        set_error("this library is a timing build (-DINNR_I8H_PROBE): the int8 filter kernel skipped its visits, the call's results are not valid");
-        return INNR_E_UNSUPPORTED;
-    }
-    return INNR_OK;
+    return finish_knn(c, engine, kout, nfallback, kept, gemm_ms, out_k, stats);
 }
 
 innr_status innr_batch_knn_u8(innr_batch* b, const float* queries, size_t Q, size_t D, size_t k, int engine,
@@ -3387,21 +3369,9 @@ innr_status innr_batch_knn_u8(innr_batch* b, const float* queries, size_t Q, siz
     INNR_TRY(u8_check(b, D));
     if (Q == 0) return INNR_OK;
     if (!queries && D) return INNR_E_BAD_ARG;
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    const size_t kout = std::min(k, b->N);
-    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
-    INNR_TRY(c->out_idx.ensure(Q * kout * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(Q * kout * sizeof(float)));
-    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
-    INNR_TRY(innr_batch_knn_u8_dev(b, c->q_row.as<float>(), Q, D, k, engine, c->out_idx.as<uint64_t>(),
-                                   c->out_score.as<float>(), out_k, stats));
-    if (*out_k) {
-        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, Q * kout * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * kout * sizeof(float)));
-        INNR_HIP_CHECK(ctx_sync(c));
-    }
-    return INNR_OK;
+    return knn_from_host(b->ctx, queries, Q, D, std::min(k, b->N), out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
+        return innr_batch_knn_u8_dev(b, dQ, Q, D, k, engine, di, ds, out_k, stats);
+    });
 }
 
 // ---- maxsim over a document corpus (maxsim.rs) -------------------------------------------------------------
@@ -4660,20 +4630,9 @@ innr_status innr_sharded_knn(innr_comm* cm, innr_batch* shard, int metric, const
     *out_k = 0;
     if (Q == 0 || k == 0) return INNR_OK;
     if ((!queries && D) || !out_idx || !out_score) return INNR_E_BAD_ARG;
-    innr_ctx* c = cm->ctx;
-    INNR_ENTER(c);
-    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
-    INNR_TRY(c->out_idx.ensure(Q * k * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(Q * k * sizeof(float)));
-    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
-    INNR_TRY(innr_sharded_knn_dev(cm, shard, metric, c->q_row.as<float>(), Q, D, k, engine, c->out_idx.as<uint64_t>(),
-                                  c->out_score.as<float>(), out_k, stats));
-    if (*out_k) {
-        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, Q * *out_k * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * *out_k * sizeof(float)));
-        INNR_HIP_CHECK(ctx_sync(c));
-    }
-    return INNR_OK;
+    return knn_from_host(cm->ctx, queries, Q, D, k, out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
+        return innr_sharded_knn_dev(cm, shard, metric, dQ, Q, D, k, engine, di, ds, out_k, stats);
+    });
 }
 
 // maxsim over a document corpus range-partitioned across the ranks (maxsim.rs:96-137 per document; SURVEY.md 8e "same scheme

@@ -132,7 +132,7 @@ def test_split_nonfinite_rows(B, innr, ctx_option, metric):
 def _bound_check(vb, innr, rows, qs, metric):
     D = rows.shape[1]
     u = 2.0 ** -24
-    rel = 1.05 * (3.1 * 2.0 ** -16 + (6 * D + 8) * u * 1.04)  # api.hip split_scale, before |q| max|v|
+    rel = 1.05 * (3.1 * 2.0 ** -16 + (6 * D + 8) * u * 1.04)  # api.hip split_filter_scale, before |q| max|v|
     got = _split_scores(vb, innr.METRIC_DOT if metric == "dot" else innr.METRIC_COSINE, qs).astype(np.float64)
     if metric == "cos":
         # the filter's operands: rows and queries scaled by their f32 inverse norms (inv_norms_kernel / inv_qnorms_kernel)
