@@ -108,7 +108,8 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * the environment ONCE, in innr_ctx_create (INNR_<NAME IN CAPITALS>); no call reads the environment afterwards. Names:
  * gemm_waves, gemm_blocks_per_cu, gemm_qt_group, gemm_seed_n, gemm_no_seed, gemm_no_kp_retry, i8_two_limb, no_auto_bf16,
  * no_auto_i8, u8_no_i8, rescore_all, maxsim_generic, no_k_rule, no_completion, no_rows_copy, i8_slices_per_cu, i8_no_small, i8_no_small4, i8_small_max_q, i8_small_free, trace, fail_local_search (a test
- * switch of the sharded calls) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
+ * switch of the sharded calls), filter_keep_selection (default 1; 0: innr_batch_knn_filtered_multi frees its selection at the end
+ * of every call) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
 const char* innr_last_error(void);
@@ -248,6 +249,27 @@ innr_status innr_batch_dimension_variance(innr_batch* b, float* out);
  * *out_k = min(k, number passing); indices refer to the original batch positions. */
 innr_status innr_batch_knn_filtered(innr_batch* b, const float* q, size_t D, size_t k, const uint8_t* mask,
                                     uint64_t* out_idx, float* out_score, size_t* out_k);
+/* batch_knn_filtered (batch.rs:820-882) applied to each of Q queries, for all three metrics (the reference's function is squared
+ * L2; DOT / COSINE are this library's batched addition). mask: N bytes, mask[i] != 0 <=> predicate(i), one mask for every query.
+ * Writes k' = min(k, number passing) results per query to out_idx[q*k' + r], out_score[q*k' + r] (arrays sized Q*min(k,N)),
+ * indices into this batch plus its index base, in innr_batch_knn's order for the metric; *out_k = k'. The dimension check comes
+ * first (batch.rs:829); then N == 0, k == 0, Q == 0 or no passing vector give *out_k = 0 (batch.rs:831-847). A null mask with
+ * N > 0 or a u8 code batch: INNR_E_BAD_ARG.
+ * Engines: INNR_KNN_EXACT scans this batch with the mask applied. Every other engine, INNR_KNN_AUTO included, runs on a SELECTION:
+ * the passing vectors gathered on the device, in index order, into a compact batch of their own, searched like any batch of that
+ * size (innr_knn_stats.engine tells which engine ran there), the indices then mapped back; results are bit-identical either way.
+ * A mask that passes every vector searches this batch itself. Memory: the batch keeps the selection of its last mask --
+ * npass*D*4 bytes (D rounded up to 32), N + 4*npass bytes of mask and map, plus the filter copies the engines build on it -- so that a
+ * call with the same mask (compared on the device after folding to 0/1) reuses it; a different mask replaces it, innr_batch_free
+ * frees it, the option filter_keep_selection = 0 frees it at the end of every call. If it does not fit, the masked exact scan
+ * serves the call. stats->total_ms covers the whole call (mask, selection build, search). */
+innr_status innr_batch_knn_filtered_multi(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, size_t k,
+                                          const uint8_t* mask, int engine, uint64_t* out_idx, float* out_score, size_t* out_k,
+                                          innr_knn_stats* stats);
+/* same, queries, mask and outputs resident on the device (innr_batch_knn_dev's conventions) */
+innr_status innr_batch_knn_filtered_multi_dev(innr_batch* b, int metric, const float* d_queries, size_t Q, size_t D, size_t k,
+                                              const uint8_t* d_mask, int engine, uint64_t* d_out_idx, float* d_out_score, size_t* out_k,
+                                              innr_knn_stats* stats);
 /* batch_knn_reordered (batch.rs:621-659): distances accumulated in decreasing-variance dimension order
  * (variance_order :599-603), then k smallest by (distance, index). */
 innr_status innr_batch_knn_reordered(innr_batch* b, const float* q, size_t D, size_t k, uint64_t* out_idx,

@@ -112,6 +112,10 @@ SIGNATURES = {
                                         C.POINTER(KnnStats)]),
     "innr_batch_dimension_variance": (C.c_int, [_vp, _vp]),
     "innr_batch_knn_filtered": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _szp]),
+    "innr_batch_knn_filtered_multi": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _szp,
+                                                C.POINTER(KnnStats)]),
+    "innr_batch_knn_filtered_multi_dev": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _szp,
+                                                    C.POINTER(KnnStats)]),
     "innr_batch_knn_reordered": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _szp]),
     "innr_batch_l2_squared_pruning": (C.c_int, [_vp, _vp, _sz, C.c_float, _vp, _vp, _sz, _szp]),
     "innr_merge_topk_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),

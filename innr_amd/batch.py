@@ -393,6 +393,62 @@ def batch_knn_filtered(query, batch: VerticalBatch, k: int, predicate: Callable[
     return _l2_variant("innr_batch_knn_filtered", query, batch, k, _vp(mask) if mask.size else None)
 
 
+def batch_knn_filtered_multi(queries, batch: VerticalBatch, k: int, mask, metric: int = METRIC_L2SQ, engine: int = KNN_AUTO,
+                             stats: Optional[KnnStats] = None):
+    """batch.rs:820-882 for Q queries at once, one mask for all of them (mask[i] != 0 <=> predicate(i)), any metric and engine
+    (innr_batch_knn_filtered_multi: the engines other than the exact one search a compact copy of the passing vectors that the
+    batch keeps for the next call with the same mask). Returns (indices uint64 [Q, k'], scores float32 [Q, k']) with
+    k' = min(k, number passing). `mask`: a NumPy bool / uint8 array of length N; or a device tensor (torch, on the batch's GPU),
+    and then the device entry point runs: the queries go to the device, the results stay there (int64 / float32 tensors)."""
+    n = batch.num_vectors()
+    if hasattr(mask, "is_cuda") and mask.is_cuda:
+        import torch
+        m = mask.reshape(-1)
+        if m.numel() != n:
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {m.numel()}\n right: {n}")
+        m = m.to(torch.uint8).contiguous() if m.dtype != torch.uint8 else m.contiguous()
+        q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(_f32(queries))
+        q = q.to(device=m.device, dtype=torch.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        q = q.contiguous()
+        nq, d = q.shape
+        if d != batch.dimension():
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {d}\n right: {batch.dimension()}")
+        batch._ctx.bind_torch_stream()  # the mask and queries were produced on torch's stream, the results are consumed there
+        kk = min(int(k), n)
+        idx = torch.empty((max(nq * kk, 1),), dtype=torch.int64, device=m.device)
+        sc = torch.empty((max(nq * kk, 1),), dtype=torch.float32, device=m.device)
+        out_k = C.c_size_t(0)
+        st = stats if stats is not None else KnnStats()
+        check(load().innr_batch_knn_filtered_multi_dev(batch._h, metric, C.c_void_p(q.data_ptr()), nq, d, int(k),
+                                                       C.c_void_p(m.data_ptr()) if n else None, engine, C.c_void_p(idx.data_ptr()),
+                                                       C.c_void_p(sc.data_ptr()), C.byref(out_k), C.byref(st)))
+        r = int(out_k.value)
+        return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+    m = np.asarray(mask)
+    if m.dtype != np.uint8:
+        m = m.astype(bool).astype(np.uint8)
+    m = np.ascontiguousarray(m.reshape(-1))
+    if m.size != n:
+        raise InnrPanic(f"assertion `left == right` failed\n  left: {m.size}\n right: {n}")
+    q = _f32(queries)
+    if q.ndim == 1:
+        q = q.reshape(1, -1)
+    nq, d = q.shape
+    if d != batch.dimension():
+        raise InnrPanic(f"assertion `left == right` failed\n  left: {d}\n right: {batch.dimension()}")
+    kk = min(int(k), n)
+    idx = np.empty(max(nq * kk, 1), dtype=np.uint64)
+    sc = np.empty(max(nq * kk, 1), dtype=np.float32)
+    out_k = C.c_size_t(0)
+    st = stats if stats is not None else KnnStats()
+    check(load().innr_batch_knn_filtered_multi(batch._h, metric, _vp(q) if q.size else None, nq, d, int(k), _vp(m) if m.size else None,
+                                               engine, _vp(idx), _vp(sc), C.byref(out_k), C.byref(st)))
+    r = int(out_k.value)
+    return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+
+
 def batch_knn_reordered(query, batch: VerticalBatch, k: int) -> BatchKnnResult:
     """batch.rs:621-659: exact kNN with distances accumulated in decreasing-variance dimension order."""
     return _l2_variant("innr_batch_knn_reordered", query, batch, k)

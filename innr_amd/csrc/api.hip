@@ -22,6 +22,7 @@
 #include "kernels_u8.h"
 #include "kernels_gemm_i8.h"
 #include "kernels_maxsim.h"
+#include "kernels_select.h"
 
 namespace innr {  // sort_full.hip
 hipError_t full_sort_scratch_bytes(size_t n, size_t* bytes);
@@ -97,6 +98,7 @@ struct innr_tuning {
     long i8_small_free = 0;      // ... its query groups run free (no soft lockstep): A/B
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
+    long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi: keep the selection of the last mask for the next call (0: free it at the end of each call)
 };
 struct TuneName { const char* name; long innr_tuning::*field; };
 static const TuneName kTuneNames[] = {
@@ -110,7 +112,7 @@ static const TuneName kTuneNames[] = {
     {"i8_slices_per_cu", &innr_tuning::i8_slices_per_cu}, {"i8_no_small", &innr_tuning::i8_no_small},
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
-    {"split_min_q", &innr_tuning::split_min_q},
+    {"split_min_q", &innr_tuning::split_min_q}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
 };
 static void tuning_from_env(innr_tuning* t) {
     for (const TuneName& n : kTuneNames) {
@@ -133,7 +135,7 @@ struct innr_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int num_cus = 256;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [4], [5]: the span of a filtered multi-query call
     // Pinned staging for SMALL host<->device transfers (queries in, top-k out, flags): a hipMemcpyAsync on pageable
     // memory costs ~40 us per call on this stack, four of them made a single-query call 190 us; through pinned
     // memory the same copies are a few us. Inputs are staged by copy_in (bump allocation), outputs land in the
@@ -177,6 +179,9 @@ struct innr_ctx {
     DevBuf q_one;      // full-sort path (k > INNR_MAX_K): one zero-padded query row
     DevBuf sort_keys;  // [2][N] composites: unsorted, sorted
     DevBuf sort_tmp;   // radix sort scratch
+    DevBuf flt_in;     // innr_batch_knn_filtered_multi: the caller's mask bytes staged on the device (host-memory entry point)
+    DevBuf flt_mask;   // ... the mask normalised to 0/1, [ldN]
+    DevBuf flt_scan;   // ... passing vectors per chunk [nchunks], their exclusive scan [nchunks], the total, the mask-differs flag
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
 };
 
@@ -267,6 +272,14 @@ struct innr_batch {
     bool i8_weak = false, i8n_weak = false;  // most proofs failed on this corpus (a range blown up by outliers): AUTO stops picking the filter
     uint32_t i8_weak_skips = 0;              // AUTO calls that skipped the int8 filter since (every 64th tries it again)
     uint32_t auto_small_calls = 0;           // AUTO calls with fewer than four queries while no int8 copy existed: the fourth builds it
+    // innr_batch_knn_filtered_multi (kernels_select.h): the selection of the last mask -- its passing vectors compacted into a batch
+    // of their own (npass * Dpad * 4 bytes, plus the filter copies the engines build on it), the normalised mask it was built from
+    // and the map selection index -> column of this batch. At most one; freed with the batch, when a call brings a different mask,
+    // and at the end of every call under filter_keep_selection = 0.
+    innr_batch* fsel = nullptr;
+    uint8_t* fsel_mask = nullptr;  // [ldN] 0/1
+    uint32_t* fsel_map = nullptr;  // [fsel->N]
+    uint32_t fsel_builds = 0;      // selections built for this batch (read by a test hook)
 };
 
 namespace innr {
@@ -403,7 +416,7 @@ static uint32_t exact_cap(uint32_t KP) { return KP <= 32 ? 384u : (KP <= 128 ? 7
 
 // optional extras of the L2 variants (device pointers; both null for the plain scans)
 struct ScanExt {
-    const uint8_t* mask = nullptr;    // [ldN] predicate bytes (batch_knn_filtered)
+    const uint8_t* mask = nullptr;    // [ldN] predicate bytes (batch_knn_filtered; all three metrics: innr_batch_knn_filtered_multi)
     const uint32_t* order = nullptr;  // [D] dimension order (batch_knn_reordered)
     uint32_t nvalid = 0xFFFFFFFFu;    // query slots of the launch beyond this one are padding (zero rows): nothing is admitted for them
 };
@@ -419,8 +432,12 @@ static innr_status launch_scan_filter_r(innr_batch* b, int metric, const float* 
     const uint32_t N = (uint32_t)b->N, D = (uint32_t)b->D;
     switch (metric) {
         case INNR_METRIC_DOT:
-            scan_filter_kernel<QB, false, false, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
+            if (ext.mask)  // innr_batch_knn_filtered_multi
+                scan_filter_kernel<QB, false, false, R, true><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
+                    b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, ext.mask, nullptr, ext.nvalid);
+            else
+                scan_filter_kernel<QB, false, false, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
+                    b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
             break;
         case INNR_METRIC_L2SQ:
             if (ext.mask || ext.order)
@@ -432,8 +449,12 @@ static innr_status launch_scan_filter_r(innr_batch* b, int metric, const float* 
                     b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
             break;
         default:
-            scan_filter_kernel<QB, false, true, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                b->V, b->ldN, N, D, dQ, ldq, b->norms, dQn, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
+            if (ext.mask)
+                scan_filter_kernel<QB, false, true, R, true><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
+                    b->V, b->ldN, N, D, dQ, ldq, b->norms, dQn, lists, counts, qstride, KP, cps, err, ext.mask, nullptr, ext.nvalid);
+            else
+                scan_filter_kernel<QB, false, true, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
+                    b->V, b->ldN, N, D, dQ, ldq, b->norms, dQn, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
             break;
     }
     INNR_HIP_CHECK(hipGetLastError());
@@ -1641,6 +1662,16 @@ static innr_status check_errflag(innr_ctx* c) {
     return INNR_OK;
 }
 
+// the cached selection of innr_batch_knn_filtered_multi (innr_batch::fsel), if any
+static void free_selection(innr_batch* b) {
+    if (b->fsel) innr_batch_free(b->fsel);
+    if (b->fsel_mask) (void)hipFree(b->fsel_mask);
+    if (b->fsel_map) (void)hipFree(b->fsel_map);
+    b->fsel = nullptr;
+    b->fsel_mask = nullptr;
+    b->fsel_map = nullptr;
+}
+
 }  // namespace innr
 
 // =====================================================================================================
@@ -1701,7 +1732,7 @@ void innr_ctx_destroy(innr_ctx* c) {
                       &c->scores, &c->tmp_norms, &c->flags, &c->out_idx, &c->out_score, &c->misc, &c->seed_idx, &c->seed_score, &c->q_one, &c->sort_keys, &c->sort_tmp, &c->q_bf16, &c->q_pad, &c->q_hat,
                       &c->redo[0].q, &c->redo[0].idx, &c->redo[0].sc, &c->redo[0].map, &c->redo[0].qn,
                       &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
-                      &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn};
+                      &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan};
     for (DevBuf* b : bufs) b->release();
     if (c->pin) (void)hipHostFree(c->pin);
     for (auto& ev : c->ev)
@@ -1855,6 +1886,7 @@ void innr_batch_free(innr_batch* b) {
         (void)hipSetDevice(b->ctx->device);
         (void)ctx_sync(b->ctx);
     }
+    free_selection(b);
     if (b->V && !b->is_view) (void)hipFree(b->V);
     if (b->C8 && !b->is_view) (void)hipFree(b->C8);
     if (b->norms) (void)hipFree(b->norms);
@@ -1947,6 +1979,9 @@ innr_status innrdbg_split_scores(innr_batch* b, int metric, const float* queries
 // Test hook: the filter kernel of the last INNR_KNN_MFMA / _BF16 first pass on this batch's context: 0 none yet, 1 the f32 kernel
 // (gemm_filter_kernel), 2 the bf16 filter, 3 the split-bf16 filter (LastFilter).
 int innrdbg_last_filter(const innr_batch* b) { return b && b->ctx ? b->ctx->last_filter : -1; }
+
+// Test hook: how many selections innr_batch_knn_filtered_multi has built for this batch (its cache misses)
+uint32_t innrdbg_filter_selection_builds(const innr_batch* b) { return b ? b->fsel_builds : 0u; }
 
 #endif  // INNR_TEST_HOOKS
 
@@ -2183,8 +2218,9 @@ innr_status innr_batch_scores(innr_batch* b, int metric, const float* q, size_t 
 // batch.rs:754-763, 790-799, scalar.rs:383-392; for batch_knn's TopK, batch.rs:398-409, the same k smallest in the same order up
 // to ties at equal distances). One query at a time: the path is for the rare "give me everything, ranked" call.
 // metric < 0: u8 codes (aux = per-query sum(q)); cosine: aux = per-query norms.
+// mask (nullable, [ldN] bytes): only the vectors with mask[i] != 0 take part (they must number kout or more; innr_batch_knn_filtered_multi).
 static innr_status knn_full_sort(innr_batch* b, int metric, const float* dQ, size_t D, const float* aux, size_t Q,
-                                 size_t kout, uint64_t* d_out_idx, float* d_out_score) {
+                                 size_t kout, uint64_t* d_out_idx, float* d_out_score, const uint8_t* mask = nullptr) {
     innr_ctx* c = b->ctx;
     const size_t ldq = round_up(D ? D : 1, 4), N = b->N;
     size_t tmp_bytes = 0;
@@ -2220,7 +2256,7 @@ static innr_status knn_full_sort(innr_batch* b, int metric, const float* dQ, siz
                                                                                           b->norms, aux + q, ds, b->ldN);
         }
         INNR_HIP_CHECK(hipGetLastError());
-        INNR_HIP_CHECK(full_sort_scores(ds, N, smaller, keys, keys + N, c->sort_tmp.p, tmp_bytes, c->stream, nullptr, kout));
+        INNR_HIP_CHECK(full_sort_scores(ds, N, smaller, keys, keys + N, c->sort_tmp.p, tmp_bytes, c->stream, mask, kout));
         emit_results_kernel<<<(unsigned)((kout + 255) / 256), 256, 0, c->stream>>>(keys + N, 0, 1, (uint32_t)kout, smaller,
                                                                                b->index_base, d_out_idx + q * kout,
                                                                                d_out_score + q * kout);
@@ -4108,6 +4144,187 @@ innr_status innr_batch_knn_reordered(innr_batch* b, const float* q, size_t D, si
                          [&](uint32_t a, uint32_t c2) { return f32_ord(var[a]) > f32_ord(var[c2]); });
     }
     return knn_l2_ext(b, q, D, k, nullptr, b->D ? order.data() : nullptr, out_idx, out_score, out_k);
+}
+
+// ---- batch_knn_filtered for Q queries: compact, then search (kernels_select.h) ----------------------------
+// The caller's mask (device, N bytes) normalised to 0/1 into c->flt_mask, counted per chunk and scanned (c->flt_scan: [nchunks]
+// counts | [nchunks] offsets | total | differs): *npass, and *same = the cached selection was built from this very mask. One
+// synchronise, for the two numbers.
+static innr_status filter_mask(innr_batch* b, const uint8_t* d_mask, size_t* npass, bool* same) {
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kSelChunk;
+    INNR_TRY(c->flt_mask.ensure(b->ldN));
+    INNR_TRY(c->flt_scan.ensure((2 * nchunks + 2) * sizeof(uint32_t)));
+    uint32_t* cnt = c->flt_scan.as<uint32_t>();
+    uint32_t* tail = cnt + 2 * nchunks;
+    INNR_HIP_CHECK(hipMemsetAsync(tail, 0, 2 * sizeof(uint32_t), c->stream));
+    select_mask_kernel<<<(unsigned)((nchunks + 3) / 4), 256, 0, c->stream>>>(d_mask, (uint32_t)b->N, nchunks, c->flt_mask.as<uint8_t>(),
+                                                                            b->fsel ? b->fsel_mask : nullptr, cnt, tail + 1);
+    INNR_HIP_CHECK(hipGetLastError());
+    // (one workgroup: at most (2^32 - 257) / 256 chunks, 16384 per thread, every sum below 2^32)
+    exclusive_scan_kernel<<<1, 1024, 0, c->stream>>>(cnt, (uint32_t)nchunks, cnt + nchunks, tail);
+    INNR_HIP_CHECK(hipGetLastError());
+    uint32_t h[2] = {0, 0};
+    INNR_HIP_CHECK(copy_out(c, h, tail, sizeof(h)));
+    INNR_HIP_CHECK(ctx_sync(c));
+    *npass = h[0];
+    *same = b->fsel != nullptr && h[1] == 0;
+    return INNR_OK;
+}
+
+// A new selection of the npass vectors c->flt_mask passes (filter_mask ran): the old one freed, the columns gathered in index order,
+// the map written, the mask kept. *built = false when it does not fit: the caller serves the call with the masked exact scan.
+static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
+    innr_ctx* c = b->ctx;
+    *built = false;
+    free_selection(b);
+    innr_batch* s = nullptr;
+    const innr_status st = alloc_batch(c, npass, b->D, &s);
+    if (st == INNR_E_OOM) {
+        (void)hipGetLastError();  // the failed hipMalloc must not surface at the next launch check
+        return INNR_OK;
+    }
+    INNR_TRY(st);
+    b->fsel = s;
+    if (hipMalloc((void**)&b->fsel_mask, b->ldN) != hipSuccess || hipMalloc((void**)&b->fsel_map, npass * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        free_selection(b);
+        return INNR_OK;
+    }
+    const size_t nchunks = b->ldN / kSelChunk;
+    const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
+    const size_t D = b->D;
+    const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
+    const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
+    select_gather_kernel<<<grid, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->V, s->ldN,
+                                                      b->fsel_map, slab);
+    INNR_HIP_CHECK(hipGetLastError());
+    INNR_HIP_CHECK(hipMemcpyAsync(b->fsel_mask, c->flt_mask.p, b->ldN, hipMemcpyDeviceToDevice, c->stream));
+    ++b->fsel_builds;
+    *built = true;
+    return INNR_OK;
+}
+
+// The masked exact scan on the batch itself (INNR_KNN_EXACT, or no room for a selection): scan_filter_kernel<..., EXT> with the
+// normalised mask for every query, or beyond INNR_MAX_K all N scores of one query at a time and a full sort with the failing
+// vectors keyed last (as knn_l2_ext does it). kout <= npass.
+static innr_status knn_masked_exact(innr_batch* b, int metric, const float* dQ, size_t Q, size_t D, size_t kout, size_t npass,
+                                    uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats) {
+    innr_ctx* c = b->ctx;
+    const uint8_t* nm = c->flt_mask.as<uint8_t>();
+    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
+    const float* dQn = nullptr;
+    if (metric == INNR_METRIC_COSINE) {
+        INNR_TRY(ensure_norms(b));
+        INNR_TRY(c->q_norm.ensure(Q * sizeof(float)));
+        query_norms_kernel<<<(unsigned)Q, 64, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)D, D, c->q_norm.as<float>());
+        INNR_HIP_CHECK(hipGetLastError());
+        dQn = c->q_norm.as<float>();
+    }
+    uint32_t kept;
+    if (kout > INNR_MAX_K) {
+        INNR_TRY(knn_full_sort(b, metric, dQ, D, dQn, Q, kout, d_out_idx, d_out_score, nm));
+        kept = (uint32_t)npass;
+    } else {
+        ScanExt ext;
+        ext.mask = nm;
+        INNR_TRY(knn_exact_range(b, metric, dQ, D, dQn, 0, Q, kout, d_out_idx, d_out_score, ext));
+        kept = pick_kp(kout, 0);
+    }
+    return finish_knn(c, INNR_KNN_EXACT, kout, 0, kept, 0.0f, out_k, stats);
+}
+
+innr_status innr_batch_knn_filtered_multi_dev(innr_batch* b, int metric, const float* d_queries, size_t Q, size_t D, size_t k,
+                                              const uint8_t* d_mask, int engine, uint64_t* d_out_idx, float* d_out_score, size_t* out_k,
+                                              innr_knn_stats* stats) {
+    if (b && !b->V) {
+        set_error("this entry point needs an f32 batch (got a u8 code batch: use the *_u8 functions)");
+        return INNR_E_BAD_ARG;
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!b || !metric_ok(metric) || !out_k) {
+        set_error("bad batch/metric/out_k");
+        return INNR_E_BAD_ARG;
+    }
+    if (D != b->D) {  // batch.rs:829
+        set_error("dimension mismatch: query.len()=%zu, batch.dimension=%zu", D, b->D);
+        return INNR_E_DIM_MISMATCH;
+    }
+    *out_k = 0;
+    if (b->N == 0 || k == 0 || Q == 0) return INNR_OK;  // batch.rs:831-836
+    if (!d_mask) {
+        set_error("mask is null");
+        return INNR_E_BAD_ARG;
+    }
+    if (!d_queries || !d_out_idx || !d_out_score) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
+    size_t npass = 0;
+    bool same = false;
+    INNR_TRY(filter_mask(b, d_mask, &npass, &same));
+    if (npass == 0) return INNR_OK;  // batch.rs:841-847
+    const size_t kout = std::min(k, npass);  // batch.rs:849
+    if (npass == b->N) {
+        // every vector passes: the batch itself, no selection
+        INNR_TRY(innr_batch_knn_dev(b, metric, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
+    } else {
+        bool have = same;
+        if (engine != INNR_KNN_EXACT && !same) INNR_TRY(build_selection(b, npass, &have));
+        if (engine != INNR_KNN_EXACT && have) {
+            // the caller's engine on the selection (its own index_base is 0), then selection indices -> this batch's
+            INNR_TRY(innr_batch_knn_dev(b->fsel, metric, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
+            const size_t n = Q * *out_k;
+            if (n) {
+                select_remap_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d_out_idx, n, b->fsel_map, (uint32_t)npass,
+                                                                                     b->index_base);
+                INNR_HIP_CHECK(hipGetLastError());
+            }
+        } else {
+            INNR_TRY(knn_masked_exact(b, metric, d_queries, Q, D, kout, npass, d_out_idx, d_out_score, out_k, stats));
+        }
+    }
+    INNR_HIP_CHECK(hipEventRecord(c->ev[5], c->stream));
+    if (!c->tune.filter_keep_selection) free_selection(b);  // (synchronises)
+    if (stats) {  // the whole call: mask, selection build, search, remap
+        float ms = 0.0f;
+        INNR_HIP_CHECK(hipEventSynchronize(c->ev[5]));
+        if (hipEventElapsedTime(&ms, c->ev[4], c->ev[5]) == hipSuccess) stats->total_ms = ms;
+    }
+    return INNR_OK;
+}
+
+innr_status innr_batch_knn_filtered_multi(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, size_t k,
+                                          const uint8_t* mask, int engine, uint64_t* out_idx, float* out_score, size_t* out_k,
+                                          innr_knn_stats* stats) {
+    if (b && !b->V) {
+        set_error("this entry point needs an f32 batch (got a u8 code batch: use the *_u8 functions)");
+        return INNR_E_BAD_ARG;
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!b || !metric_ok(metric) || !out_k) {
+        set_error("bad batch/metric/out_k");
+        return INNR_E_BAD_ARG;
+    }
+    if (D != b->D) {
+        set_error("dimension mismatch: query.len()=%zu, batch.dimension=%zu", D, b->D);
+        return INNR_E_DIM_MISMATCH;
+    }
+    *out_k = 0;
+    if (b->N == 0 || k == 0 || Q == 0) return INNR_OK;
+    if (!mask) {
+        set_error("mask is null");
+        return INNR_E_BAD_ARG;
+    }
+    if (!queries && D) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_TRY(c->flt_in.ensure(b->N));
+    INNR_HIP_CHECK(hipMemcpyAsync(c->flt_in.p, mask, b->N, hipMemcpyHostToDevice, c->stream));
+    return knn_from_host(c, queries, Q, D, std::min(k, b->N), out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
+        return innr_batch_knn_filtered_multi_dev(b, metric, dQ, Q, D, k, c->flt_in.as<uint8_t>(), engine, di, ds, out_k, stats);
+    });
 }
 
 innr_status innr_batch_l2_squared_pruning(innr_batch* b, const float* q, size_t D, float threshold, uint64_t* out_idx,

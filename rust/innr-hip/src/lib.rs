@@ -88,6 +88,8 @@ pub mod ffi {
         pub fn innr_maxsim_topk_multi(d: *mut InnrDocs, cosine: c_int, qtoks: *const f32, q: usize, tq: *const u32, tq_stride: usize, dim: usize, k: usize, engine: c_int, out_doc: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_dimension_variance(b: *mut InnrBatch, out: *mut f32) -> c_int;
         pub fn innr_batch_knn_filtered(b: *mut InnrBatch, q: *const f32, d: usize, k: usize, mask: *const u8, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize) -> c_int;
+        pub fn innr_batch_knn_filtered_multi(b: *mut InnrBatch, metric: c_int, queries: *const f32, q: usize, d: usize, k: usize, mask: *const u8, engine: c_int, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_knn_filtered_multi_dev(b: *mut InnrBatch, metric: c_int, d_queries: *const f32, q: usize, d: usize, k: usize, d_mask: *const u8, engine: c_int, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_knn_reordered(b: *mut InnrBatch, q: *const f32, d: usize, k: usize, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize) -> c_int;
         pub fn innr_batch_l2_squared_pruning(b: *mut InnrBatch, q: *const f32, d: usize, threshold: f32, out_idx: *mut u64, out_dist: *mut f32, cap: usize, out_n: *mut usize) -> c_int;
         pub fn innr_dot_f32(a: *const f32, b: *const f32, n: usize) -> f32;
@@ -340,6 +342,25 @@ pub mod batch {
         check(unsafe { ffi::innr_batch_knn_filtered(batch.handle(), query.as_ptr(), query.len(), k, mask.as_ptr(),
                                                     idx.as_mut_ptr(), sc.as_mut_ptr(), &mut n) });
         collect(idx, sc, n)
+    }
+
+    /// batch.rs:820-882 for Q row-major queries at once, one mask for all of them (`mask[i]` <=> predicate(i)), any metric and
+    /// engine (ffi::INNR_KNN_*); min(k, passing) results per query. The engines other than the exact one search a compact copy of
+    /// the passing vectors that the batch keeps for the next call with the same mask (include/innr_hip.h).
+    pub fn batch_knn_filtered_multi(engine: i32, metric: i32, queries: &[f32], dimension: usize, batch: &VerticalBatch, k: usize,
+                                    mask: &[bool]) -> Vec<BatchKnnResult> {
+        assert_eq!(dimension, batch.dimension);
+        assert_eq!(mask.len(), batch.num_vectors);
+        let q = if dimension == 0 { 0 } else { queries.len() / dimension };
+        let bytes: Vec<u8> = mask.iter().map(|&m| m as u8).collect();
+        let kk = k.min(batch.num_vectors);
+        let (mut idx, mut sc, mut out_k) = (vec![0u64; q * kk.max(1)], vec![0f32; q * kk.max(1)], 0usize);
+        check(unsafe { ffi::innr_batch_knn_filtered_multi(batch.handle(), metric, queries.as_ptr(), q, dimension, k, bytes.as_ptr(),
+                                                          engine, idx.as_mut_ptr(), sc.as_mut_ptr(), &mut out_k, std::ptr::null_mut()) });
+        (0..q).map(|j| BatchKnnResult {
+            indices: idx[j * out_k..(j + 1) * out_k].iter().map(|&i| i as usize).collect(),
+            scores: sc[j * out_k..(j + 1) * out_k].to_vec(),
+        }).collect()
     }
 
     /// batch.rs:621-659
