@@ -8,13 +8,16 @@ queries]) with the corpus and the queries already resident in HBM; for N > 1 GPU
 range-partitioned, weak scaling: 10M vectors PER GPU) the step also includes the RCCL all-gather of the
 per-shard top-k and the merge. value = vectors scanned per second = Q * N_total / step time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: one process per GPU -- launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`, or, from a
   bare shell, by bench.py itself (it starts that launcher as a child before touching a GPU and relays rank 0's line).
 
-Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel: the GEMM, timed live with HIP events on
-the stream it is launched on) and `cpu_baseline` (the CPU oracle = "port" of innr's portable path, single
-thread like the reference, on a bounded sample) objects described in DESIGN.md.
+Prints ONE JSON line on rank 0 with the `roofline` object described in DESIGN.md (dominant kernel: the GEMM, timed live with
+HIP events on the stream it is launched on, inside the timed steps). A plain run does only what that line needs: set-up,
+warm-up, the timed steps, the --dump-outputs arrays and the line. --full adds the measurements that take runs of their own
+(N = 1 only): the side rows (the same call on the bf16 and int8 filter engines with a bit-equality check against the f32
+engine, and on the reference example's LCG data) and `cpu_baseline` (the CPU oracle = "port" of innr's portable path, single
+thread like the reference, on a bounded sample); --no-side-rows and --no-cpu-baseline drop either from a --full run.
 """
 from __future__ import annotations
 
@@ -232,8 +235,11 @@ def main() -> None:
     ap.add_argument("--queries", type=int, default=1024)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--metric", choices=["dot", "cosine"], default="dot")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-rows", action="store_true", help="skip the bf16-filter side measurement of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the side rows and the CPU baseline (N = 1 "
+                         "only); off by default, so a plain run does only set-up, warm-up, the timed steps and its outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side-rows", action="store_true", help="with --full: skip the bf16 / int8 filter-engine and LCG-data side rows")
     ap.add_argument("--data", choices=["uniform", "lcg"], default="uniform",
                     help="uniform: i.i.d. uniform(-1,1), the distribution of the reference's criterion benches (default, the "
                          "judged row); lcg: the reference EXAMPLE's generator (examples/batch_demo.rs:233-242: corpus row i = "
@@ -267,7 +273,7 @@ def main() -> None:
     if args.rehearse_cpu:
         raise SystemExit(rehearse_cpu(args))
 
-    if not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0:
+    if args.full and not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0:
         import oracle
         oracle.lib()  # load (or, on a stale build, re-make) the CPU checker BEFORE this process touches the GPU: no exec after HIP init
         oracle.build_native()  # the same source compiled -march=native on THIS host, for the cpu_baseline leg
@@ -419,7 +425,7 @@ def main() -> None:
                 **(pmc_traffic(args) if args.engine == "f32" else {"traffic": None}),
             },
         }
-        if world == 1 and args.engine == "f32" and args.data == "uniform" and not args.no_side_rows:
+        if args.full and world == 1 and args.engine == "f32" and args.data == "uniform" and not args.no_side_rows:
             # side rows (not `value`): the same call with the FILTER stage on a low-precision matrix pipe -- the bf16 copy
             # (INNR_KNN_MFMA_BF16, what INNR_KNN_AUTO picks for such a batch) and the scalar-quantised int8 copy
             # (INNR_KNN_MFMA_I8) -- each with a check that it returns the f32 engine's answer bit for bit
@@ -443,7 +449,7 @@ def main() -> None:
                     "queries_redone": int(st2.queries_fallback), "candidates_per_query": int(st2.candidates_kept),
                     "identical_to_f32_engine": bool(torch.equal(f_idx, b_idx) and torch.equal(f_sc.view(torch.int32), b_sc.view(torch.int32))),
                 }
-        if world == 1 and args.engine == "f32" and args.data == "uniform" and not args.no_side_rows:
+        if args.full and world == 1 and args.engine == "f32" and args.data == "uniform" and not args.no_side_rows:
             # side row (not `value`): the same call on the reference EXAMPLE's generator (examples/batch_demo.rs:233-242, what
             # SURVEY 8d names) -- near-tie data on which every margin proof of the first pass fails (tens of thousands of vectors
             # within the f32 error bound of every k-th score); the step is then the GEMM pass + ONE completion pass (collect mode,
@@ -479,7 +485,7 @@ def main() -> None:
             out["roofline"]["frac"] = out["roofline"]["achieved"] / PEAK_F32_MFMA_TFLOPS
             out["roofline"]["algorithmic_flop_per_launch"] = flop
             out["roofline"]["launches_per_step"] = 2
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.dim, args.k)
         print(json.dumps(out), flush=True)
     if world > 1:
