@@ -242,6 +242,28 @@ innr_status innr_maxsim_topk_multi(innr_docs* d, int cosine, const float* qtoks,
                                    size_t Tq_stride, size_t dim, size_t k, int engine, uint64_t* out_doc, float* out_score,
                                    size_t* out_k, innr_knn_stats* stats);
 
+/* Second stage for multi-vector corpora (an addition; the document-side twin of innr_batch_rerank): exact maxsim (cosine != 0:
+ * maxsim_cosine) of query j against ITS candidates cand[j*kc .. j*kc + kc), best min(k, kc) per query. Every candidate is scored
+ * exactly, once, on the exact engine's arithmetic: no approximate stage, no proof, the MFMA engine is not involved.
+ * Queries as in innr_maxsim_topk_multi: Q blocks of Tq_stride*dim floats, query j using its first tq[j] tokens (tq == NULL:
+ * Tq_stride each; any tq[j] <= Tq_stride, 0 included). Candidates as in innr_batch_rerank: GLOBAL document indices (index base +
+ * local index), any kc >= 1, no duplicates within one query (duplicates: that query's result is unspecified, no other query is
+ * affected). A candidate outside [base, base + docs) -> INNR_E_BAD_ARG, detected on the device and reported at the end of the
+ * call; outputs then unspecified. *out_k = min(k, kc); out_doc[j*out_k + r], out_score[j*out_k + r], ordered by score descending
+ * (total order), ties -> lower document index; scores bit-identical to innr_maxsim_scores' for the same document (an empty
+ * query or document scores 0.0). The dimension check comes first (INNR_E_DIM_MISMATCH); then docs == 0, Q == 0, k == 0 or
+ * kc == 0 give *out_k = 0; Q*kc beyond 32-bit slots -> INNR_E_UNSUPPORTED.
+ * Out of scope: ragged candidate counts or sentinel entries, a sharded variant (innr_sharded_maxsim is unchanged), re-ranking on
+ * the MFMA engine, u8 / bf16 token stores. */
+innr_status innr_maxsim_rerank(innr_docs* d, int cosine, const float* qtoks, size_t Q, const uint32_t* tq, size_t Tq_stride,
+                               size_t dim, const uint64_t* cand, size_t kc, size_t k, uint64_t* out_doc, float* out_score,
+                               size_t* out_k);
+/* the same with qtoks, cand, out_doc and out_score resident on the device (tq stays a host array); the call synchronises with
+ * the host once, to read the bad-candidate flag */
+innr_status innr_maxsim_rerank_dev(innr_docs* d, int cosine, const float* d_qtoks, size_t Q, const uint32_t* tq, size_t Tq_stride,
+                                   size_t dim, const uint64_t* d_cand, size_t kc, size_t k, uint64_t* d_out_doc,
+                                   float* d_out_score, size_t* out_k);
+
 /* ---- L2 variants of the batch module (exact engine, one query) -------------------------------------- */
 /* batch_dimension_variance (batch.rs:572-592): out[D]; sequential sums in the reference's order, cached per batch */
 innr_status innr_batch_dimension_variance(innr_batch* b, float* out);

@@ -110,6 +110,8 @@ SIGNATURES = {
     "innr_maxsim_topk": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
     "innr_maxsim_topk_multi": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp,
                                         C.POINTER(KnnStats)]),
+    "innr_maxsim_rerank": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _szp]),
+    "innr_maxsim_rerank_dev": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _vp, _szp]),
     "innr_batch_dimension_variance": (C.c_int, [_vp, _vp]),
     "innr_batch_knn_filtered": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _szp]),
     "innr_batch_knn_filtered_multi": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _szp,

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -3994,6 +3995,153 @@ innr_status innr_maxsim_topk_multi(innr_docs* d, int cosine, const float* qtoks,
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
     }
+    return INNR_OK;
+}
+
+// slots and document ids are 32-bit in the re-rank kernels; its pack and norms launches have one thread per packed float / token
+static innr_status maxsim_rerank_fits(size_t Q, size_t kc, size_t Tq_stride, size_t dim) {
+    const size_t stride_pad = round_up(std::max<size_t>(Tq_stride, 1), kMsQ);
+    if (kc > 0xFFFFFF00ull / Q || Tq_stride > 0xFFFFFFFFull || stride_pad > ((size_t)0x7fffffff * 256) / (Q * (ms_rerank_blk(dim) / kMsQ))) {
+        set_error("maxsim rerank: %zu queries x %zu candidates (x %zu query tokens) is beyond one launch", Q, kc, Tq_stride);
+        return INNR_E_UNSUPPORTED;
+    }
+    return INNR_OK;
+}
+
+// Second stage for multi-vector corpora (an addition, the document-side twin of innr_batch_rerank): exact maxsim /
+// maxsim_cosine of query j against ITS kc candidate documents, best min(k, kc) per query. Every candidate is scored
+// exactly, once (maxsim_rerank_kernel: the corpus scan's arithmetic over all Q*kc pairs in one launch per 32-token pass);
+// there is no approximate stage and nothing to prove. Queries as in innr_maxsim_topk_multi, candidates as in innr_batch_rerank.
+innr_status innr_maxsim_rerank_dev(innr_docs* d, int cosine, const float* d_qtoks, size_t Q, const uint32_t* tq, size_t Tq_stride,
+                                   size_t dim, const uint64_t* d_cand, size_t kc, size_t k, uint64_t* d_out_doc, float* d_out_score,
+                                   size_t* out_k) {
+    if (!d || !out_k) return INNR_E_BAD_ARG;
+    *out_k = 0;
+    if (dim != d->dim) {  // maxsim.rs:103-110
+        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
+        return INNR_E_DIM_MISMATCH;
+    }
+    if (d->ndocs == 0 || Q == 0 || k == 0 || kc == 0) return INNR_OK;
+    if (!d_cand || !d_out_doc || !d_out_score) return INNR_E_BAD_ARG;
+    INNR_TRY(maxsim_rerank_fits(Q, kc, Tq_stride, dim));
+    std::unique_ptr<uint32_t[]> tqv(new (std::nothrow) uint32_t[Q]);
+    if (!tqv) return INNR_E_OOM;
+    size_t tq_max = 0;
+    for (size_t i = 0; i < Q; ++i) {
+        tqv[i] = (uint32_t)(tq ? std::min<size_t>(tq[i], Tq_stride) : Tq_stride);
+        tq_max = std::max<size_t>(tq_max, tqv[i]);
+    }
+    if (!d_qtoks && tq_max * dim) return INNR_E_BAD_ARG;
+    const size_t npass = std::max<size_t>((tq_max + kMsQ - 1) / kMsQ, 1), blk = ms_rerank_blk(dim);
+    const size_t kout = std::min(k, kc);
+    innr_ctx* c = d->ctx;
+    INNR_ENTER(c);
+    size_t tmp_bytes = 0;
+    INNR_HIP_CHECK(segmented_sort_scratch_bytes(Q, kc, &tmp_bytes));
+    INNR_TRY(c->sort_keys.ensure((2 * Q * kc + full_topk_out_capacity(kout)) * sizeof(uint64_t)));
+    INNR_TRY(c->sort_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    INNR_TRY(c->misc.ensure(Q * sizeof(uint32_t) + 64));
+    INNR_TRY(c->q_kmajor.ensure(Q * npass * blk * sizeof(float)));
+    if (cosine) INNR_TRY(c->q_norm.ensure(std::max<size_t>(2 * Q * Tq_stride, 1) * sizeof(float)));
+    if (npass > 1) INNR_TRY(c->scores.ensure(Q * kc * sizeof(float)));
+    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
+    uint32_t* bad = c->flags.as<uint32_t>() + 65;  // set by the kernel for a candidate outside the corpus
+    uint32_t* d_tq = c->misc.as<uint32_t>();
+    INNR_HIP_CHECK(copy_in(c, d_tq, tqv.get(), Q * sizeof(uint32_t)));
+    float* qpk = c->q_kmajor.as<float>();
+    float* aa = cosine ? c->q_norm.as<float>() : nullptr;
+    float* saa = cosine ? aa + Q * Tq_stride : nullptr;
+    if (tq_max && d->T) {
+        maxsim_rerank_pack_kernel<<<(unsigned)((Q * npass * blk + 255) / 256), 256, 0, c->stream>>>(
+            d_qtoks, d_tq, (uint32_t)Q, (uint32_t)Tq_stride, (uint32_t)dim, (uint32_t)npass, (uint32_t)tq_max, qpk);
+        if (cosine)
+            maxsim_rerank_norms_kernel<<<(unsigned)((Q * Tq_stride + 255) / 256), 256, 0, c->stream>>>(
+                d_qtoks, d_tq, (uint32_t)Q, (uint32_t)Tq_stride, (uint32_t)dim, aa, saa);
+        INNR_HIP_CHECK(hipGetLastError());
+    }
+    uint32_t Tp = 1;
+    while (Tp < d->T && Tp < 64) Tp <<= 1;
+    const uint32_t docs_per_wave = 64 / Tp;
+    const size_t units = Q * ((kc + docs_per_wave - 1) / docs_per_wave);
+    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((units + 3) / 4, (size_t)c->num_cus * 2));
+    uint64_t* keys = c->sort_keys.as<uint64_t>();
+    float* partial = c->scores.as<float>();
+    INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+    for (size_t pass = 0; pass < npass; ++pass) {
+#define INNR_MS_RERANK(COSV, NQV, MULTIV)                                                                                \
+    maxsim_rerank_kernel<COSV, NQV, MULTIV><<<blocks, kMsThreads, 0, c->stream>>>(                                       \
+        d->tok, d->doc_len, (uint32_t)d->ndocs, (uint32_t)d->T, Tp, (uint32_t)dim, d_qtoks, (uint32_t)Tq_stride, d_tq, qpk, \
+        (uint32_t)npass, (uint32_t)pass, aa, saa, d_cand, (uint32_t)Q, (uint32_t)kc, d->index_base, partial, keys, bad)
+#define INNR_MS_RERANK_NQ(COSV, MULTIV)                                       \
+    do {                                                                      \
+        switch (ms_pass_nq((uint32_t)tq_max, (uint32_t)pass)) {               \
+            case 8: INNR_MS_RERANK(COSV, 8, MULTIV); break;                   \
+            case 16: INNR_MS_RERANK(COSV, 16, MULTIV); break;                 \
+            default: INNR_MS_RERANK(COSV, 32, MULTIV); break;                 \
+        }                                                                     \
+    } while (0)
+        if (cosine) {
+            if (d->T > 64) INNR_MS_RERANK_NQ(true, true); else INNR_MS_RERANK_NQ(true, false);
+        } else {
+            if (d->T > 64) INNR_MS_RERANK_NQ(false, true); else INNR_MS_RERANK_NQ(false, false);
+        }
+#undef INNR_MS_RERANK_NQ
+#undef INNR_MS_RERANK
+        INNR_HIP_CHECK(hipGetLastError());
+    }
+    INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+    INNR_HIP_CHECK(segmented_topk_keys(keys, keys + Q * kc, Q, kc, kout, keys + 2 * Q * kc, c->sort_tmp.p, c->stream));
+    const size_t total = Q * kout;
+    emit_results_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(keys + Q * kc, (uint32_t)kc, (uint32_t)Q, (uint32_t)kout,
+                                                                               false, d->index_base, d_out_doc, d_out_score);
+    INNR_HIP_CHECK(hipGetLastError());
+    uint32_t hbad = 0;  // the call's one host read
+    INNR_HIP_CHECK(copy_out(c, &hbad, bad, 4));
+    INNR_HIP_CHECK(ctx_sync(c));
+    if (c->tune.trace) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess)
+            fprintf(stderr, "innr: maxsim_rerank Q=%zu kc=%zu passes=%zu: scan kernels %.4f ms\n", Q, kc, npass, ms);
+    }
+    if (hbad) {
+        set_error("maxsim rerank: a candidate index lies outside this corpus' range [%llu, %llu)", (unsigned long long)d->index_base,
+                  (unsigned long long)(d->index_base + d->ndocs));
+        return INNR_E_BAD_ARG;
+    }
+    *out_k = kout;
+    return INNR_OK;
+}
+
+innr_status innr_maxsim_rerank(innr_docs* d, int cosine, const float* qtoks, size_t Q, const uint32_t* tq, size_t Tq_stride, size_t dim,
+                               const uint64_t* cand, size_t kc, size_t k, uint64_t* out_doc, float* out_score, size_t* out_k) {
+    if (!d || !out_k) return INNR_E_BAD_ARG;
+    *out_k = 0;
+    if (dim != d->dim) {
+        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
+        return INNR_E_DIM_MISMATCH;
+    }
+    if (d->ndocs == 0 || Q == 0 || k == 0 || kc == 0) return INNR_OK;
+    if (!cand || !out_doc || !out_score) return INNR_E_BAD_ARG;
+    INNR_TRY(maxsim_rerank_fits(Q, kc, Tq_stride, dim));  // before anything of the caller's is read
+    const size_t qfloats = Q * Tq_stride * dim;
+    if (!qtoks && qfloats) {
+        bool needed = !tq;
+        for (size_t i = 0; tq && i < Q; ++i) needed = needed || tq[i] != 0;
+        if (needed) return INNR_E_BAD_ARG;
+    }
+    innr_ctx* c = d->ctx;
+    INNR_ENTER(c);
+    const size_t kout = std::min(k, kc);
+    INNR_TRY(c->q_row.ensure(std::max<size_t>(qfloats, 1) * sizeof(float)));
+    INNR_TRY(c->out_idx.ensure(Q * (kout + kc) * sizeof(uint64_t)));
+    INNR_TRY(c->out_score.ensure(Q * kout * sizeof(float)));
+    uint64_t* d_cand = c->out_idx.as<uint64_t>() + Q * kout;
+    if (qtoks && qfloats) INNR_HIP_CHECK(copy_in(c, c->q_row.p, qtoks, qfloats * sizeof(float)));
+    INNR_HIP_CHECK(copy_in(c, d_cand, cand, Q * kc * sizeof(uint64_t)));
+    INNR_TRY(innr_maxsim_rerank_dev(d, cosine, c->q_row.as<float>(), Q, tq, Tq_stride, dim, d_cand, kc, k, c->out_idx.as<uint64_t>(), c->out_score.as<float>(), out_k));
+    INNR_HIP_CHECK(copy_out(c, out_doc, c->out_idx.p, Q * kout * sizeof(uint64_t)));
+    INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * kout * sizeof(float)));
+    INNR_HIP_CHECK(ctx_sync(c));
     return INNR_OK;
 }
 

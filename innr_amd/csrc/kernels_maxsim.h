@@ -383,17 +383,254 @@ __global__ void sqrt_kernel(const float* __restrict__ x, uint32_t n, float* __re
 }
 
 // aa[i] = sum of squares of query token i in cosine_portable's 4-way order (dense.rs:288-339)
-__global__ void query_token_sq_kernel(const float* __restrict__ qtok, uint32_t nq, uint32_t dim, float* __restrict__ aa) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq) return;
-    const float* a = qtok + (size_t)i * dim;
+__device__ __forceinline__ float query_token_sq(const float* __restrict__ a, uint32_t dim) {
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     const uint32_t chunks = dim / 4;
     for (uint32_t c = 0; c < chunks; ++c)
         for (int e = 0; e < 4; ++e) s[e] = ex::mad2(s[e], a[4 * c + e], a[4 * c + e]);
     float r = ex::add(ex::add(ex::add(s[0], s[1]), s[2]), s[3]);
     for (uint32_t d = chunks * 4; d < dim; ++d) r = ex::mad2(r, a[d], a[d]);
+    return r;
+}
+__global__ void query_token_sq_kernel(const float* __restrict__ qtok, uint32_t nq, uint32_t dim, float* __restrict__ aa) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    aa[i] = query_token_sq(qtok + (size_t)i * dim, dim);
+}
+
+// The body of maxsim_scan_kernel's document loop as a function of its own, for maxsim_rerank_kernel: one wave, one pass of NQ
+// query tokens over the wave's 64/Tp documents (lane = token lane % Tp of document `doc`, which has `len` tokens; len = 0 on
+// lanes without a document): the per-lane arithmetic, the max over token lanes and the ordered sum, statement for statement the
+// scan's. Returns the running total over query tokens on the lanes with lane % Tp == 0; total0() supplies what the earlier passes
+// left there (-0.0 on the first). qpk, qtok, q_aa, q_saa must be wave-uniform.
+// A copy, not shared with the scan kernel: calling it from there moved the scan's register allocation (VGPRs 154 -> 143,
+// 200 -> 183, 256 -> 248 in three instantiations, innr_amd/csrc/resusage.py), and the scan's recorded timings rest on the old one.
+// Change the arithmetic in both places; tests/test_gpu_maxsim_rerank.py compares the two bit for bit.
+// MULTI: documents longer than 64 tokens (several token groups per document, a running max per query token kept
+// across them: 32 more live registers, so it is a separate instantiation).
+template <bool COS, int NQ, bool MULTI, class Total0>
+__device__ __forceinline__ float maxsim_wave_pass(const float* __restrict__ tok, uint32_t T, uint32_t Tp, uint32_t dim, int lane, int tmode,
+                                                  uint32_t doc, uint32_t len, const float* __restrict__ qtok,
+                                                  const float* __restrict__ qpk, uint32_t nq, const float* __restrict__ q_aa,
+                                                  const float* __restrict__ q_saa, Total0 total0) {
+    const uint32_t t = lane % Tp;
+    const uint32_t chunks = dim / 4;
+    // documents with T > 64 tokens: walk the tokens in groups of Tp = 64, keeping a running max per query token
+    float best[NQ];
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) best[qi] = -INFINITY;
+    for (uint32_t t0 = 0; t0 < (MULTI ? T : 1u); t0 += Tp) {
+        const bool live = (t0 + t) < len;
+        // lanes without a token read token 0 of the corpus (always mapped) and are masked out of the max below:
+        // no per-load predication in the hot loop
+        const float* row = tok + (live ? ((size_t)doc * T + t0 + t) * dim : (size_t)0);
+        f32x2 acc[NQ][2];
+        float bb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) acc[qi][0] = acc[qi][1] = f32x2{0.0f, 0.0f};
+        // bursts of 8 chunks (32 dims = one 128-B line of this lane's token row), the next burst's line already
+        // in flight while this one is multiplied; per accumulator the chunks are visited in ascending order,
+        // which is all dot_portable's result depends on
+        uint32_t c0 = 0;
+        float4 dv[kMsBurst], dn[kMsBurst];
+        if (kMsBurst <= chunks) maxsim_load_burst(dv, row, 0, lane);
+#pragma unroll 1
+        for (; c0 + kMsBurst <= chunks; c0 += kMsBurst) {
+            const bool more = c0 + 2 * kMsBurst <= chunks;  // wave-uniform
+            if (more) maxsim_load_burst(dn, row, c0 + kMsBurst, lane);
+            maxsim_burst<NQ, COS>(acc, bb, dv, qpk + (size_t)c0 * NQ * 4);
+            if (more) {
+#pragma unroll
+                for (int b = 0; b < kMsBurst; ++b) dv[b] = dn[b];
+            }
+        }
+        // remaining chunks (dim not a multiple of 32): one group at a time, not pipelined
+        for (; c0 < chunks; ++c0) {
+            const float4 d4 = *reinterpret_cast<const float4*>(row + 4 * c0);
+            if (COS) maxsim_bb(bb, d4);
+#pragma unroll
+            for (int gi = 0; gi < NQ / 4; ++gi) {
+                f32x16 q;
+                sload16<0>(q, qpk + ((size_t)c0 * NQ + 4 * gi) * 4);
+                swait0(q);
+                maxsim_group<NQ>(acc, q, 4 * gi, d4);
+            }
+        }
+        // ((s0+s1)+s2)+s3 then the sequential tail (dense.rs:119-124)
+        float sbb = ex::add(ex::add(ex::add(bb[0], bb[1]), bb[2]), bb[3]);
+        float tailv[3] = {0.f, 0.f, 0.f};
+        const uint32_t ntail = dim - chunks * 4;
+        for (uint32_t e = 0; e < ntail; ++e) {
+            tailv[e] = row[chunks * 4 + e];
+            if (COS) sbb = ex::mad2(sbb, tailv[e], tailv[e]);
+        }
+#ifdef INNR_MS_PROBE_NOEPI  // tools/maxsim_probe.hip: the hot loop alone (the accumulators folded into one value per lane)
+        {
+            float f = 0.0f;
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) f += (acc[qi][0].x + acc[qi][0].y) + (acc[qi][1].x + acc[qi][1].y);
+            best[0] = fmaxf(best[0], f + sbb + (float)ntail);
+        }
+#else
+        // Per query token: the lane's dot product, then the max over the document's Tp token lanes. With the segment width a
+        // run-time value the 32 butterflies were 32 loops (and the tail's per-token pointers 146 spilled SGPRs): this epilogue
+        // cost 31 % of the kernel at C4 (tools/maxsim_probe.hip, -DINNR_MS_PROBE_NOEPI: 3.20 -> 2.19 ms on 200 K documents).
+        // Now one wave-uniform switch picks straight-line code for the segment width -- the transposing butterfly ms_tmax --;
+        // a dimension that is not a multiple of four, or fewer than 8 tokens per document, keep the general form.
+        const float sqrt_bb = COS ? ex::sqrt(sbb) : 0.0f;
+        auto epilogue = [&](auto tp_tag, auto tail_tag) {
+            constexpr int TPC = decltype(tp_tag)::value;  // 0: run-time width
+            constexpr bool TAIL = decltype(tail_tag)::value;
+            float val[NQ];
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) {
+                if ((uint32_t)qi < nq) {
+                    float sdot = ex::add(ex::add(ex::add(acc[qi][0].x, acc[qi][0].y), acc[qi][1].x), acc[qi][1].y);
+                    if (TAIL)
+                        for (uint32_t e = 0; e < ntail; ++e) sdot = ex::mad2(sdot, qtok[(size_t)qi * dim + chunks * 4 + e], tailv[e]);
+                    float sc = sdot;
+                    if (COS) {  // dense.rs:341-345
+                        const float aa = q_aa[qi];
+                        constexpr float kEpsSq = INNR_NORM_EPSILON * INNR_NORM_EPSILON;  // lib.rs:184
+                        sc = (aa > kEpsSq && sbb > kEpsSq) ? ex::div(sdot, ex::mul(q_saa ? q_saa[qi] : ex::sqrt(aa), sqrt_bb)) : 0.0f;
+                    }
+                    sc = live ? sc : -INFINITY;  // tokens beyond the document's length do not take part in the max
+                    if (TPC == 0) best[qi] = fmaxf(best[qi], wave_max_seg(sc, (int)Tp));
+                    else val[qi] = sc;
+                } else if (TPC != 0) {
+                    val[qi] = -INFINITY;  // (a padded query token: computed, never summed)
+                }
+            }
+            if constexpr (TPC != 0) {  // transposed: best[s] = running max of slot s (ms_tmax)
+                ms_tmax<NQ, NQ, TPC / 2>(val, lane);
+#pragma unroll
+                for (int s2 = 0; s2 < ms_tmax_left(NQ, TPC); ++s2) best[s2] = fmaxf(best[s2], val[s2]);
+            }
+        };
+        using std::integral_constant;
+        if (tmode == 0 && ntail != 0) epilogue(integral_constant<int, 0>(), integral_constant<bool, true>());
+        else if (tmode == 0) epilogue(integral_constant<int, 0>(), integral_constant<bool, false>());
+        else if (Tp == 64) epilogue(integral_constant<int, 64>(), integral_constant<bool, false>());
+        else if (Tp == 32) epilogue(integral_constant<int, 32>(), integral_constant<bool, false>());
+        else if (Tp == 16) epilogue(integral_constant<int, 16>(), integral_constant<bool, false>());
+        else epilogue(integral_constant<int, 8>(), integral_constant<bool, false>());
+#endif
+    }
+    // sum over query tokens in token order, folded from -0.0 (first pass) or from the previous passes' total
+    float total = total0();
+    auto fold = [&](auto tp_tag) {
+        constexpr int TPC = decltype(tp_tag)::value;
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi)
+            if ((uint32_t)qi < nq) {
+                float b;
+                if constexpr (TPC == 0) b = best[qi];
+                else b = __shfl(best[ms_tmax_slot(NQ, TPC, qi)], (lane & ~(TPC - 1)) | ms_tmax_lane(NQ, TPC, qi), 64);  // (every lane takes part)
+                total = ex::add(total, b);
+            }
+    };
+    if (tmode == 0) fold(std::integral_constant<int, 0>());
+    else if (Tp == 64) fold(std::integral_constant<int, 64>());
+    else if (Tp == 32) fold(std::integral_constant<int, 32>());
+    else if (Tp == 16) fold(std::integral_constant<int, 16>());
+    else fold(std::integral_constant<int, 8>());
+    return total;
+}
+
+// ---- re-rank: MANY queries, each against ITS OWN candidate documents, exact (innr_maxsim_rerank) --------------------
+// The second stage of a late-interaction pipeline: a first stage hands kc candidate documents per query, and only those
+// Q*kc (query, document) pairs are scored -- in maxsim_wave_pass, i.e. with the corpus scan's arithmetic bit for bit. One
+// launch per 32-token pass covers every pair. A wave works on candidates of ONE query (64/Tp at a time), so the query stays
+// a wave-uniform scalar operand; the last wave of a query's kc candidates is partly idle rather than straddling two queries.
+//
+// Batch-wide query operands, built once per call:
+//   qpk : [Q][npass] blocks of kMsRerankBlk(dim) floats; block (q, p) holds query q's tokens 32p .. 32p + NQ_p - 1 packed as
+//         [chunk][NQ_p][4] (maxsim_pack_query_kernel's layout), tokens at or beyond tq[q] as zeros. NQ_p = ms_pass_nq of the
+//         BATCH's longest query, since the pass' kernel instantiation is one for all queries;
+//   aa, saa : [Q][Tq_stride] squared token norms and their square roots (cosine), zeros beyond tq[q].
+__host__ __device__ __forceinline__ constexpr uint32_t ms_pass_nq(uint32_t tq_max, uint32_t pass) {  // 8 / 16 / 32
+    const uint32_t left = tq_max > pass * kMsQ ? tq_max - pass * kMsQ : 0u;
+    return left <= 8 ? 8u : (left <= 16 ? 16u : (uint32_t)kMsQ);
+}
+__host__ __device__ __forceinline__ constexpr size_t ms_rerank_blk(size_t dim) { return (dim / 4 ? dim / 4 : 1) * (size_t)kMsQ * 4; }
+
+__global__ void maxsim_rerank_pack_kernel(const float* __restrict__ qtoks, const uint32_t* __restrict__ tq, uint32_t Q, uint32_t Tq_stride,
+                                          uint32_t dim, uint32_t npass, uint32_t tq_max, float* __restrict__ qpk) {
+    const size_t blk = ms_rerank_blk(dim);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)Q * npass * blk) return;
+    const uint32_t j = (uint32_t)(i % blk), p = (uint32_t)((i / blk) % npass), q = (uint32_t)(i / blk / npass);
+    const uint32_t NQ = ms_pass_nq(tq_max, p);
+    if (j >= (dim / 4) * NQ * 4) return;  // (the block is sized for NQ = 32)
+    const uint32_t e = j & 3, qi = (j >> 2) % NQ, c = (j >> 2) / NQ, tk = p * kMsQ + qi;
+    qpk[i] = tk < tq[q] ? qtoks[((size_t)q * Tq_stride + tk) * dim + 4 * c + e] : 0.0f;
+}
+
+// the roundings of query_token_sq_kernel + sqrt_kernel, for every token of the batch
+__global__ void maxsim_rerank_norms_kernel(const float* __restrict__ qtoks, const uint32_t* __restrict__ tq, uint32_t Q, uint32_t Tq_stride,
+                                           uint32_t dim, float* __restrict__ aa, float* __restrict__ saa) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)Q * Tq_stride) return;
+    const uint32_t q = (uint32_t)(i / Tq_stride), tk = (uint32_t)(i % Tq_stride);
+    const float r = tk < tq[q] ? query_token_sq(qtoks + i * dim, dim) : 0.0f;
     aa[i] = r;
+    saa[i] = ex::sqrt(r);
+}
+
+// Pass `pass` (query tokens 32*pass ..) over all Q*kc slots; slot q*kc + ci = candidate ci of query q. A query that ended on an
+// earlier pass is skipped; on its last pass a slot's composite [ord(score) | ~local document index] goes to keys[slot], before
+// that its running total to partial[slot]. An empty query (or T == 0) scores 0.0 without touching the corpus. A candidate
+// outside [index_base, index_base + ndocs) raises `bad` and is scored as document 0: no address is formed from a bad index.
+template <bool COS, int NQ, bool MULTI>
+__global__ __launch_bounds__(kMsThreads, 2) void maxsim_rerank_kernel(
+    const float* __restrict__ tok, const uint32_t* __restrict__ doc_len, uint32_t ndocs, uint32_t T, uint32_t Tp, uint32_t dim,
+    const float* __restrict__ qtoks /*[Q][Tq_stride][dim]*/, uint32_t Tq_stride, const uint32_t* __restrict__ tq /*[Q], <= Tq_stride*/,
+    const float* __restrict__ qpk, uint32_t npass, uint32_t pass, const float* __restrict__ q_aa /*[Q][Tq_stride] COS*/,
+    const float* __restrict__ q_saa /*[Q][Tq_stride] COS*/, const uint64_t* __restrict__ cand /*[Q][kc] global indices*/, uint32_t Q,
+    uint32_t kc, uint64_t index_base, float* __restrict__ partial /*[Q*kc], npass > 1*/, uint64_t* __restrict__ keys /*[Q*kc]*/,
+    uint32_t* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t docs_per_wave = 64 / Tp;
+    // the wave index as an SGPR value: the query index, its token count and every query operand address stay on the scalar unit
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * kMsThreads + threadIdx.x) >> 6);
+    const uint32_t nwaves = (gridDim.x * kMsThreads) >> 6;
+    const uint32_t wpq = (kc + docs_per_wave - 1) / docs_per_wave;  // waves' worth of work per query
+    const uint32_t units = Q * wpq;                                 // <= Q*kc, which the host keeps below 2^32
+    const int tmode = (dim % 4 == 0 && (Tp == 64 || Tp == 32 || Tp == 16 || Tp == 8)) ? 1 : 0;
+    const uint32_t p0 = pass * kMsQ;
+    for (uint32_t u = wave; u < units; u += nwaves) {
+        const uint32_t q = u / wpq, w = u - q * wpq;
+        const uint32_t tqq = tq[q];
+        if (pass != 0 && tqq <= p0) continue;  // the query ended on an earlier pass: its keys are written
+        const uint32_t nq = tqq > p0 ? min(tqq - p0, (uint32_t)kMsQ) : 0u;
+        const bool last = tqq <= p0 + kMsQ;
+        const uint32_t ci = w * docs_per_wave + lane / Tp, t = lane % Tp;
+        const bool valid = ci < kc;
+        const uint32_t slot = q * kc + (valid ? ci : 0u);
+        uint32_t doc = 0;
+        if (valid) {
+            const uint64_t g = cand[slot];
+            if (g < index_base || g - index_base >= ndocs) {
+                if (t == 0) atomicOr(bad, 1u);
+            } else {
+                doc = (uint32_t)(g - index_base);
+            }
+        }
+        if (nq == 0 || T == 0) {  // wave-uniform; maxsim.rs:97-99
+            if (t == 0 && valid) keys[slot] = cand_make(f32_ord(0.0f), doc);
+            continue;
+        }
+        const uint32_t len = valid ? (doc_len ? min(doc_len[doc], T) : T) : 0;
+        const size_t qrow = (size_t)q * Tq_stride + p0;
+        const float total = maxsim_wave_pass<COS, NQ, MULTI>(
+            tok, T, Tp, dim, lane, tmode, doc, len, qtoks + qrow * dim, qpk + ((size_t)q * npass + pass) * ms_rerank_blk(dim), nq,
+            COS ? q_aa + qrow : nullptr, COS ? q_saa + qrow : nullptr,
+            [&]() { return (t == 0 && valid && pass != 0) ? partial[slot] : -0.0f; });
+        if (t == 0 && valid) {
+            if (last) keys[slot] = cand_make(f32_ord(len == 0 ? 0.0f : total), doc);  // empty document -> 0.0 (maxsim.rs:97-99)
+            else partial[slot] = total;
+        }
+    }
 }
 
 // ---- MFMA engine: approximate scores of every document, then exact re-score of the best (api.hip) ---------------

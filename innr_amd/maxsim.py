@@ -188,6 +188,68 @@ class DocumentCorpus:
         r = int(out_k.value)
         return idx[:, :r].copy(), sc[:, :r].copy()
 
+    def rerank(self, queries, candidates, k: int, cosine: bool = False):
+        """Second stage of a late-interaction pipeline: query j scored exactly against ITS candidate documents
+        candidates[j] (global document indices, no duplicates within one query), all queries in one device call
+        (innr_maxsim_rerank). `queries`: a list of [Tq_i, dim] token matrices or a [Q, Tq, dim] array; `candidates`: a
+        [Q, kc] integer array. Returns (indices [Q, k'], scores [Q, k']), k' = min(k, kc), row j ordered by score
+        descending, ties -> lower index; scores bit-identical to `scores(queries[j])` at those documents. With torch CUDA
+        tensors for both (`queries` then [Q, Tq, dim]) the device entry point runs and the results are CUDA tensors
+        (int64 / float32)."""
+        cos = 1 if cosine else 0
+        if hasattr(candidates, "is_cuda") and candidates.is_cuda and hasattr(queries, "is_cuda") and queries.is_cuda:
+            import torch
+            if queries.ndim != 3 or candidates.ndim != 2 or candidates.shape[0] != queries.shape[0]:
+                raise InnrPanic("rerank: queries must be [Q, Tq, dim] and candidates [Q, kc]")
+            q = queries.to(dtype=torch.float32).contiguous()
+            cd = candidates.to(dtype=torch.int64).contiguous()
+            nq, stride, dim = (int(x) for x in q.shape)
+            kc = int(cd.shape[1])
+            self._ctx.bind_torch_stream()  # queries and candidates were produced on torch's stream, the results are consumed there
+            kk = max(min(int(k), kc), 1)
+            idx = torch.empty((max(nq, 1) * kk,), dtype=torch.int64, device=cd.device)
+            sc = torch.empty((max(nq, 1) * kk,), dtype=torch.float32, device=cd.device)
+            out_k = C.c_size_t(0)
+            check(load().innr_maxsim_rerank_dev(self._h, cos, C.c_void_p(q.data_ptr()) if q.numel() else None, nq, None, stride, dim,
+                                                C.c_void_p(cd.data_ptr()) if cd.numel() else None, kc, int(k),
+                                                C.c_void_p(idx.data_ptr()), C.c_void_p(sc.data_ptr()), C.byref(out_k)))
+            r = int(out_k.value)
+            return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+        if hasattr(queries, "is_cuda"):
+            queries = queries.detach().cpu().numpy()
+        if hasattr(candidates, "is_cuda"):
+            candidates = candidates.detach().cpu().numpy()
+        qs = [_tokens(q, "query") for q in queries]
+        nq = len(qs)
+        if nq == 0:
+            return np.empty((0, 0), np.uint64), np.empty((0, 0), np.float32)
+        cd = np.asarray(candidates)
+        if cd.size and not np.issubdtype(cd.dtype, np.integer):
+            raise InnrPanic("rerank: candidates must be an integer array")
+        cd = np.ascontiguousarray(cd.astype(np.uint64, copy=False))  # (a negative index wraps far outside any corpus: E_BAD_ARG)
+        if cd.ndim != 2 or cd.shape[0] != nq:
+            raise InnrPanic(f"rerank: candidates must be [Q, kc] with Q = {nq} (got shape {cd.shape})")
+        kc = cd.shape[1]
+        for q in qs:
+            if q.size and q.shape[1] != self._dim:
+                raise InnrPanic(f"dimension mismatch (doc): query dim {q.shape[1]}, document dim {self._dim}")
+        stride = max([q.shape[0] for q in qs] + [1])
+        packed = np.zeros((max(nq, 1), stride, self._dim), dtype=np.float32)
+        tq = np.zeros(max(nq, 1), dtype=np.uint32)
+        for i, q in enumerate(qs):
+            if q.size:
+                packed[i, :q.shape[0]] = q
+                tq[i] = q.shape[0]
+        kk = max(min(int(k), kc), 1)
+        idx = np.empty((max(nq, 1), kk), dtype=np.uint64)
+        sc = np.empty((max(nq, 1), kk), dtype=np.float32)
+        out_k = C.c_size_t(0)
+        check(load().innr_maxsim_rerank(self._h, cos, C.c_void_p(packed.ctypes.data), nq, C.c_void_p(tq.ctypes.data), stride,
+                                        self._dim, C.c_void_p(cd.ctypes.data) if cd.size else None, kc, int(k),
+                                        C.c_void_p(idx.ctypes.data), C.c_void_p(sc.ctypes.data), C.byref(out_k)))
+        r = int(out_k.value)
+        return idx[:nq, :r].copy(), sc[:nq, :r].copy()
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             if getattr(self._ctx, "handle", None):

@@ -86,6 +86,8 @@ pub mod ffi {
         pub fn innr_maxsim_scores(d: *mut InnrDocs, cosine: c_int, qtok: *const f32, tq: usize, dim: usize, out: *mut f32) -> c_int;
         pub fn innr_maxsim_topk(d: *mut InnrDocs, cosine: c_int, qtok: *const f32, tq: usize, dim: usize, k: usize, engine: c_int, out_doc: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_maxsim_topk_multi(d: *mut InnrDocs, cosine: c_int, qtoks: *const f32, q: usize, tq: *const u32, tq_stride: usize, dim: usize, k: usize, engine: c_int, out_doc: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_maxsim_rerank(d: *mut InnrDocs, cosine: c_int, qtoks: *const f32, q: usize, tq: *const u32, tq_stride: usize, dim: usize, cand: *const u64, kc: usize, k: usize, out_doc: *mut u64, out_score: *mut f32, out_k: *mut usize) -> c_int;
+        pub fn innr_maxsim_rerank_dev(d: *mut InnrDocs, cosine: c_int, d_qtoks: *const f32, q: usize, tq: *const u32, tq_stride: usize, dim: usize, d_cand: *const u64, kc: usize, k: usize, d_out_doc: *mut u64, d_out_score: *mut f32, out_k: *mut usize) -> c_int;
         pub fn innr_batch_dimension_variance(b: *mut InnrBatch, out: *mut f32) -> c_int;
         pub fn innr_batch_knn_filtered(b: *mut InnrBatch, q: *const f32, d: usize, k: usize, mask: *const u8, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize) -> c_int;
         pub fn innr_batch_knn_filtered_multi(b: *mut InnrBatch, metric: c_int, queries: *const f32, q: usize, d: usize, k: usize, mask: *const u8, engine: c_int, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
@@ -511,6 +513,30 @@ pub mod maxsim {
             check(unsafe { ffi::innr_maxsim_topk(self.h, cosine as i32, q.as_ptr(), query_tokens.len(), dim, k, ffi::INNR_KNN_AUTO,
                                                  idx.as_mut_ptr(), sc.as_mut_ptr(), &mut n, std::ptr::null_mut()) });
             (0..n).map(|i| (idx[i] as usize, sc[i])).collect()
+        }
+        /// Second stage: `queries[j]` scored exactly against ITS candidate documents `candidates[j]` (global indices, the
+        /// same count for every query, no duplicates within one); per query the `min(k, count)` best as `(document, score)`,
+        /// best first, scores identical to `maxsim()` per pair. One device call for all queries (innr_maxsim_rerank).
+        #[must_use] pub fn rerank(&self, queries: &[&[&[f32]]], candidates: &[&[u64]], k: usize, cosine: bool) -> Vec<Vec<(usize, f32)>> {
+            assert_eq!(queries.len(), candidates.len(), "one candidate list per query");
+            let nq = queries.len();
+            let kc = candidates.first().map_or(0, |c| c.len());
+            assert!(candidates.iter().all(|c| c.len() == kc), "every query brings the same number of candidates");
+            let dim = queries.iter().flat_map(|q| q.first()).map(|t| t.len()).next().unwrap_or(self.dim);
+            assert!(queries.iter().all(|q| q.iter().all(|t| t.len() == dim)), "dimension mismatch (query)");
+            let stride = queries.iter().map(|q| q.len()).max().unwrap_or(0);
+            let mut packed = vec![0f32; nq * stride * dim];
+            let mut tq = vec![0u32; nq];
+            for (j, q) in queries.iter().enumerate() {
+                tq[j] = q.len() as u32;
+                for (t, tokv) in q.iter().enumerate() { packed[(j * stride + t) * dim..][..dim].copy_from_slice(tokv); }
+            }
+            let cand: Vec<u64> = candidates.iter().flat_map(|c| c.iter().copied()).collect();
+            let kk = k.min(kc).max(1);
+            let (mut idx, mut sc, mut n) = (vec![0u64; nq.max(1) * kk], vec![0f32; nq.max(1) * kk], 0usize);
+            check(unsafe { ffi::innr_maxsim_rerank(self.h, cosine as i32, packed.as_ptr(), nq, tq.as_ptr(), stride, dim, cand.as_ptr(), kc, k,
+                                                   idx.as_mut_ptr(), sc.as_mut_ptr(), &mut n) });
+            (0..nq).map(|j| (0..n).map(|r| (idx[j * n + r] as usize, sc[j * n + r])).collect()).collect()
         }
     }
 }
