@@ -125,6 +125,29 @@ static void tuning_from_env(innr_tuning* t) {
     }
 }
 
+// One templated kernel launch of the filter and scan families, as its dispatch site chose it (innr_ctx::launch_log). Written by
+// plain host stores at the dispatch sites of every build; read only by the test hooks (innrdbg_launch_log), which
+// tests/test_gpu_kernel_variants.py decodes: its table names every instantiation a call may reach.
+enum LaunchFamily {
+    kLaunchGemmF32 = 1,    // gemm_filter_kernel<KIND, RR, MODE, WV>
+    kLaunchGemmBf16 = 2,   // gemm_bf16_filter_kernel<RR, 0, 1>: args RR, MODE, LIMBS
+    kLaunchGemmSplit = 3,  // gemm_bf16_filter_kernel<RR, MODE, 3>: args RR, MODE, LIMBS
+    kLaunchI8One = 4,      // gemm_i8h_filter_kernel<RR, MODE>
+    kLaunchI8Two = 5,      // gemm_i8_filter_kernel<RR, MODE>
+    kLaunchI8Small = 6,    // gemm_i8s_filter_kernel<12, NK, CT, MODE>: args NK, CT, MODE
+    kLaunchMsScan = 7,     // maxsim_scan_kernel<COS, NQ, MULTI>, once per pass
+    kLaunchMsTile = 8,     // maxsim_mfma_tile_kernel<COS, NB, NQ>, once per pass
+    kLaunchMsGeneric = 9,  // maxsim_mfma_kernel<COS>, once per pass
+    kLaunchMsRerank = 10,  // maxsim_rerank_kernel<COS, NQ, MULTI>, once per pass
+};
+struct LaunchRec {
+    uint8_t family;    // LaunchFamily
+    uint8_t lockstep;  // gemm_i8s_filter_kernel: the soft-lockstep `prog` buffer was passed
+    int16_t arg[4];    // the template arguments, in the order of the family's comment above (unused: 0)
+    uint32_t groups;   // query groups (tiles) of the launch; the maxsim families: queries per corpus pass
+};
+constexpr size_t kLaunchLogCap = 64;
+
 struct innr_ctx {
     innr_tuning tune;
     // One call at a time per context: the workspace below (grow-by-free DevBufs, the pinned bump allocator, `pending`,
@@ -184,7 +207,22 @@ struct innr_ctx {
     DevBuf flt_mask;   // ... the mask normalised to 0/1, [ldN]
     DevBuf flt_scan;   // ... passing vectors per chunk [nchunks], their exclusive scan [nchunks], the total, the mask-differs flag
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
+    LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (log_launch; read by a test hook)
+    uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
 };
+
+// record one templated launch (the caller holds the context's lock, as every dispatch site does): a few host stores
+static inline void log_launch(innr_ctx* c, int family, int a0, int a1 = 0, int a2 = 0, int a3 = 0, uint32_t groups = 1,
+                              bool lockstep = false) {
+    LaunchRec& r = c->launch_log[c->launch_total++ % kLaunchLogCap];
+    r.family = (uint8_t)family;
+    r.lockstep = lockstep ? 1 : 0;
+    r.arg[0] = (int16_t)a0;
+    r.arg[1] = (int16_t)a1;
+    r.arg[2] = (int16_t)a2;
+    r.arg[3] = (int16_t)a3;
+    r.groups = groups;
+}
 
 namespace innr {
 constexpr size_t kPinIn = 512 << 10, kPinOut = 768 << 10, kPinSmall = 256 << 10;
@@ -776,10 +814,13 @@ static innr_status launch_gemm(innr_batch* b, const GemmPlan& p, size_t nreal_q,
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, MODE == 2 ? 32u : p.KP, seed, nreal_q, kmargin, &gslots, &nslot));  // (MODE 2: only the bounds are used)
 #define INNR_GEMM_LAUNCH_W(RR, WV)                                                                               \
-    gemm_filter_kernel<KIND, RR, MODE, WV><<<p.nblocks, 64 * WV, 0, c->stream>>>(                                  \
-        KIND == kGemmU8 ? (const void*)b->C8 : (const void*)b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->Dpad, Qt, p.Qpad, \
-        p.nqt, p.qtg, p.tps, invn, invq, b->alpha / 255.0f, lists, counts, p.KP, kk, err, gslots, gslots + nslot, dump,   \
-        ld_dump)
+    do {                                                                                                         \
+        log_launch(c, kLaunchGemmF32, KIND, RR, MODE, WV, p.nqt);                                                \
+        gemm_filter_kernel<KIND, RR, MODE, WV><<<p.nblocks, 64 * WV, 0, c->stream>>>(                              \
+            KIND == kGemmU8 ? (const void*)b->C8 : (const void*)b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->Dpad, Qt, p.Qpad, \
+            p.nqt, p.qtg, p.tps, invn, invq, b->alpha / 255.0f, lists, counts, p.KP, kk, err, gslots, gslots + nslot, dump, \
+            ld_dump);                                                                                            \
+    } while (0)
     // the 8-, 2- and 1-wave tiles exist for the product path only (MODE 0; the narrow ones not for the u8 kind); the
     // layout-dump hook stays on 4 waves
 #define INNR_GEMM_LAUNCH(RR)                                                                                    \
@@ -793,7 +834,7 @@ static innr_status launch_gemm(innr_batch* b, const GemmPlan& p, size_t nreal_q,
         if (KIND == kGemmDot && p.waves == 8) INNR_GEMM_LAUNCH_W(6, ((MODE == 2 && KIND == kGemmDot) ? 8 : 4));
         else INNR_GEMM_LAUNCH_W(6, 4);
     } else
-    switch (p.cap) {
+    switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
         case 384: INNR_GEMM_LAUNCH(6); break;
         case 512: INNR_GEMM_LAUNCH(8); break;
         case 768: INNR_GEMM_LAUNCH(12); break;
@@ -1340,11 +1381,12 @@ static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nre
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
 #define INNR_BF16_LAUNCH(RR)                                                                                              \
+    log_launch(c, kLaunchGemmBf16, RR, 0, 1, 0, p.nqt);                                                                   \
     gemm_bf16_filter_kernel<RR, 0, 1><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                          \
         variant == kBfCos ? b->Abn : (variant == kBfL2 ? b->Abl : b->Ab), nullptr, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N, \
         variant == kBfL2 ? b->abl_nk : b->ab_nk, p.Qpad, p.nqt, p.qtg, p.tps,                                                  \
         c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, nullptr, 0)
-    switch (p.cap) {
+    switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
         case 384: INNR_BF16_LAUNCH(6); break;
         case 512: INNR_BF16_LAUNCH(8); break;
         case 768: INNR_BF16_LAUNCH(12); break;
@@ -1422,6 +1464,7 @@ static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nr
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
 #define INNR_SPLIT_LAUNCH(RR)                                                                                             \
+    log_launch(c, kLaunchGemmSplit, RR, MODE, 3, 0, p.nqt);                                                               \
     gemm_bf16_filter_kernel<RR, MODE, 3><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                      \
         cos ? b->Abn : b->Ab, cos ? b->Abnx : b->Abx, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N,          \
         b->ab_nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk,                  \
@@ -1429,7 +1472,7 @@ static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nr
     if constexpr (MODE == 1) {  // the dense-score dump: the list geometry plays no part
         INNR_SPLIT_LAUNCH(6);
     } else {
-        switch (p.cap) {
+        switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
             case 384: INNR_SPLIT_LAUNCH(6); break;
             case 512: INNR_SPLIT_LAUNCH(8); break;
             case 768: INNR_SPLIT_LAUNCH(12); break;
@@ -1983,6 +2026,25 @@ int innrdbg_last_filter(const innr_batch* b) { return b && b->ctx ? b->ctx->last
 
 // Test hook: how many selections innr_batch_knn_filtered_multi has built for this batch (its cache misses)
 uint32_t innrdbg_filter_selection_builds(const innr_batch* b) { return b ? b->fsel_builds : 0u; }
+
+// Test hook: the context's launch record (innr_ctx::launch_log), oldest first: up to `cap` entries of 16 bytes (LaunchRec) into
+// `out`, the number written returned; *total = launches recorded since the last reset (beyond kLaunchLogCap the oldest are gone).
+extern "C" size_t innrdbg_launch_log(innr_ctx* c, void* out, size_t cap, uint64_t* total) {
+    if (!c) return 0;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    static_assert(sizeof(LaunchRec) == 16, "the hook's reader decodes 16-byte entries");
+    if (total) *total = c->launch_total;
+    const uint64_t have = std::min<uint64_t>(c->launch_total, kLaunchLogCap);
+    const size_t n = out ? (size_t)std::min<uint64_t>(have, cap) : 0;
+    for (size_t i = 0; i < n; ++i)  // the last n entries
+        static_cast<LaunchRec*>(out)[i] = c->launch_log[(c->launch_total - n + i) % kLaunchLogCap];
+    return n;
+}
+extern "C" void innrdbg_launch_log_reset(innr_ctx* c) {
+    if (!c) return;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    c->launch_total = 0;
+}
 
 #endif  // INNR_TEST_HOOKS
 
@@ -2954,6 +3016,7 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
         c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump
 #define INNR_I8_LAUNCH(RR)                                                                                                \
     do {                                                                                                                  \
+        log_launch(c, two ? kLaunchI8Two : kLaunchI8One, RR, MODE, 0, 0, p.nqt);                                          \
         if (two) gemm_i8_filter_kernel<RR, MODE><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);                  \
         else gemm_i8h_filter_kernel<RR, MODE><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);                     \
     } while (0)
@@ -2971,10 +3034,12 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
         if (dyn > 48 * 1024) /* (per device and call: no process-wide state) */                                                      \
             INNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_i8s_filter_kernel<12, NKV, CTV, MODE>),           \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)i8s_dyn_lds_bytes(NKV, CTV)));      \
+        log_launch(c, kLaunchI8Small, NKV, CTV, MODE, 0, p.nqt, prog != nullptr);                                                   \
         gemm_i8s_filter_kernel<12, NKV, CTV, MODE><<<p.nblocks, 64 * kI8sWaves, dyn, c->stream>>>(                                   \
             corpus, c->q_bf16.as<char>(), 4 * p.ntiles, (uint32_t)b->N, p.Qpad, p.nqt, p.tps, qc, c->lists.as<uint64_t>(),          \
             c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, prog);                             \
     } while (0)
+            // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: I8_SMALL)
             if (p.small_ct == 4) {
                 switch (p.nk) {  // (plan_i8_small: even, 8 .. 16)
                     case 8: INNR_I8S_LAUNCH(8, 4); break;
@@ -3003,13 +3068,15 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
     } else if constexpr (MODE == 1) {
         INNR_I8_LAUNCH(6);
     } else if constexpr (MODE == 2) {  // collect (the completion pass): one-limb kernel, the list geometry plays no part
+        log_launch(c, kLaunchI8One, 6, 2, 0, 0, p.nqt);
         gemm_i8h_filter_kernel<6, 2><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);
     } else {
-        switch (p.cap) {
+        switch (p.cap) {  // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: I8_TILES)
             case 384: INNR_I8_LAUNCH(6); break;
             case 512: INNR_I8_LAUNCH(8); break;
             case 768: INNR_I8_LAUNCH(12); break;
             default:  // lists of 256 candidates: the two-limb kernel only (plan_i8)
+                log_launch(c, kLaunchI8Two, 20, MODE, 0, 0, p.nqt);
                 gemm_i8_filter_kernel<20, MODE><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);
                 break;
         }
@@ -3569,6 +3636,7 @@ static innr_status maxsim_scan_exact(innr_docs* d, int cosine, size_t Tq, const 
         const unsigned npk = (unsigned)(dim / 4) * NQV * 4;                                                             \
         if (npk)                                                                                                        \
             maxsim_pack_query_kernel<<<(npk + 255) / 256, 256, 0, c->stream>>>(qp, NQV, (uint32_t)dim, qpk);            \
+        log_launch(c, kLaunchMsScan, COSV, NQV, d->T > 64);                                                             \
         if (d->T > 64)                                                                                                  \
             maxsim_scan_kernel<COSV, NQV, true><<<blocks, kMsThreads, 0, c->stream>>>(                                  \
                 d->tok, d->doc_len, (uint32_t)nslots, (uint32_t)d->T, Tp, (uint32_t)dim, qp, qpk, nq,                   \
@@ -3578,6 +3646,7 @@ static innr_status maxsim_scan_exact(innr_docs* d, int cosine, size_t Tq, const 
                 d->tok, d->doc_len, (uint32_t)nslots, (uint32_t)d->T, Tp, (uint32_t)dim, qp, qpk, nq,                   \
                 COSV ? aa : nullptr, out, out, p0 == 0, doc_ids, COSV ? saa : nullptr);                                 \
     } while (0)
+        // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: MS_SCAN)
         if (cosine) {
             if (nq <= 8) INNR_MS_LAUNCH(true, 8); else if (nq <= 16) INNR_MS_LAUNCH(true, 16); else INNR_MS_LAUNCH(true, 32);
         } else {
@@ -3731,6 +3800,7 @@ static innr_status maxsim_approx(innr_docs* d, int cosine, const float* const* q
         INNR_HIP_CHECK(copy_in(c, nq_dev + 4 * (p0 / kMsQ), nq_host, sizeof(nq_host)));
         const uint32_t* nqp = nq_dev + 4 * (p0 / kMsQ);
 #define INNR_MS_TILE(COSV, NBV, NQV)                                                                                    \
+    log_launch(c, kLaunchMsTile, COSV, NBV, NQV, 0, (uint32_t)nqr);                                                     \
     maxsim_mfma_tile_kernel<COSV, NBV, NQV><<<blocks, kMsThreads, lds, c->stream>>>(                                     \
         d->tok, d->doc_len, COSV ? d->tok_inv : nullptr, (uint32_t)d->ndocs, (uint32_t)d->T, qB, nqp,                     \
         COSV ? qscale + p0 : nullptr, approx, approx, p0 == 0)
@@ -3741,6 +3811,7 @@ static innr_status maxsim_approx(innr_docs* d, int cosine, const float* const* q
         case 3: INNR_MS_TILE(COSV, 3, NQV); break;                                                                      \
         default: INNR_MS_TILE(COSV, 4, NQV); break;                                                                     \
     }
+        // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: MS_TILE, MS_GENERIC)
         if (tiled && nqr == 4) {
             if (cosine) { INNR_MS_TILE_NB(true, 4) } else { INNR_MS_TILE_NB(false, 4) }
         } else if (tiled && nqr == 2) {
@@ -3750,14 +3821,17 @@ static innr_status maxsim_approx(innr_docs* d, int cosine, const float* const* q
         } else if (nqr != 1) {
             set_error("internal: multi-query maxsim needs the tile-unrolled kernel");
             return INNR_E_UNSUPPORTED;
-        } else if (cosine)
+        } else if (cosine) {
+            log_launch(c, kLaunchMsGeneric, 1);
             maxsim_mfma_kernel<true><<<blocks, kMsThreads, lds, c->stream>>>(d->tok, d->doc_len, d->tok_inv, (uint32_t)d->ndocs,
                                                                              (uint32_t)d->T, (uint32_t)dim, qB, nq_host[0],
                                                                              qscale + p0, approx, approx, p0 == 0);
-        else
+        } else {
+            log_launch(c, kLaunchMsGeneric, 0);
             maxsim_mfma_kernel<false><<<blocks, kMsThreads, lds, c->stream>>>(d->tok, d->doc_len, nullptr, (uint32_t)d->ndocs,
                                                                               (uint32_t)d->T, (uint32_t)dim, qB, nq_host[0],
                                                                               nullptr, approx, approx, p0 == 0);
+        }
 #undef INNR_MS_TILE_NB
 #undef INNR_MS_TILE
         INNR_HIP_CHECK(hipGetLastError());
@@ -4069,6 +4143,7 @@ innr_status innr_maxsim_rerank_dev(innr_docs* d, int cosine, const float* d_qtok
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     for (size_t pass = 0; pass < npass; ++pass) {
 #define INNR_MS_RERANK(COSV, NQV, MULTIV)                                                                                \
+    log_launch(c, kLaunchMsRerank, COSV, NQV, MULTIV, 0, (uint32_t)Q);                                                   \
     maxsim_rerank_kernel<COSV, NQV, MULTIV><<<blocks, kMsThreads, 0, c->stream>>>(                                       \
         d->tok, d->doc_len, (uint32_t)d->ndocs, (uint32_t)d->T, Tp, (uint32_t)dim, d_qtoks, (uint32_t)Tq_stride, d_tq, qpk, \
         (uint32_t)npass, (uint32_t)pass, aa, saa, d_cand, (uint32_t)Q, (uint32_t)kc, d->index_base, partial, keys, bad)
@@ -4080,6 +4155,7 @@ innr_status innr_maxsim_rerank_dev(innr_docs* d, int cosine, const float* d_qtok
             default: INNR_MS_RERANK(COSV, 32, MULTIV); break;                 \
         }                                                                     \
     } while (0)
+        // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: MS_RERANK)
         if (cosine) {
             if (d->T > 64) INNR_MS_RERANK_NQ(true, true); else INNR_MS_RERANK_NQ(true, false);
         } else {

@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 import oracle
 from test_gpu_exact import B, _check_knn, _corpus, _queries, bits_equal, innr, same_knn  # noqa: F401  (fixtures)
+from test_gpu_kernel_variants import logged  # the context's launch record: which kernel instantiation served a call
 
 
 @pytest.mark.parametrize("n,dim,nq,k", [(10_000, 128, 100, 10), (20_000, 100, 513, 10), (70_000, 64, 600, 10), (3000, 20, 300, 48),
@@ -150,6 +151,13 @@ def test_int8_filter_of_f32_corpus_special_cases(B, innr):
     B.batch_knn_dot_multi(qs, vb, 100, engine=innr.KNN_MFMA_I8, stats=st)
     assert st.engine == innr.KNN_MFMA_I8  # k > 48: lists of k + 16 and the filter's completion pass
     _check_knn(B, innr, "dot", vb, data, qs, 100, innr.KNN_MFMA_I8)
+    # (on this well-separated data the lists of 128 prove every answer: the launch record showed no completion pass behind the two
+    #  calls above. 437 of the rows ~160 times each: more ties at the top than a list holds, no first-pass proof can hold, and the
+    #  completion pass -- a collect-mode (MODE 2) launch -- has to settle every query)
+    tied = np.tile(rows[:437], (161, 1))[:70_000].copy()
+    tied[::7] *= np.float32(1.0 + 2.0 ** -20)
+    _, log = logged(lambda: _check_knn(B, innr, "dot", tied, oracle.from_rows(tied), qs, 100, innr.KNN_MFMA_I8))
+    assert any(e.family in ("i8_small", "i8_one") and e.args[-1] == 2 for e in log), log
     B.batch_knn_dot_multi(qs, vb, 241, engine=innr.KNN_MFMA_I8, stats=st)
     assert st.engine == innr.KNN_EXACT  # beyond INNR_MAX_K: all scores + a sort
     _check_knn(B, innr, "l2", vb, data, qs, 10, innr.KNN_MFMA_I8)
@@ -209,6 +217,14 @@ def test_int8_filter_squared_l2(B, innr, n, dim, nq, k):
     _check_knn(B, innr, "dot", vb, oracle.from_rows(rows), qs, min(k, 48), innr.KNN_MFMA_I8)  # (the dot copy beside it, same range)
 
 
+def _l2_copy_nk(rows, data):
+    """K-steps of 64 dimensions of the squared-L2 int8 copy (api.hip ensure_f32_i8_corpus): D + R + 1 dimensions, R from the largest
+    squared norm over the corpus' value range, at most 120"""
+    nmax = float(np.float32(oracle.batch_norms(data).max()) ** 2) * 1.000001
+    r = int(min(120.0, max(1.0, np.ceil(0.5 * nmax / float(rows.max() - rows.min())))))
+    return -(-(rows.shape[1] + r + 1) // 128) * 2
+
+
 @pytest.mark.parametrize("dim,nq", [(64, 64), (200, 5), (300, 1), (500, 3), (600, 2), (768, 4), (1000, 2),
                                     (500, 65), (600, 100), (768, 128), (1000, 70),  # (65 .. 128 queries: four column tiles per wave)
                                     (600, 200), (768, 256)])  # (two query groups: a block per group and corpus slice)
@@ -223,25 +239,49 @@ def test_int8_small_batch_kernel_every_k_step_count(B, innr, dim, nq, ctx_option
     data = oracle.from_rows(rows)
     qs = _queries(nq, dim, 99, uniform=True)
     vb = B.VerticalBatch.from_rows(rows)
+    ct = 4 if nq > 64 else 2           # column tiles of 32 queries per wave
+    groups = -(-nq // (32 * ct))       # query groups: blocks side by side per corpus slice, in soft lockstep from two on
     for metric, fn in (("dot", B.batch_knn_dot_multi), ("cos", B.batch_knn_cosine_multi), ("l2", B.batch_knn_multi)):
         _check_knn(B, innr, metric, vb, data, qs, 10, innr.KNN_MFMA_I8)
         st = innr.KnnStats()
-        i1, s1 = fn(qs, vb, 10, engine=innr.KNN_MFMA_I8, stats=st)
+        (i1, s1), log = logged(lambda: fn(qs, vb, 10, engine=innr.KNN_MFMA_I8, stats=st))
         assert st.engine == innr.KNN_MFMA_I8 and st.queries_fallback <= 1
+        # the small-batch kernel served it, on the K-step count of the copy it filters on -- where that count has an instantiation
+        # (<= 16): the squared-L2 copy of the 1000-dimension rows has 18, which leaves that metric on the 512-query tile
+        nk = _l2_copy_nk(rows, data) if metric == "l2" else -(-dim // 128) * 2
+        small = [e for e in log if e.family == "i8_small" and e.args[2] == 0]  # (MODE 2: the completion pass of an unproven query)
+        if nk <= 16:
+            assert [e.args for e in small] == [(nk, ct, 0)] and small[0].groups == groups and small[0].lockstep == (groups > 1), log
+            assert not any(e.family in ("i8_one", "i8_two") and e.args[-1] == 0 for e in log), log
+        else:
+            assert metric == "l2" and dim == 1000 and not small and any(e.inst == ("i8_one", 12, 0) for e in log), log
         ctx_option("i8_no_small", 1)
-        i2, s2 = fn(qs, vb, 10, engine=innr.KNN_MFMA_I8)
+        (i2, s2), log = logged(lambda: fn(qs, vb, 10, engine=innr.KNN_MFMA_I8))
         ctx_option("i8_no_small", 0)
+        assert any(e.inst == ("i8_one", 12, 0) for e in log) and not any(e.family == "i8_small" for e in log), log  # the 512-query tile
         assert np.array_equal(i1, i2) and bits_equal(s1, s2)
 
 
 @pytest.mark.parametrize("k,nq", [(20, 9), (48, 70), (33, 1)])
-def test_int8_small_batch_k_17_to_48(B, innr, k, nq):
+def test_int8_small_batch_k_17_to_48(B, innr, k, nq, ctx_option):
     """k = 17 .. 48 in a small batch: lists of 128 on the small-batch kernel plus its collect pass for the proofs that fail (direct
-    lists would be 256 long: the two-limb kernel). Same answers as the oracle."""
-    n, dim = 140_000, 128
+    lists would be 256 long: the two-limb kernel). Same answers as the oracle, and as the 512-query tile (i8_no_small) bit for bit.
+    (Beyond 64 queries the small-batch kernel needs 8 K-steps or more: that row has 512 dimensions -- at 128 the launch record
+    showed the 512-query tile serving both runs.)"""
+    n, dim = 140_000, (128 if nq <= 64 else 512)
     rows, _ = _corpus(n, dim, 8, uniform=True)
     data = oracle.from_rows(rows)
     qs = _queries(nq, dim, 17, uniform=True)
+    ct = 4 if nq > 64 else 2
     vb = None
-    for metric in ("dot", "cos", "l2"):
+    for metric, fn in (("dot", B.batch_knn_dot_multi), ("cos", B.batch_knn_cosine_multi), ("l2", B.batch_knn_multi)):
         vb = _check_knn(B, innr, metric, vb if vb is not None else rows, data, qs, k, innr.KNN_MFMA_I8)
+        (i1, s1), log = logged(lambda: fn(qs, vb, k, engine=innr.KNN_MFMA_I8))
+        small = [e for e in log if e.family == "i8_small" and e.args[1:] == (ct, 0)]
+        assert len(small) == 1 and small[0].groups == 1 and not small[0].lockstep, log
+        assert not any(e.family in ("i8_one", "i8_two") and e.args[-1] == 0 for e in log), log
+        ctx_option("i8_no_small", 1)
+        (i2, s2), log = logged(lambda: fn(qs, vb, k, engine=innr.KNN_MFMA_I8))
+        ctx_option("i8_no_small", 0)
+        assert any(e.inst == ("i8_one", 12, 0) for e in log) and not any(e.family == "i8_small" for e in log), log
+        assert np.array_equal(i1, i2) and bits_equal(s1, s2)

@@ -11,6 +11,7 @@ import oracle
 import kat_cases as K
 from backends import HipBackend
 from test_gpu_exact import bits_equal, same_knn
+from test_gpu_kernel_variants import logged  # the context's launch record: which kernel instantiation served a call
 
 
 @pytest.fixture(scope="module")
@@ -162,13 +163,18 @@ def test_batch_knn_u8_small_batch_kernel(S, innr, nq, dim, ctx_option):
     qc = S.QuantizedCorpus.from_codes(codes, n, dim, S.QuantizationParams(alpha, offset))
     qs = oracle.generate_uniform(nq, dim, 321)
     st = innr.KnnStats()
-    idx, sc = qc.knn_multi(qs, k, engine=innr.KNN_MFMA_I8, stats=st)
+    (idx, sc), log = logged(lambda: qc.knn_multi(qs, k, engine=innr.KNN_MFMA_I8, stats=st))
     assert st.engine == innr.KNN_MFMA_I8
+    # the small-batch kernel served it: 2 column tiles per wave up to 64 queries, 4 beyond; one query group
+    small = [e for e in log if e.inst == ("i8_small", -(-dim // 128) * 2, 4 if nq > 64 else 2, 0)]
+    assert len(small) == 1 and small[0].groups == 1 and not small[0].lockstep, log
+    assert not any(e.family in ("i8_one", "i8_two") for e in log), log
     for j in range(nq):
         oi, os_ = _oracle_knn(qs[j], codes, alpha, offset, k)
         assert same_knn("dot", idx[j], sc[j], oi, os_), (j, idx[j], oi)
     ctx_option("i8_no_small", 1)
-    idx2, sc2 = qc.knn_multi(qs, k, engine=innr.KNN_MFMA_I8)
+    (idx2, sc2), log = logged(lambda: qc.knn_multi(qs, k, engine=innr.KNN_MFMA_I8))
+    assert any(e.inst == ("i8_one", 12, 0) for e in log) and not any(e.family == "i8_small" for e in log), log  # the 512-query tile
     assert np.array_equal(idx, idx2) and np.array_equal(sc.view(np.uint32), sc2.view(np.uint32))
 
 
@@ -186,7 +192,7 @@ def test_u8_edge_cases(S, innr):
         B.batch_dot([1.0, 2.0, 3.0, 4.0], type("X", (), {"_h": qc._h, "dimension": lambda s: 4, "num_vectors": lambda s: 3})())
 
 
-def test_u8_engines_agree_large(S, innr):
+def test_u8_engines_agree_large(S, innr, ctx_option):
     p = S.QuantizationParams.from_range(-1.0, 1.0)
     qc = S.QuantizedCorpus.generate(2_000_000, 128, p, seed=1)
     qs = oracle.generate_uniform(256, 128, 9)
@@ -198,8 +204,15 @@ def test_u8_engines_agree_large(S, innr):
         assert st.engine == (innr.KNN_MFMA_I8 if engine == innr.KNN_AUTO else engine)  # AUTO: the int8 filter
         print(f"u8 2Mx128 256q engine {st.engine}: gemm {st.gemm_ms:.2f} ms total {st.total_ms:.2f} ms fallback {st.queries_fallback}")
     st = innr.KnnStats()
-    i1, s1 = qc.knn_multi(qs[:13], 10, engine=innr.KNN_AUTO, stats=st)  # the copy exists: the int8 engine's small-batch kernel
+    (i1, s1), log = logged(lambda: qc.knn_multi(qs[:13], 10, engine=innr.KNN_AUTO, stats=st))  # the copy exists: the int8 engine's small-batch kernel
     assert st.engine == innr.KNN_MFMA_I8 and np.array_equal(i1, i2[:13]) and bits_equal(s1, s2[:13])
+    small = [e for e in log if e.inst == ("i8_small", 2, 2, 0)]
+    assert len(small) == 1 and small[0].groups == 1 and not small[0].lockstep and not any(e.family in ("i8_one", "i8_two") for e in log), log
+    ctx_option("i8_no_small", 1)  # the same call on the 512-query tile (lists of 32): same bits
+    (i3, s3), log = logged(lambda: qc.knn_multi(qs[:13], 10, engine=innr.KNN_AUTO, stats=st))
+    ctx_option("i8_no_small", 0)
+    assert any(e.inst == ("i8_one", 6, 0) for e in log) and not any(e.family == "i8_small" for e in log), log
+    assert st.engine == innr.KNN_MFMA_I8 and np.array_equal(i3, i1) and bits_equal(s3, s1)
     i1, s1 = qc.knn_multi(qs[:1], 10, engine=innr.KNN_AUTO, stats=st)  # one query: one pass of the exact scan streams the same bytes
     assert st.engine == innr.KNN_EXACT and np.array_equal(i1, i2[:1]) and bits_equal(s1, s2[:1])
     qc2 = S.QuantizedCorpus.generate(200_000, 128, p, seed=2)
