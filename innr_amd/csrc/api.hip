@@ -258,6 +258,16 @@ static hipError_t ctx_sync(innr_ctx* c) {
     c->pin_in_off = c->pin_out_off = 0;
     return e;
 }
+
+// The derived copies of its corpus a batch can own (innr_batch::copy), and what the batch keeps of each
+enum CopyKind { kCopyRows, kCopyBfDot, kCopyBfCos, kCopyBfL2, kCopyBfDotLo, kCopyBfCosLo, kCopyI8Dot, kCopyI8Cos, kCopyI8L2, kCopyKinds };
+struct CorpusCopy {
+    char* p = nullptr;
+    size_t bytes = 0;
+    uint32_t nk = 0;       // K-steps of this copy (the rows copy: Dr)
+    bool refused = false;  // rows, lo limbs (for the split pair): it did not fit -- do not try again on every call
+    bool weak = false;     // int8 kinds: most proofs failed on this corpus (a range blown up by outliers): AUTO stops picking the filter
+};
 }  // namespace innr
 
 
@@ -273,42 +283,33 @@ struct innr_batch {
     float max_norm = 0.0f;
     uint64_t index_base = 0;
     std::vector<float> dimvar;  // batch_dimension_variance, computed once (batch.rs:572)
-    // Row-major copy Vr[i*Dr + d] (Dr = D rounded up to 4), built on the first call that has MANY candidates per query to
-    // re-score exactly (the completion pass, k beyond the candidate lists): in the dimension-major store a candidate's D values
-    // lie in D different cache lines (64 B fetched per 4 B used); here they are contiguous. Always owned; + N*Dr*4 bytes.
-    float* Vr = nullptr;
-    size_t Dr = 0;
-    bool vr_refused = false;  // it did not fit: do not try again on every call
     // scalar-quantised corpus (scalar.rs): codes C8[d*ldN + i] instead of V, with the collection's params
     uint8_t* C8 = nullptr;
     float alpha = 1.0f, offset = 0.0f;
     // innr_batch_prefix_view: V / C8 belong to another batch (never freed here). Rows D..Dpad of a view can hold the
     // parent's next dimensions instead of zero padding; the GEMM engine (which multiplies all Dpad rows) is then off.
     bool is_view = false, gemm_ok = true;
-    // bf16 filter engine (kernels_gemm_bf16.h): K-packed bf16 copy of the corpus, built on first use, always owned
-    char* Ab = nullptr;
-    char* Abn = nullptr;  // the same with every row scaled by 1/||v||: the cosine filter (built on the first cosine call)
-    char* Abl = nullptr;  // the squared-L2 filter's copy: six more K columns per row (|v|^2 in three limbs, three ones)
-    uint32_t ab_nk = 0, abl_nk = 0;
-    // the split-bf16 filter of INNR_KNN_MFMA: the lo limbs x - rne_bf16(x) of Ab's (Abx) and Abn's (Abnx)
-    // values, in the same layout; built on first use when they fit, always owned
-    char* Abx = nullptr;
-    char* Abnx = nullptr;
-    bool split_refused = false, splitn_refused = false;  // a copy did not fit: do not try again on every call
-    // int8 filter engine (kernels_gemm_i8.h): K-packed signed copy of the u8 codes, built on first use, always owned
-    char* Ai8 = nullptr;
-    uint32_t ai8_nk = 0;
-    // ... and of an F32 batch: its values scalar-quantised with one (offset, alpha) for the whole corpus (Ai8, i8_*), resp. its
-    // normalised rows quantised over [-1, 1] (Ai8n: the cosine filter) -- INNR_KNN_MFMA_I8 on an f32 batch
-    char* Ai8n = nullptr;
-    float i8_alpha = 0.0f, i8_offset = 0.0f, i8n_alpha = 0.0f, i8n_offset = 0.0f;
-    // ... and the squared-L2 copy: the dot copy's quantisation plus R + 1 more dimensions that carry |v|^2 in two 8-bit limbs
-    // (pack_corpus_f32_i8_kernel); D' = D + R + 1, ai8l_nk K-steps
-    char* Ai8l = nullptr;
-    uint32_t ai8l_nk = 0, i8l_R = 0;
-    float i8l_nmax = 0.0f;
-    bool i8l_weak = false;
-    bool i8_weak = false, i8n_weak = false;  // most proofs failed on this corpus (a range blown up by outliers): AUTO stops picking the filter
+    // The derived copies of the corpus, indexed by innr::CopyKind; each is built on first use and always owned:
+    //  rows: row-major rows[i*Dr + d] (Dr = D rounded up to 4, kept in nk), built on the first call that has MANY candidates per
+    //    query to re-score exactly (the completion pass, k beyond the candidate lists): in the dimension-major store a candidate's D
+    //    values lie in D different cache lines (64 B fetched per 4 B used); here they are contiguous. + N*Dr*4 bytes.
+    //  bf16 filter engine (kernels_gemm_bf16.h): the K-packed bf16 copy (dot), the same with every row scaled by 1/||v|| (cosine,
+    //    built on the first cosine call) and the squared-L2 filter's copy: six more K columns per row (|v|^2 in three limbs, three ones)
+    //  split-bf16 filter of INNR_KNN_MFMA: the lo limbs x - rne_bf16(x) of the dot and the cosine copy's values, in
+    //    the same layout; built on first use when they fit
+    //  int8 filter engine (kernels_gemm_i8.h): of a u8 code batch the K-packed signed copy of the codes (the dot kind); of an F32
+    //    batch (INNR_KNN_MFMA_I8) its values scalar-quantised with one (offset, alpha) for the whole corpus (dot), its normalised
+    //    rows quantised over their own range (cosine), and the squared-L2 copy: the dot copy's quantisation plus R + 1 more
+    //    dimensions that carry |v|^2 in two 8-bit limbs (pack_corpus_f32_i8_kernel); D' = D + R + 1
+    innr::CorpusCopy copy[innr::kCopyKinds];
+    // what the int8 copies of an F32 batch were quantised with: the raw values' range (the dot and squared-L2 copies), the
+    // normalised rows' (the cosine copy), and the squared-L2 copy's extra dimensions
+    struct I8Range {
+        float alpha = 0.0f, offset = 0.0f;
+    } i8_raw, i8_norm;
+    I8Range& i8_range(innr::CopyKind k) { return k == innr::kCopyI8Cos ? i8_norm : i8_raw; }
+    uint32_t i8l2_R = 0;
+    float i8l2_nmax = 0.0f;
     uint32_t i8_weak_skips = 0;              // AUTO calls that skipped the int8 filter since (every 64th tries it again)
     uint32_t auto_small_calls = 0;           // AUTO calls with fewer than four queries while no int8 copy existed: the fourth builds it
     // innr_batch_knn_filtered_multi (kernels_select.h): the selection of the last mask -- its passing vectors compacted into a batch
@@ -322,6 +323,42 @@ struct innr_batch {
 };
 
 namespace innr {
+
+// which copy a call of a metric filters on: the bf16 kinds (lo: the split filter's lo limbs, dot and cosine only) and the int8 kinds
+static CopyKind bf16_kind(int metric, bool lo = false) {
+    if (metric == INNR_METRIC_COSINE) return lo ? kCopyBfCosLo : kCopyBfCos;
+    return lo ? kCopyBfDotLo : (metric == INNR_METRIC_L2SQ ? kCopyBfL2 : kCopyBfDot);
+}
+static CopyKind i8_kind(int metric) {
+    return metric == INNR_METRIC_COSINE ? kCopyI8Cos : (metric == INNR_METRIC_L2SQ ? kCopyI8L2 : kCopyI8Dot);
+}
+
+// The memory rule of every copy that is built unasked: it may be built when free memory is at least twice its size plus 8 GiB
+static bool copy_fits(size_t free_bytes, size_t copy_bytes) { return free_bytes >= 2 * copy_bytes + ((size_t)8 << 30); }
+
+// Device memory for copy `kind` (`what` names it in the error message); the caller packs into copy[kind].p. Two policies:
+// hard (the bf16 and int8 filter copies, which a call cannot do without): a failed hipMalloc is INNR_E_OOM;
+// soft (the rows copy, the lo limbs): the memory rule first, and when it or hipMalloc says no the refusal sticks, the HIP error
+// is cleared and the call goes on without the copy -- INNR_OK with a null pointer.
+static innr_status alloc_copy(innr_batch* b, CopyKind kind, size_t bytes, uint32_t nk, bool soft, const char* what) {
+    CorpusCopy& cc = b->copy[kind];
+    size_t free_b = 0, total_b = 0;
+    const bool fits = !soft || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && copy_fits(free_b, bytes));
+    const hipError_t e = fits ? hipMalloc((void**)&cc.p, bytes) : hipErrorOutOfMemory;
+    if (e == hipSuccess) {
+        cc.bytes = bytes;
+        cc.nk = nk;
+        return INNR_OK;
+    }
+    cc.p = nullptr;
+    if (!soft) {
+        set_error("hipMalloc(%zu bytes) for the %s failed: %s", bytes, what, hipGetErrorString(e));
+        return INNR_E_OOM;
+    }
+    (void)hipGetLastError();
+    cc.refused = true;
+    return INNR_OK;
+}
 
 static innr_status bind_device(innr_ctx* ctx) {
     INNR_HIP_CHECK(hipSetDevice(ctx->device));
@@ -706,16 +743,16 @@ static innr_status launch_rescore(innr_batch* b, ScoreSpace space, const float* 
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
-// u8 code corpus (rescore_u8_kernel); Ai8 / nk: the int8 filter's copy, eq its per-query quantisation share
+// u8 code corpus (rescore_u8_kernel); i8copy / nk: the int8 filter's copy, eq its per-query quantisation share
 static innr_status launch_rescore_u8(innr_batch* b, const float* dQ, size_t Q, const float* qsum, const float* qnorm, uint32_t KP,
                                      size_t kout, float err_scale, uint64_t* d_out_idx, float* d_out_score, uint32_t* fallback,
-                                     const float* eq, const uint4* Ai8, uint32_t nk, const uint32_t* gthr) {
+                                     const float* eq, const uint4* i8copy, uint32_t nk, const uint32_t* gthr) {
     innr_ctx* c = b->ctx;
     with_rk(KP, [&](auto rk) {
         rescore_u8_kernel<decltype(rk)::value><<<(unsigned)Q, 64, 0, c->stream>>>(
             b->C8, b->ldN, (uint32_t)b->D, dQ, qsum, qnorm, b->alpha / 255.0f, b->offset, c->sel.as<uint64_t>(),
             c->sel_cnt.as<uint32_t>(), KP, (uint32_t)kout, err_scale, b->index_base, d_out_idx, d_out_score, fallback, eq,
-            !c->tune.rescore_all, Ai8, nk, gthr);
+            !c->tune.rescore_all, i8copy, nk, gthr);
     });
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
@@ -1135,25 +1172,16 @@ __global__ __launch_bounds__(kSelThreads) void segment_topk_kernel(const uint64_
     }
 }
 
-// the row-major copy of an f32 batch (innr_batch::Vr), if it exists or fits with room to spare (twice its size + 8 GiB free)
+// the row-major copy of an f32 batch (kCopyRows), if it exists or fits with room to spare (copy_fits)
 static innr_status ensure_rowmajor(innr_batch* b, bool* have) {
-    *have = b->Vr != nullptr && !b->ctx->tune.no_rows_copy;
-    if (b->Vr || b->vr_refused || b->ctx->tune.no_rows_copy || !b->V || b->N == 0 || b->D == 0) return INNR_OK;
-    const size_t Dr = round_up(b->D, 4), bytes = b->N * Dr * sizeof(float);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * bytes + ((size_t)8 << 30)) {
-        b->vr_refused = true;
-        return INNR_OK;
-    }
-    if (hipMalloc((void**)&b->Vr, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        b->Vr = nullptr;
-        b->vr_refused = true;
-        return INNR_OK;
-    }
-    b->Dr = Dr;
+    CorpusCopy& rows = b->copy[kCopyRows];
+    *have = rows.p != nullptr && !b->ctx->tune.no_rows_copy;
+    if (rows.p || rows.refused || b->ctx->tune.no_rows_copy || !b->V || b->N == 0 || b->D == 0) return INNR_OK;
+    const size_t Dr = round_up(b->D, 4);
+    INNR_TRY(alloc_copy(b, kCopyRows, b->N * Dr * sizeof(float), (uint32_t)Dr, true, "row-major copy"));
+    if (!rows.p) return INNR_OK;
     dim3 grid((unsigned)((b->N + 31) / 32), (unsigned)((Dr + 31) / 32));
-    pdx_to_rows_kernel<<<grid, 256, 0, b->ctx->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, b->Vr, (uint32_t)Dr);
+    pdx_to_rows_kernel<<<grid, 256, 0, b->ctx->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, reinterpret_cast<float*>(rows.p), (uint32_t)Dr);
     INNR_HIP_CHECK(hipGetLastError());
     *have = true;
     return INNR_OK;
@@ -1175,9 +1203,11 @@ static innr_status collect_finish(innr_batch* b, int metric, const float* Qm, co
     bool rows = false;
     INNR_TRY(ensure_rowmajor(b, &rows));  // contiguous candidate rows instead of D cache lines each, when the copy exists or fits
     if (rows) {
-        if (cos) collect_scores_rows_kernel<1><<<sg, 256, 0, c->stream>>>(b->Vr, (uint32_t)b->Dr, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
-        else if (l2) collect_scores_rows_kernel<2><<<sg, 256, 0, c->stream>>>(b->Vr, (uint32_t)b->Dr, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
-        else collect_scores_rows_kernel<0><<<sg, 256, 0, c->stream>>>(b->Vr, (uint32_t)b->Dr, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
+        const CorpusCopy& rowc = b->copy[kCopyRows];
+        const float* rowp = reinterpret_cast<const float*>(rowc.p);
+        if (cos) collect_scores_rows_kernel<1><<<sg, 256, 0, c->stream>>>(rowp, rowc.nk, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
+        else if (l2) collect_scores_rows_kernel<2><<<sg, 256, 0, c->stream>>>(rowp, rowc.nk, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
+        else collect_scores_rows_kernel<0><<<sg, 256, 0, c->stream>>>(rowp, rowc.nk, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
     } else {
         if (cos) collect_scores_kernel<1><<<sg, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
         else if (l2) collect_scores_kernel<2><<<sg, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
@@ -1346,36 +1376,30 @@ static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, cons
     return collect_scatter(b, redo, kout, d_out_idx, d_out_score, c->sel_cnt.as<uint32_t>(), unresolved, gemm_ms);  // (synchronises)
 }
 
-enum { kBfDot = 0, kBfCos = 1, kBfL2 = 2 };  // which bf16 copy of the corpus a call filters on
-static uint32_t bf16_nk(const innr_batch* b, int variant = kBfDot) {  // K-steps of 32, even
-    return (uint32_t)(round_up((b->D ? b->D : 1) + (variant == kBfL2 ? kBfL2Extra : 0), 64) / 32);
+static uint32_t bf16_nk(const innr_batch* b, CopyKind kind = kCopyBfDot) {  // K-steps of 32, even
+    return (uint32_t)(round_up((b->D ? b->D : 1) + (kind == kCopyBfL2 ? kBfL2Extra : 0), 64) / 32);
 }
 
-static size_t bf16_copy_bytes(const innr_batch* b, int variant = kBfDot) { return (b->ldN / 128) * (size_t)bf16_nk(b, variant) * 512 * 16; }
+static size_t bf16_copy_bytes(const innr_batch* b, CopyKind kind = kCopyBfDot) { return (b->ldN / 128) * (size_t)bf16_nk(b, kind) * 512 * 16; }
 
-// normalised == true: the cosine copy (rows scaled by 1/||v||; needs b->invn)
-static innr_status ensure_bf16_corpus(innr_batch* b, int variant) {
-    char*& copy = variant == kBfCos ? b->Abn : (variant == kBfL2 ? b->Abl : b->Ab);
-    if (copy) return INNR_OK;
-    const uint32_t nk = bf16_nk(b, variant);
+// kind: kCopyBfDot, kCopyBfCos (rows scaled by 1/||v||; needs b->invn) or kCopyBfL2 (needs b->sqn)
+static innr_status ensure_bf16_corpus(innr_batch* b, CopyKind kind) {
+    const CorpusCopy& cc = b->copy[kind];
+    if (cc.p) return INNR_OK;
+    const uint32_t nk = bf16_nk(b, kind);
     const size_t units = (b->ldN / 128) * (size_t)nk * 512;  // 16-byte units
-    hipError_t e = hipMalloc((void**)&copy, units * 16);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) for the bf16 corpus copy failed: %s", units * 16, hipGetErrorString(e));
-        copy = nullptr;
-        return INNR_E_OOM;
-    }
+    INNR_TRY(alloc_copy(b, kind, units * 16, nk, false, "bf16 corpus copy"));
     pack_corpus_bf16_kernel<<<(unsigned)((units + 255) / 256), 256, 0, b->ctx->stream>>>(
-        b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(copy), variant == kBfCos ? b->invn : nullptr,
-        variant == kBfL2 ? b->sqn : nullptr);
+        b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(cc.p), kind == kCopyBfCos ? b->invn : nullptr,
+        kind == kCopyBfL2 ? b->sqn : nullptr);
     INNR_HIP_CHECK(hipGetLastError());
-    (variant == kBfL2 ? b->abl_nk : b->ab_nk) = nk;
     return INNR_OK;
 }
 
-static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nreal_q, const uint32_t* seed, int variant,
+static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nreal_q, const uint32_t* seed, CopyKind kind,
                                     const float* kmargin = nullptr, uint32_t kk = 0) {
     innr_ctx* c = b->ctx;
+    const CorpusCopy& cc = b->copy[kind];
     uint32_t* gslots = nullptr;
     size_t nslot = 0;
     if (!kmargin) kk = 0;
@@ -1383,8 +1407,7 @@ static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nre
 #define INNR_BF16_LAUNCH(RR)                                                                                              \
     log_launch(c, kLaunchGemmBf16, RR, 0, 1, 0, p.nqt);                                                                   \
     gemm_bf16_filter_kernel<RR, 0, 1><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                          \
-        variant == kBfCos ? b->Abn : (variant == kBfL2 ? b->Abl : b->Ab), nullptr, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N, \
-        variant == kBfL2 ? b->abl_nk : b->ab_nk, p.Qpad, p.nqt, p.qtg, p.tps,                                                  \
+        cc.p, nullptr, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N, cc.nk, p.Qpad, p.nqt, p.qtg, p.tps,  \
         c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, nullptr, 0)
     switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
         case 384: INNR_BF16_LAUNCH(6); break;
@@ -1405,36 +1428,30 @@ enum LastFilter { kFilterNone = 0, kFilterF32 = 1, kFilterBf16 = 2, kFilterSplit
 // (two-wave tile), 256 queries 15.5 vs 28.8.
 constexpr size_t kSplitMinQ = 65;
 
-// The hi (Ab / Abn) and lo (Abx / Abnx) limb copies of the dot / cosine kind. Each copy is built only with twice its size + 8 GiB
-// free (the rule of the other filter copies); *ok == false: one did not fit, the call filters on the f32 kernel instead.
-static innr_status ensure_split_corpus(innr_batch* b, bool cos, bool* ok) {
+// The hi and lo limb copies of the dot / cosine kind. Each copy is built only when it fits (copy_fits, the rule of the other
+// filter copies); *ok == false: one did not fit, the call filters on the f32 kernel instead.
+static innr_status ensure_split_corpus(innr_batch* b, int metric, bool* ok) {
     *ok = false;
-    bool& refused = cos ? b->splitn_refused : b->split_refused;
-    if (refused) return INNR_OK;
-    char*& hi = cos ? b->Abn : b->Ab;
-    char*& lo = cos ? b->Abnx : b->Abx;
-    const size_t bytes = bf16_copy_bytes(b, kBfDot);
-    for (int l = 0; l < 2; ++l) {
-        if ((l == 0 ? hi : lo) != nullptr) continue;
+    const CopyKind hk = bf16_kind(metric), lk = bf16_kind(metric, true);
+    CorpusCopy &hi = b->copy[hk], &lo = b->copy[lk];  // (lo.refused stands for the pair)
+    if (lo.refused) return INNR_OK;
+    const uint32_t nk = bf16_nk(b, hk);
+    const size_t bytes = bf16_copy_bytes(b, hk);
+    if (!hi.p) {  // (the rule like a lo limb; once it passes, a filter copy like any other: INNR_E_OOM when hipMalloc fails)
         size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * bytes + ((size_t)8 << 30)) {
-            refused = true;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !copy_fits(free_b, bytes)) {
+            lo.refused = true;
             return INNR_OK;
         }
-        if (l == 0) {
-            INNR_TRY(ensure_bf16_corpus(b, cos ? kBfCos : kBfDot));
-            continue;
-        }
-        if (hipMalloc((void**)&lo, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            lo = nullptr;
-            refused = true;
-            return INNR_OK;
-        }
-        const uint32_t nk = bf16_nk(b, kBfDot);
+        INNR_TRY(ensure_bf16_corpus(b, hk));
+    }
+    if (!lo.p) {
+        INNR_TRY(alloc_copy(b, lk, bytes, nk, true, "bf16 lo-limb copy"));
+        if (!lo.p) return INNR_OK;
         const size_t units = bytes / 16;
         pack_corpus_bf16_kernel<<<(unsigned)((units + 255) / 256), 256, 0, b->ctx->stream>>>(
-            b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(lo), cos ? b->invn : nullptr, nullptr, 1);
+            b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(lo.p), hk == kCopyBfCos ? b->invn : nullptr,
+            nullptr, 1);
         INNR_HIP_CHECK(hipGetLastError());
     }
     *ok = true;
@@ -1444,7 +1461,7 @@ static innr_status ensure_split_corpus(innr_batch* b, bool cos, bool* ok) {
 // c->q_bf16: the queries' hi limbs (nk K-steps), then their lo limbs (cosine: of the normalised queries, qscale = 1/||q||)
 static innr_status pack_queries_split(innr_batch* b, const GemmPlan& p, const float* dQ, size_t Q, const float* qscale) {
     innr_ctx* c = b->ctx;
-    const uint32_t nk = bf16_nk(b, kBfDot);
+    const uint32_t nk = bf16_nk(b);
     const size_t units = (size_t)nk * 4 * p.Qpad;
     INNR_TRY(c->q_bf16.ensure(2 * units * 16));
     for (int l = 0; l < 2; ++l) {
@@ -1456,9 +1473,10 @@ static innr_status pack_queries_split(innr_batch* b, const GemmPlan& p, const fl
 }
 
 template <int MODE>
-static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nreal_q, bool cos, const uint32_t* seed,
+static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nreal_q, int metric, const uint32_t* seed,
                                      const float* kmargin = nullptr, uint32_t kk = 0, float* dump = nullptr, size_t ld_dump = 0) {
     innr_ctx* c = b->ctx;
+    const CorpusCopy &hi = b->copy[bf16_kind(metric)], &lo = b->copy[bf16_kind(metric, true)];
     uint32_t* gslots = nullptr;
     size_t nslot = 0;
     if (!kmargin) kk = 0;
@@ -1466,8 +1484,8 @@ static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nr
 #define INNR_SPLIT_LAUNCH(RR)                                                                                             \
     log_launch(c, kLaunchGemmSplit, RR, MODE, 3, 0, p.nqt);                                                               \
     gemm_bf16_filter_kernel<RR, MODE, 3><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                      \
-        cos ? b->Abn : b->Ab, cos ? b->Abnx : b->Abx, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N,          \
-        b->ab_nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk,                  \
+        hi.p, lo.p, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N,                                       \
+        hi.nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk,                  \
         c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump)
     if constexpr (MODE == 1) {  // the dense-score dump: the list geometry plays no part
         INNR_SPLIT_LAUNCH(6);
@@ -1533,7 +1551,7 @@ static innr_status choose_f32_filter(innr_batch* b, int metric, size_t Q, size_t
                      (!mfin || (b->max_norm >= 1e-12f && b->max_norm <= 1e18f));
     if (use_split) {
         if (cos) INNR_TRY(ensure_invnorms(b));
-        INNR_TRY(ensure_split_corpus(b, cos, &use_split));  // does not fit: the f32 kernel
+        INNR_TRY(ensure_split_corpus(b, metric, &use_split));  // does not fit: the f32 kernel
     }
     *filter = use_bf16 ? kFilterBf16 : (use_split ? kFilterSplit : kFilterF32);
     if (level == 0) c->last_filter = *filter;
@@ -1562,7 +1580,7 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     float err_scale;
     INNR_TRY(choose_f32_filter(b, metric, Q, kout, bf16, kp_force, level, &filter, &p, &err_scale));
     const bool use_bf16 = filter == kFilterBf16, use_split = filter == kFilterSplit;
-    const int bfv = cos ? kBfCos : (l2 ? kBfL2 : kBfDot);
+    const CopyKind bfv = bf16_kind(metric);
     if (cos) INNR_TRY(ensure_invnorms(b));
     if (l2) INNR_TRY(ensure_sqnorms(b));
     INNR_TRY(prep_queries(b, p, dQ, Q, cos));  // K-major queries, exact query norms (c->q_norm), cosine: 1/||q|| at c->misc
@@ -1604,7 +1622,7 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     const uint32_t kk = (uint32_t)kout;
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     if (use_bf16) INNR_TRY(launch_gemm_bf16(b, p, Q, seed, bfv, kmargin, kk));
-    else if (use_split) INNR_TRY(launch_gemm_split<0>(b, p, Q, cos, seed, kmargin, kk));
+    else if (use_split) INNR_TRY(launch_gemm_split<0>(b, p, Q, metric, seed, kmargin, kk));
     else if (cos) INNR_TRY((launch_gemm<kGemmCos, 0>(b, p, Q, c->q_kmajor.as<float>(), b->invn, invq, nullptr, 0, seed, kmargin, kk)));
     else if (l2) INNR_TRY((launch_gemm<kGemmL2, 0>(b, p, Q, c->q_kmajor.as<float>(), b->sqn, invq, nullptr, 0, seed, kmargin, kk)));
     // (A first pass of the same kernel over 1/16 of the corpus, only to harvest tighter bounds for the full pass, was
@@ -1937,15 +1955,8 @@ void innr_batch_free(innr_batch* b) {
     if (b->invn) (void)hipFree(b->invn);
     if (b->sqn) (void)hipFree(b->sqn);
     if (b->max_norm_bits) (void)hipFree(b->max_norm_bits);
-    if (b->Vr) (void)hipFree(b->Vr);
-    if (b->Ab) (void)hipFree(b->Ab);
-    if (b->Abn) (void)hipFree(b->Abn);
-    if (b->Abl) (void)hipFree(b->Abl);
-    if (b->Abx) (void)hipFree(b->Abx);
-    if (b->Abnx) (void)hipFree(b->Abnx);
-    if (b->Ai8) (void)hipFree(b->Ai8);
-    if (b->Ai8n) (void)hipFree(b->Ai8n);
-    if (b->Ai8l) (void)hipFree(b->Ai8l);
+    for (const CorpusCopy& cc : b->copy)
+        if (cc.p) (void)hipFree(cc.p);
     delete b;
 }
 
@@ -2005,7 +2016,7 @@ innr_status innrdbg_split_scores(innr_batch* b, int metric, const float* queries
     INNR_TRY(ensure_norms(b));
     if (cos) INNR_TRY(ensure_invnorms(b));
     bool ok = false;
-    INNR_TRY(ensure_split_corpus(b, cos, &ok));
+    INNR_TRY(ensure_split_corpus(b, metric, &ok));
     if (!ok) return INNR_E_UNSUPPORTED;
     INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
     INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
@@ -2013,7 +2024,7 @@ innr_status innrdbg_split_scores(innr_batch* b, int metric, const float* queries
     INNR_TRY(pack_queries_split(b, p, c->q_row.as<float>(), Q, cos ? c->misc.as<float>() : nullptr));
     INNR_TRY(ensure_lists(c, p));
     INNR_TRY(c->scores.ensure(p.Qpad * b->ldN * sizeof(float)));
-    INNR_TRY(launch_gemm_split<1>(b, p, Q, cos, nullptr, nullptr, 0, c->scores.as<float>(), b->ldN));
+    INNR_TRY(launch_gemm_split<1>(b, p, Q, metric, nullptr, nullptr, 0, c->scores.as<float>(), b->ldN));
     INNR_HIP_CHECK(hipMemcpy2DAsync(out, b->N * sizeof(float), c->scores.p, b->ldN * sizeof(float),
                                     b->N * sizeof(float), Q, hipMemcpyDeviceToHost, c->stream));
     INNR_HIP_CHECK(ctx_sync(c));
@@ -2409,23 +2420,18 @@ innr_status innr_batch_knn_dev(innr_batch* b, int metric, const float* d_queries
         // one is ruled out; N*D*2 bytes) takes 6.0 - 6.7 ms there: from 9 queries on, where the alternative is the f32 GEMM.
         const bool big_enough = b->N >= 65536 && gemm_addressable(b, Q) && b->gemm_ok;
         if (big_enough && kout <= INNR_MAX_K && !b->ctx->tune.no_auto_bf16) {
-            const bool cosm = metric == INNR_METRIC_COSINE;
-            const int bfv = cosm ? kBfCos : (metric == INNR_METRIC_L2SQ ? kBfL2 : kBfDot);
+            const CorpusCopy &i8c = b->copy[i8_kind(metric)], &bfc = b->copy[bf16_kind(metric)];
             size_t free_b = 0, total_b = 0;
             const bool have_mem = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-            const size_t slack = (size_t)8 << 30;
             // (a corpus marked weak -- its proofs failed on the int8 filter -- is looked at again every 64th call: data change)
-            const bool l2m = metric == INNR_METRIC_L2SQ;
-            const bool weak = (cosm ? b->i8n_weak : (l2m ? b->i8l_weak : b->i8_weak)) && (++b->i8_weak_skips % 64u) != 0;
-            const bool i8_copy = (cosm ? b->Ai8n : (l2m ? b->Ai8l : b->Ai8)) != nullptr;
+            const bool weak = i8c.weak && (++b->i8_weak_skips % 64u) != 0;
             // (a caller that keeps sending one to three queries -- the reference's own one-query signature in a loop -- gets the copy
             //  with its fourth call: 1.6 ms per query from then on instead of 5.3)
-            const bool worth = Q >= 4 || (!i8_copy && ++b->auto_small_calls >= 4);
+            const bool worth = Q >= 4 || (!i8c.p && ++b->auto_small_calls >= 4);
             if (f32_i8_eligible(b, metric, Q, kout) && !b->ctx->tune.no_auto_i8 && !weak &&
-                (i8_copy || (worth && have_mem && free_b > 2 * f32_i8_copy_bytes(b, metric) + slack)))
+                (i8c.p || (worth && have_mem && copy_fits(free_b, f32_i8_copy_bytes(b, metric)))))
                 engine = INNR_KNN_MFMA_I8;
-            else if (Q >= 9 && ((bfv == kBfCos ? b->Abn : (bfv == kBfL2 ? b->Abl : b->Ab)) != nullptr ||
-                                (have_mem && free_b > 2 * bf16_copy_bytes(b, bfv) + slack)))
+            else if (Q >= 9 && (bfc.p || (have_mem && copy_fits(free_b, bf16_copy_bytes(b, bf16_kind(metric))))))
                 engine = INNR_KNN_MFMA_BF16;
         }
     }
@@ -2921,27 +2927,23 @@ static bool i8_eligible(const innr_batch* b, size_t Q) {
 }
 
 static innr_status ensure_i8_corpus(innr_batch* b) {
-    if (b->Ai8) return INNR_OK;
+    const CorpusCopy& cc = b->copy[kCopyI8Dot];
+    if (cc.p) return INNR_OK;
     const uint32_t nk = i8_nk(b);
-    const size_t ntiles = b->ldN / 128, bytes = ntiles * nk * (size_t)kI8StageBytes;
-    hipError_t e = hipMalloc((void**)&b->Ai8, bytes);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) for the int8 corpus copy failed: %s", bytes, hipGetErrorString(e));
-        b->Ai8 = nullptr;
-        return INNR_E_OOM;
-    }
+    const size_t ntiles = b->ldN / 128;
+    INNR_TRY(alloc_copy(b, kCopyI8Dot, ntiles * nk * (size_t)kI8StageBytes, nk, false, "int8 corpus copy"));
     const size_t nthreads = ntiles * nk * 128;
     pack_corpus_i8_kernel<<<(unsigned)((nthreads + 255) / 256), 256, 0, b->ctx->stream>>>(b->C8, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk,
-                                                                                      nthreads, reinterpret_cast<uint4*>(b->Ai8));
+                                                                                      nthreads, reinterpret_cast<uint4*>(cc.p));
     INNR_HIP_CHECK(hipGetLastError());
-    b->ai8_nk = nk;
     return INNR_OK;
 }
 
 struct I8Plan {
     size_t Qpad;
     uint32_t nqt, qtg, nslices, tps, KP, cap, nblocks, ntiles;
-    uint32_t nk;  // K-steps of 64 dimensions of the corpus copy the launch multiplies (the squared-L2 copy has more than the others)
+    const char* corpus;  // the copy the launch multiplies (built before the plan is made) ...
+    uint32_t nk;         // ... and its K-steps of 64 dimensions (the squared-L2 copy has more than the others)
     bool two;  // both limbs on the matrix pipe (256-query tiles) instead of one limb + fix-up (512-query tiles)
     bool small = false;  // gemm_i8s_filter_kernel (<= 128 queries, every wave a slice of its own): nslices waves, tps QUARTER tiles each
     uint32_t small_ct = 2;  // ... its column tiles of 32 queries per wave: 2 (<= 64 queries) or 4
@@ -2974,10 +2976,11 @@ static bool plan_i8_small(const innr_batch* b, I8Plan* p, size_t Q, bool seeded,
     p->tps = (nquarter + p->nslices - 1) / p->nslices;
     return true;
 }
-static I8Plan plan_i8(const innr_batch* b, size_t Q, size_t kout, uint32_t kp_override = 0, bool one_limb = false) {
+static I8Plan plan_i8(const innr_batch* b, CopyKind kind, size_t Q, size_t kout, uint32_t kp_override = 0, bool one_limb = false) {
     I8Plan p;
+    p.corpus = b->copy[kind].p;
     p.two = !one_limb && (i8_two_limb(b->ctx, kout) || kp_override > 128);  // (collect mode: always the one-limb kernel)
-    p.nk = b->ai8_nk ? b->ai8_nk : i8_nk(b);
+    p.nk = b->copy[kind].nk;
     const size_t bq = p.two ? (size_t)kI8BQ : (size_t)kI8hBQ;  // queries per block tile
     p.Qpad = round_up(Q, bq);
     p.nqt = (uint32_t)(p.Qpad / bq);
@@ -3002,9 +3005,7 @@ static I8Plan plan_i8(const innr_batch* b, size_t Q, size_t kout, uint32_t kp_ov
 
 template <int MODE>
 static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q, const float* qc, float* dump, size_t ld_dump,
-                                  const uint32_t* seed = nullptr, const char* corpus = nullptr, const float* kmargin = nullptr,
-                                  uint32_t kk = 0) {
-    if (!corpus) corpus = b->Ai8;
+                                  const uint32_t* seed = nullptr, const float* kmargin = nullptr, uint32_t kk = 0) {
     innr_ctx* c = b->ctx;
     uint32_t* gslots = nullptr;
     size_t nslot = 0;
@@ -3012,7 +3013,7 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
     INNR_TRY(prep_gthr(c, p.Qpad, MODE == 2 ? 32u : p.KP, seed, nreal_q, kmargin, &gslots, &nslot));  // (MODE 2: only the bounds are used)
     const bool two = p.two;
 #define INNR_I8_ARGS                                                                                                      \
-    corpus, c->q_bf16.as<char>(), p.ntiles, (uint32_t)b->N, p.nk, p.Qpad, p.nqt, p.qtg, p.tps, qc, c->lists.as<uint64_t>(), \
+    p.corpus, c->q_bf16.as<char>(), p.ntiles, (uint32_t)b->N, p.nk, p.Qpad, p.nqt, p.qtg, p.tps, qc, c->lists.as<uint64_t>(), \
         c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump
 #define INNR_I8_LAUNCH(RR)                                                                                                \
     do {                                                                                                                  \
@@ -3036,7 +3037,7 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)i8s_dyn_lds_bytes(NKV, CTV)));      \
         log_launch(c, kLaunchI8Small, NKV, CTV, MODE, 0, p.nqt, prog != nullptr);                                                   \
         gemm_i8s_filter_kernel<12, NKV, CTV, MODE><<<p.nblocks, 64 * kI8sWaves, dyn, c->stream>>>(                                   \
-            corpus, c->q_bf16.as<char>(), 4 * p.ntiles, (uint32_t)b->N, p.Qpad, p.nqt, p.tps, qc, c->lists.as<uint64_t>(),          \
+            p.corpus, c->q_bf16.as<char>(), 4 * p.ntiles, (uint32_t)b->N, p.Qpad, p.nqt, p.tps, qc, c->lists.as<uint64_t>(),          \
             c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, prog);                             \
     } while (0)
             // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: I8_SMALL)
@@ -3107,12 +3108,12 @@ static innr_status knn_u8_i8(innr_batch* b, const float* dQ, size_t Q, size_t ko
                              uint64_t* d_out_idx, float* d_out_score, uint32_t* nfallback, uint32_t* kept, float* gemm_ms) {
     innr_ctx* c = b->ctx;
     INNR_TRY(ensure_i8_corpus(b));
-    I8Plan p = plan_i8(b, Q, kout);
+    I8Plan p = plan_i8(b, kCopyI8Dot, Q, kout);
     const bool seeded = seeding_on(b, true, Q, p.KP);
     if (!plan_i8_small(b, &p, Q, seeded) && seeded && p.KP < 128 && Q <= 1024) {
         // the small-batch kernel is instantiated for lists of 128: a small k takes them too (a capacity, not a threshold -- the k
         // rule sets the bounds) rather than the 512-query tile
-        I8Plan p2 = plan_i8(b, Q, kout, 128u);
+        I8Plan p2 = plan_i8(b, kCopyI8Dot, Q, kout, 128u);
         if (plan_i8_small(b, &p2, Q, seeded)) p = p2;
     }
     INNR_TRY(prep_queries_i8(b, p, dQ, Q, qsum, b->alpha, b->offset));
@@ -3140,11 +3141,11 @@ static innr_status knn_u8_i8(innr_batch* b, const float* dQ, size_t Q, size_t ko
     const float* kmargin = nullptr;
     INNR_TRY(make_kmargin(c, kSpaceCode, err_scale, qnorm, nullptr, qc + 3 * p.Qpad, b->offset, qsum, Q, p.Qpad, &kmargin));
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-    INNR_TRY(launch_gemm_i8<0>(b, p, Q, qc, nullptr, 0, seed, nullptr, kmargin, (uint32_t)kout));
+    INNR_TRY(launch_gemm_i8<0>(b, p, Q, qc, nullptr, 0, seed, kmargin, (uint32_t)kout));
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP, (uint32_t)Q));
     INNR_TRY(launch_rescore_u8(b, dQ, Q, qsum, qnorm, p.KP, kout, err_scale, d_out_idx, d_out_score, fallback, qc + 3 * p.Qpad,
-                               reinterpret_cast<const uint4*>(b->Ai8), b->ai8_nk, gthr_bounds(c, p.Qpad, p.KP)));
+                               reinterpret_cast<const uint4*>(p.corpus), p.nk, gthr_bounds(c, p.Qpad, p.KP)));
     std::vector<uint32_t> redo;
     INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms));
     return redo_batch_u8(b, dQ, qsum, redo, kout, d_out_idx, d_out_score);
@@ -3160,7 +3161,7 @@ extern "C" innr_status innrdbg_i8_scores(innr_batch* b, const float* queries, si
     innr_ctx* c = b->ctx;
     INNR_ENTER(c);
     INNR_TRY(ensure_i8_corpus(b));
-    const I8Plan p = plan_i8(b, Q, 1);
+    const I8Plan p = plan_i8(b, kCopyI8Dot, Q, 1);
     INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
     INNR_TRY(c->q_norm.ensure(2 * p.Qpad * sizeof(float)));
     INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
@@ -3196,15 +3197,15 @@ static size_t f32_i8_copy_bytes(const innr_batch* b, int metric) {  // (squared 
     return (b->ldN / 128) * nk * kI8StageBytes;
 }
 
-enum { kI8Dot = 0, kI8Cos = 1, kI8L2 = 2 };  // which int8 copy of an f32 corpus a call filters on
-static innr_status ensure_f32_i8_corpus(innr_batch* b, int variant, bool* usable) {
+static innr_status ensure_f32_i8_corpus(innr_batch* b, CopyKind kind, bool* usable) {
     *usable = true;
-    const bool normalised = variant == kI8Cos;
-    char*& copy = variant == kI8Cos ? b->Ai8n : (variant == kI8L2 ? b->Ai8l : b->Ai8);
-    if (copy) return INNR_OK;
+    const bool normalised = kind == kCopyI8Cos, l2 = kind == kCopyI8L2;
+    const CorpusCopy& cc = b->copy[kind];
+    if (cc.p) return INNR_OK;
     // the range of what is quantised: the corpus values (dot and squared L2), resp. the normalised rows (for 768-dimensional
     // uniform data these live in +-0.06: quantising them over [-1, 1] would throw four of the eight bits away)
-    float offset = normalised ? b->i8n_offset : b->i8_offset, alpha = normalised ? b->i8n_alpha : b->i8_alpha;
+    innr_batch::I8Range& range = b->i8_range(kind);
+    float offset = range.offset, alpha = range.alpha;
     if (!(alpha > 0.0f)) {
         innr_ctx* c = b->ctx;
         INNR_TRY(c->misc.ensure(4096));
@@ -3223,12 +3224,11 @@ static innr_status ensure_f32_i8_corpus(innr_batch* b, int variant, bool* usable
             return INNR_OK;
         }
         offset = mn;
-        (normalised ? b->i8n_alpha : b->i8_alpha) = alpha;
-        (normalised ? b->i8n_offset : b->i8_offset) = offset;
+        range = {alpha, offset};
     }
     uint32_t nk = i8_nk(b), R = 0;
     float nmax = 0.0f;
-    if (variant == kI8L2) {
+    if (l2) {
         // |v|^2 in R + 1 more dimensions: R such that the weight -(nmax / alpha) / R of each stays near the 2 q_d beside it
         nmax = b->max_norm * b->max_norm * 1.000001f;
         const float ratio = nmax / alpha;
@@ -3239,24 +3239,16 @@ static innr_status ensure_f32_i8_corpus(innr_batch* b, int variant, bool* usable
         R = (uint32_t)std::min(120.0f, std::max(1.0f, ceilf(0.5f * ratio)));
         nk = (uint32_t)(round_up(b->D + R + 1, 128) / 64);
     }
-    const size_t ntiles = b->ldN / 128, bytes = ntiles * nk * (size_t)kI8StageBytes;
-    hipError_t e = hipMalloc((void**)&copy, bytes);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) for the int8 filter copy failed: %s", bytes, hipGetErrorString(e));
-        copy = nullptr;
-        return INNR_E_OOM;
-    }
+    const size_t ntiles = b->ldN / 128;
+    INNR_TRY(alloc_copy(b, kind, ntiles * nk * (size_t)kI8StageBytes, nk, false, "int8 filter copy"));
     const size_t nthreads = ntiles * nk * 128;
     pack_corpus_f32_i8_kernel<<<(unsigned)((nthreads + 255) / 256), 256, 0, b->ctx->stream>>>(
         b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, nthreads, offset, 255.0f / alpha, normalised ? b->invn : nullptr,
-        reinterpret_cast<uint4*>(copy), variant == kI8L2 ? b->sqn : nullptr, R, variant == kI8L2 ? 1.0f / nmax : 0.0f);
+        reinterpret_cast<uint4*>(cc.p), l2 ? b->sqn : nullptr, R, l2 ? 1.0f / nmax : 0.0f);
     INNR_HIP_CHECK(hipGetLastError());
-    if (variant == kI8L2) {
-        b->ai8l_nk = nk;
-        b->i8l_R = R;
-        b->i8l_nmax = nmax;
-    } else {
-        b->ai8_nk = nk;
+    if (l2) {
+        b->i8l2_R = R;
+        b->i8l2_nmax = nmax;
     }
     return INNR_OK;
 }
@@ -3277,13 +3269,13 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     if (cos) INNR_TRY(ensure_invnorms(b));
     if (l2) INNR_TRY(ensure_sqnorms(b));
     bool usable = true;
-    INNR_TRY(ensure_f32_i8_corpus(b, cos ? kI8Cos : (l2 ? kI8L2 : kI8Dot), &usable));
+    const CopyKind kind = i8_kind(metric);
+    INNR_TRY(ensure_f32_i8_corpus(b, kind, &usable));
     if (!usable) return INNR_OK;
     *served = true;
-    const float alpha = cos ? b->i8n_alpha : b->i8_alpha, offset = cos ? b->i8n_offset : b->i8_offset;
-    const char* copy = cos ? b->Ai8n : (l2 ? b->Ai8l : b->Ai8);
+    const float alpha = b->i8_range(kind).alpha, offset = b->i8_range(kind).offset;
     // squared L2 (pack_corpus_f32_i8_kernel): a dot product over D' = D + R + 1 dimensions plus per-query constants
-    const size_t Dq = l2 ? b->D + b->i8l_R + 1 : b->D;
+    const size_t Dq = l2 ? b->D + b->i8l2_R + 1 : b->D;
     // Lists of 4k + 64 let the k-th exact score clear the KP-th approximate one by a visible margin (k <= 48); beyond that the
     // lists hold k + 16 (one-limb kernel up to 128, two-limb kernel to 256), most proofs fail BY DESIGN and the completion pass
     // (one more pass of this filter in collect mode) settles them: k = 100 at C2 needs ~450 candidates per query.
@@ -3292,8 +3284,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     // 64) and the collect pass settles the rest: 2.1 ms for eight queries at k = 32, 4.0 for 64 at k = 48.
     const uint32_t direct_kp = pick_kp(4 * kout + 64, 0);
     const bool direct = direct_kp <= 128;
-    I8Plan p = plan_i8(b, Q, kout, collect_kth ? 32u : (direct ? direct_kp : std::max(128u, pick_kp(kout, 16))), collect_kth != nullptr);
-    if (l2) p.nk = b->ai8l_nk;
+    I8Plan p = plan_i8(b, kind, Q, kout, collect_kth ? 32u : (direct ? direct_kp : std::max(128u, pick_kp(kout, 16))), collect_kth != nullptr);
     const bool seeded = seeding_on(b, true, Q, p.KP);
     (void)plan_i8_small(b, &p, Q, seeded, collect_kth != nullptr);
     // exact query norms; cosine: 1/||q|| and the normalised copy the filter multiplies; sum and L1 norm of what it multiplies
@@ -3314,10 +3305,10 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
         INNR_HIP_CHECK(hipGetLastError());
         Qp = c->q_hat.as<float>();
     }
-    const float W = l2 ? b->i8l_nmax / alpha : 0.0f, w1 = l2 ? W / (float)b->i8l_R : 0.0f, w2 = W / 255.0f;
+    const float W = l2 ? b->i8l2_nmax / alpha : 0.0f, w1 = l2 ? W / (float)b->i8l2_R : 0.0f, w2 = W / 255.0f;
     if (l2) {
         INNR_TRY(c->q_hat.ensure(std::max<size_t>(Q * Dq, 1) * sizeof(float)));
-        f32i8_l2_queries_kernel<<<(unsigned)((Q * Dq + 255) / 256), 256, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)b->D, b->i8l_R, w1, w2,
+        f32i8_l2_queries_kernel<<<(unsigned)((Q * Dq + 255) / 256), 256, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)b->D, b->i8l2_R, w1, w2,
                                                                                      c->q_hat.as<float>());
         INNR_HIP_CHECK(hipGetLastError());
         f32i8_query_prep_kernel<<<(unsigned)Q, 64, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)b->D, nullptr, nullptr, qsum, ql1q);
@@ -3344,7 +3335,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
         // nmax, relative to |offset| + alpha, times W); the f32 squared-L2 engine's (6D + 40) u C_j covers the cached norms, the
         // constants and the reference's own direct-difference sum
         const float K0 = W * offset + w2 * (offset + 0.5f * alpha);
-        const float enc_err = b->i8l_nmax * (1.1f / 130050.0f + 3.0e-7f * (fabsf(offset) / alpha + 1.0f));
+        const float enc_err = b->i8l2_nmax * (1.1f / 130050.0f + 3.0e-7f * (fabsf(offset) / alpha + 1.0f));
         f32i8_l2_finish_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, c->stream>>>(qc, (uint32_t)p.Qpad, (uint32_t)Q, cq, Cj, K0, enc_err,
                                                                                 f32_filter_scale(b, metric));
         INNR_HIP_CHECK(hipGetLastError());
@@ -3365,7 +3356,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
         I8Plan pl = p;
         pl.KP = kCollectCap;
         INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-        INNR_TRY(launch_gemm_i8<2>(b, pl, Q, qc, nullptr, 0, thr, copy));
+        INNR_TRY(launch_gemm_i8<2>(b, pl, Q, qc, nullptr, 0, thr));
         INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
         INNR_TRY(collect_finish(b, metric, dQ, c->q_norm.as<float>(), Q, kout, d_out_idx, d_out_score, d_unresolved));
         return INNR_OK;  // (the caller reads ev[2..3] once it has synchronised)
@@ -3385,7 +3376,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     const float* kmargin = nullptr;
     INNR_TRY(make_kmargin(c, kSpaceEq, 0.0f, nullptr, nullptr, eq, 0.0f, nullptr, Q, p.Qpad, &kmargin));
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-    INNR_TRY(launch_gemm_i8<0>(b, p, Q, qc, nullptr, 0, seed, copy, kmargin, (uint32_t)kout));
+    INNR_TRY(launch_gemm_i8<0>(b, p, Q, qc, nullptr, 0, seed, kmargin, (uint32_t)kout));
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP, (uint32_t)Q));
     INNR_TRY(launch_rescore(b, metric_space(metric), dQ, Q, l2 ? Cj : nullptr, p.KP, kout, 0.0f, d_out_idx, d_out_score, fallback, eq,
@@ -3394,7 +3385,7 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms));
     // (lists sized for a direct proof that mostly fail: the corpus' range is blown up by outliers; AUTO takes the bf16 filter,
     //  whose error is relative, on this corpus from now on -- and looks at the int8 one again every 64th call, innr_batch_knn_dev)
-    if (direct && Q >= 16) (cos ? b->i8n_weak : (l2 ? b->i8l_weak : b->i8_weak)) = redo.size() * 2 > Q;
+    if (direct && Q >= 16) b->copy[kind].weak = redo.size() * 2 > Q;
     // ONE more pass of this filter in collect mode settles the unproven queries (k beyond the direct lists: nearly all of them)
     // (from the first unproven query on: one more pass over the int8 copy costs less than an exact pass over the f32 corpus)
     if (!redo.empty() && !c->tune.no_completion) {
@@ -3442,8 +3433,9 @@ innr_status innr_batch_knn_u8_dev(innr_batch* b, const float* d_queries, size_t 
             size_t free_b = 0, total_b = 0;
             const bool have_mem = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
             const size_t copy_b = (b->ldN / 128) * (size_t)i8_nk(b) * kI8StageBytes;
-            const bool worth = Q >= 4 || (Q >= 2 && !b->Ai8 && ++b->auto_small_calls >= 4);  // (the fourth small call builds the copy)
-            if (b->Ai8 ? Q >= 2 : (worth && have_mem && free_b > 2 * copy_b + ((size_t)8 << 30))) engine = INNR_KNN_MFMA_I8;
+            const bool have_copy = b->copy[kCopyI8Dot].p != nullptr;
+            const bool worth = Q >= 4 || (Q >= 2 && !have_copy && ++b->auto_small_calls >= 4);  // (the fourth small call builds the copy)
+            if (have_copy ? Q >= 2 : (worth && have_mem && copy_fits(free_b, copy_b))) engine = INNR_KNN_MFMA_I8;
         }
     }
     if (engine == INNR_KNN_MFMA_BF16) engine = INNR_KNN_MFMA;  // codes are exact in 8 bits: the low-precision filter is the int8 one

@@ -18,7 +18,7 @@
 //
 // LIMBS = 3: the f32 GEMM engine's TIGHT filter as a split-bf16 GEMM. Every value is written x = h + l + r with
 // h = rne_bf16(x), l = rne_bf16(x - h) (x - h is exact in f32, |r| <= 2^-16 |x|); the kernel accumulates qh.vh + qh.vl + ql.vh,
-// three bf16 products per dimension, each exact in f32. The corpus lo limbs live in a second copy Abx of Ab's exact layout, the
+// three bf16 products per dimension, each exact in f32. The corpus lo limbs live in a second copy (kCopyBfDotLo / kCopyBfCosLo) of the hi copy's exact layout, the
 // query lo limbs in a second Bb block right behind the first. A stage carries both 8-KiB corpus pieces (16 KiB, 8 stages =
 // 128 KiB of LDS); a step issues 2 DMA + 2 x 4 query loads (hi, hi, lo, lo per depth) -- still the same sequence every step.
 #pragma once
@@ -53,7 +53,7 @@ __device__ __forceinline__ uint16_t bf16_limb(float x, int l) {
 constexpr uint32_t kBfL2Extra = 6;  // the squared-L2 copy's additional K columns
 
 // one thread per 16-byte output unit (8 dimensions of one corpus row)
-// limb: 0 = the rounded values (Ab, the hi limb), 1 = their lo limbs (Abx, the split filter; not with sqn)
+// limb: 0 = the rounded values (the hi limb: kCopyBfDot / -Cos / -L2), 1 = their lo limbs (kCopyBfDotLo / -CosLo, the split filter; not with sqn)
 // rowscale (nullable): 1/||v|| per row (0 for zero-norm rows) -- the COSINE copy holds the normalised rows, so that the plain
 // dot of the filter kernel IS the approximate cosine (with the queries normalised the same way) and no norm is loaded per tile
 // sqn (nullable): |v|^2 per row -- the SQUARED-L2 copy carries six more K columns per row, [three bf16 limbs of |v|^2, 1, 1, 1],
@@ -142,7 +142,7 @@ struct alignas(16) GemmBf16Lds {
 };
 
 // MODE 0: fused top-k filter. MODE 1: dump the dense score matrix (layout test).
-// LIMBS 1: the bf16 filter (Abx unused). LIMBS 3: the split filter -- Abx the corpus lo limbs, Bb holds nk K-steps of query hi
+// LIMBS 1: the bf16 filter (Abx unused). LIMBS 3: the split filter -- Abx the corpus' lo-limb copy, Bb holds nk K-steps of query hi
 // limbs followed by nk K-steps of lo limbs.
 template <int R, int MODE, int LIMBS>
 __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(

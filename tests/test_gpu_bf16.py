@@ -13,18 +13,27 @@ from test_gpu_exact import B, _check_knn, _corpus, _queries, bits_equal, innr, s
 from test_gpu_kernel_variants import logged  # the context's launch record: which kernel instantiation served a call
 
 
-@pytest.mark.parametrize("n,dim,nq,k", [(10_000, 128, 100, 10), (20_000, 100, 513, 10), (70_000, 64, 600, 10), (3000, 20, 300, 48),
-                                        (257, 33, 5, 16), (1000, 64, 9, 33), (5, 3, 2, 10), (200_000, 32, 40, 1)])
+_DOT_SHAPES = [(10_000, 128, 100, 10), (20_000, 100, 513, 10), (70_000, 64, 600, 10), (3000, 20, 300, 48),
+               (257, 33, 5, 16), (1000, 64, 9, 33), (5, 3, 2, 10), (200_000, 32, 40, 1)]
+# ... and once with the batch's copies built in the reverse order (L2, cosine, dot), at the smallest shape that asserts the fallback
+# bound: at D = 128 the copies of one batch differ in their K-step counts (int8: 2 for dot / cosine, 4 for L2; bf16: 4 and 6), so
+# a count kept for one copy and used for another shows here
+_DOT_CASES = [pytest.param(*s, False, id="-".join(map(str, s))) for s in _DOT_SHAPES] + \
+             [pytest.param(10_000, 128, 100, 10, True, id="10000-128-100-10-reversed")]
+
+
+@pytest.mark.parametrize("n,dim,nq,k,reverse", _DOT_CASES)
 @pytest.mark.parametrize("filt", ["bf16", "int8"])
-def test_bf16_filter_dot_matches_oracle(B, innr, n, dim, nq, k, filt):
+def test_bf16_filter_dot_matches_oracle(B, innr, n, dim, nq, k, reverse, filt):
     rows, data = _corpus(n, dim, 77, uniform=True)
     rows = (rows * (1.0 + 0.5 * np.sin(np.arange(n, dtype=np.float32)))[:, None]).astype(np.float32)  # unequal norms: cosine != dot order
     data = oracle.from_rows(rows)
     vb = B.VerticalBatch.from_rows(rows)
     qs = _queries(nq, dim, 4242, uniform=True)
     engine = innr.KNN_MFMA_BF16 if filt == "bf16" else innr.KNN_MFMA_I8  # int8: the scalar-quantised corpus as the filter
-    for metric, fn, ofn in (("dot", B.batch_knn_dot_multi, oracle.batch_knn_dot), ("cos", B.batch_knn_cosine_multi, oracle.batch_knn_cosine),
-                            ("l2", B.batch_knn_multi, oracle.batch_knn)):
+    kinds = (("dot", B.batch_knn_dot_multi, oracle.batch_knn_dot), ("cos", B.batch_knn_cosine_multi, oracle.batch_knn_cosine),
+             ("l2", B.batch_knn_multi, oracle.batch_knn))
+    for metric, fn, ofn in kinds[::-1] if reverse else kinds:
         st = innr.KnnStats()
         idx, sc = fn(qs, vb, k, engine=engine, stats=st)
         # (squared L2 on the int8 filter: |v|^2 as two 8-bit limbs in R + 1 more dimensions of its own corpus copy)
