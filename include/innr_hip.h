@@ -300,6 +300,42 @@ innr_status innr_batch_knn_reordered(innr_batch* b, const float* q, size_t D, si
  * in index order. *out_n = number of survivors; at most `cap` of them are written. */
 innr_status innr_batch_l2_squared_pruning(innr_batch* b, const float* q, size_t D, float threshold, uint64_t* out_idx,
                                           float* out_dist, size_t cap, size_t* out_n);
+/* Range search: batch_l2_squared_pruning (batch.rs:320-365) for Q queries at once, each with its own threshold, for all three
+ * metrics (the reference's function is one query, squared L2; DOT / COSINE are this library's addition). queries: row-major [Q*D];
+ * thresholds: [Q]. A vector survives for query j iff
+ *   INNR_METRIC_L2SQ:          !(dist > thresholds[j])   -- the reference's rule (batch.rs:351): a NaN distance survives;
+ *   INNR_METRIC_DOT / _COSINE: !(score < thresholds[j])  -- the same rule for similarities;
+ * dist / score have the bits of innr_batch_scores for that query (cosine: the cached norms, both epsilon guards). Query j owns
+ * [out_offsets[j], out_offsets[j+1]) of the FULL result (out_offsets: Q + 1 entries, 64-bit: Q*N can pass 2^32), its entries in
+ * ascending index order as the reference pushes them, indices = index base + local index; *out_total = out_offsets[Q]. Only the
+ * entries at global positions < cap are written to out_idx / out_score; cap == 0 (out_idx / out_score may then be null) is a
+ * count-only call. *out_total > cap is still INNR_OK -- enlarge the buffers and call again (innr_batch_l2_squared_pruning's
+ * convention). For Q = 1 and squared L2 the result equals innr_batch_l2_squared_pruning's bit for bit.
+ * The dimension check comes first (INNR_E_DIM_MISMATCH); then N == 0 or Q == 0 give all-zero offsets. A u8 code batch, a null
+ * out_offsets / out_total, null thresholds with Q > 0: INNR_E_BAD_ARG.
+ * Engines: INNR_KNN_EXACT scans the corpus in the reference's arithmetic, up to eight queries per pass: one pass counts the
+ * survivors per 256-vector chunk, a second one -- which skips every chunk without survivors -- writes them. INNR_KNN_MFMA (and the
+ * _BF16 / _I8 requests) collects, in one pass of the f32 matrix-pipe filter, every vector whose approximate score is within the
+ * filter's error bound of the threshold, re-scores those exactly and keeps what passes the exact predicate; a query with more
+ * than 65536 collected vectors, a query norm or threshold outside the bound's range, and every query of a corpus whose largest
+ * norm is outside [1e-12, 1e18] are finished by the exact scan instead (stats->queries_fallback counts them). A prefix view whose
+ * length is no multiple of 32 has no matrix-pipe engine (innr_batch_knn's rule): the exact engine serves the whole call, nothing
+ * counts as a fallback. Results are bit-identical either way. INNR_KNN_AUTO: the exact scan for small batches, the collect path
+ * from a measured batch size on (kRangeAutoQ0 in api.hip, 64 in this build; DESIGN.md 4.5c has the table) -- a tuning constant, not part of this contract.
+ * stats->engine = INNR_KNN_MFMA if a collect pass ran, else INNR_KNN_EXACT; candidates_kept = the longest
+ * collected list; gemm_ms = device time of the collect passes (exact engine: of the scans), total_ms of the whole call.
+ * The host-memory entry point stages min(cap, Q*N) results on the device; where that is more than 256 MiB it counts first (one
+ * more search) and stages what the result needs, so a generous cap costs time, not memory; its stats describe the last search.
+ * Memory: the call works in rounds of at most 4096 queries whose workspace stays within 2 GiB (per query N/64 bytes of counts;
+ * on the collect path N/8 bytes of bitmap and 768 KiB of lists more).
+ * Out of scope: the int8 / bf16 collect modes, u8 code batches, a sharded variant. */
+innr_status innr_batch_range_search(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const float* thresholds,
+                                    int engine, uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap,
+                                    size_t* out_total, innr_knn_stats* stats);
+/* same, queries, thresholds, out_offsets, out_idx and out_score resident on the device; the call synchronises with the host */
+innr_status innr_batch_range_search_dev(innr_batch* b, int metric, const float* d_queries, size_t Q, size_t D,
+                                        const float* d_thresholds, int engine, uint64_t* d_out_offsets, uint64_t* d_out_idx,
+                                        float* d_out_score, size_t cap, size_t* out_total, innr_knn_stats* stats);
 
 /* ---- pairwise surface kept on the host: called per PAIR by graph indexes, so a kernel
  * launch cannot pay for itself. Plain host functions in the reference's portable arithmetic order. ------------ */

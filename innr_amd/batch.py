@@ -466,3 +466,76 @@ def batch_l2_squared_pruning(query, batch: VerticalBatch, threshold: float):
                                                _vp(idx), _vp(ds), n, C.byref(out_n)))
     r = int(out_n.value)
     return [(int(idx[i]), float(ds[i])) for i in range(r)]
+
+
+def batch_range_search(queries, batch: VerticalBatch, thresholds, metric: int = METRIC_L2SQ, engine: int = KNN_AUTO,
+                       stats: Optional[KnnStats] = None, max_results: Optional[int] = None):
+    """batch_l2_squared_pruning (batch.rs:320-365) for Q queries at once, each with its own threshold, any metric
+    (innr_batch_range_search): query j keeps every vector with !(distance > thresholds[j]) (squared L2) or !(score < thresholds[j])
+    (dot, cosine), in index order. Returns (offsets uint64 [Q + 1], indices uint64 [total], scores float32 [total]); query j owns
+    [offsets[j], offsets[j + 1]). A scalar threshold is broadcast to all queries. max_results: room for that many results -- the
+    offsets are the full ones, indices / scores hold the first min(total, max_results) entries, 0 only counts; None: one call with
+    a guessed capacity and, only if that was exceeded, a second one with room for everything. Torch device tensors (queries on the
+    batch's GPU) take the device entry point: thresholds go to the device, offsets (int64), indices (int64) and scores stay there."""
+    n = batch.num_vectors()
+    lib = load()
+    st = stats if stats is not None else KnnStats()
+    total = C.c_size_t(0)
+    if hasattr(queries, "is_cuda") and queries.is_cuda:
+        import torch
+        q = queries.to(torch.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        q = q.contiguous()
+        nq, d = q.shape
+        if d != batch.dimension():
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {d}\n right: {batch.dimension()}")
+        t = thresholds if isinstance(thresholds, torch.Tensor) else torch.from_numpy(_f32(thresholds))
+        t = t.to(device=q.device, dtype=torch.float32).reshape(-1)
+        if t.numel() == 1 and nq != 1:
+            t = t.expand(nq)
+        if t.numel() != nq:
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {t.numel()}\n right: {nq}")
+        t = t.contiguous()
+        batch._ctx.bind_torch_stream()  # the queries were produced on torch's stream, the results are consumed there
+        off = torch.zeros((nq + 1,), dtype=torch.int64, device=q.device)
+
+        def call_dev(room: int):
+            idx = torch.empty((max(room, 1),), dtype=torch.int64, device=q.device)
+            sc = torch.empty((max(room, 1),), dtype=torch.float32, device=q.device)
+            check(lib.innr_batch_range_search_dev(batch._h, metric, C.c_void_p(q.data_ptr()), nq, d,
+                                                  C.c_void_p(t.data_ptr()) if nq else None, engine, C.c_void_p(off.data_ptr()),
+                                                  C.c_void_p(idx.data_ptr()), C.c_void_p(sc.data_ptr()), room, C.byref(total),
+                                                  C.byref(st)))
+            return idx, sc
+
+        call = call_dev
+    else:
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, d = q.shape
+        if d != batch.dimension():
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {d}\n right: {batch.dimension()}")
+        t = _f32(thresholds).reshape(-1)
+        if t.size == 1 and nq != 1:
+            t = np.full(nq, t[0], dtype=np.float32)
+        if t.size != nq:
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {t.size}\n right: {nq}")
+        off = np.zeros(nq + 1, dtype=np.uint64)
+
+        def call_host(room: int):
+            idx = np.empty(max(room, 1), dtype=np.uint64)
+            sc = np.empty(max(room, 1), dtype=np.float32)
+            check(lib.innr_batch_range_search(batch._h, metric, _vp(q) if q.size else None, nq, d, _vp(t) if t.size else None,
+                                              engine, _vp(off), _vp(idx), _vp(sc), room, C.byref(total), C.byref(st)))
+            return idx, sc
+
+        call = call_host
+    room = int(max_results) if max_results is not None else min(nq * n, max(1 << 16, 256 * nq))
+    idx, sc = call(room)
+    if max_results is None and int(total.value) > room:
+        room = int(total.value)
+        idx, sc = call(room)
+    r = min(int(total.value), room)
+    return off, idx[:r], sc[:r]

@@ -139,6 +139,7 @@ enum LaunchFamily {
     kLaunchMsTile = 8,     // maxsim_mfma_tile_kernel<COS, NB, NQ>, once per pass
     kLaunchMsGeneric = 9,  // maxsim_mfma_kernel<COS>, once per pass
     kLaunchMsRerank = 10,  // maxsim_rerank_kernel<COS, NQ, MULTI>, once per pass
+    kLaunchRangeScan = 11, // range_scan_kernel<QB, L2, COS, EMIT>: args QB, metric (INNR_METRIC_*), EMIT; groups = query groups
 };
 struct LaunchRec {
     uint8_t family;    // LaunchFamily
@@ -206,6 +207,11 @@ struct innr_ctx {
     DevBuf flt_in;     // innr_batch_knn_filtered_multi: the caller's mask bytes staged on the device (host-memory entry point)
     DevBuf flt_mask;   // ... the mask normalised to 0/1, [ldN]
     DevBuf flt_scan;   // ... passing vectors per chunk [nchunks], their exclusive scan [nchunks], the total, the mask-differs flag
+    DevBuf rs_cnt;     // innr_batch_range_search: survivors per 256-vector chunk [queries][nchunks + 1], scanned in place
+    DevBuf rs_bits;    // ... the collect path's survivor bitmaps [queries][ldN / 32]
+    DevBuf rs_tot;     // ... [queries] totals, then [queries] flags: the exact scan finishes this query
+    DevBuf rs_thr;     // ... the thresholds and [Q + 1] offsets of the host-memory entry point, staged on the device
+    DevBuf rs_off;
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (log_launch; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
@@ -1187,11 +1193,10 @@ static innr_status ensure_rowmajor(innr_batch* b, bool* have) {
     return INNR_OK;
 }
 
-// The second half of a completion pass, whatever filter collected: exact scores of every collected candidate (row-major copy when
-// it exists or fits, else column gathers), best kout per query -> d_out_* [Q][kout]; d_unresolved[q] = 1 for overflowed lists.
-// clist / ccnt: c->lists / c->counts as the collect-mode kernels left them; Qm: the queries the exact scores are taken with.
-static innr_status collect_finish(innr_batch* b, int metric, const float* Qm, const float* qnorm, size_t nq, size_t kout,
-                                  uint64_t* d_out_idx, float* d_out_score, uint32_t* d_unresolved) {
+// Exact composites of every collected candidate at c->sort_keys [nq][kCollectCap] (the first min(count, kCollectCap) of a query are
+// written), from the row-major copy when it exists or fits (*used_rows), else by column gathers. clist / ccnt: c->lists / c->counts
+// as the collect-mode kernels left them; Qm: the queries the exact scores are taken with. The range search shares this step.
+static innr_status collect_rescore(innr_batch* b, int metric, const float* Qm, const float* qnorm, size_t nq, bool* used_rows) {
     innr_ctx* c = b->ctx;
     const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
     const size_t D = b->D;
@@ -1214,6 +1219,19 @@ static innr_status collect_finish(innr_batch* b, int metric, const float* Qm, co
         else collect_scores_kernel<0><<<sg, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, Qm, b->norms, qnorm, clist, ccnt, kCollectCap, keys);
     }
     INNR_HIP_CHECK(hipGetLastError());
+    *used_rows = rows;
+    return INNR_OK;
+}
+// The second half of a completion pass, whatever filter collected: those exact scores, then the best kout per query -> d_out_*
+// [Q][kout]; d_unresolved[q] = 1 for overflowed lists.
+static innr_status collect_finish(innr_batch* b, int metric, const float* Qm, const float* qnorm, size_t nq, size_t kout,
+                                  uint64_t* d_out_idx, float* d_out_score, uint32_t* d_unresolved) {
+    innr_ctx* c = b->ctx;
+    const bool l2 = metric == INNR_METRIC_L2SQ;
+    bool rows = false;
+    INNR_TRY(collect_rescore(b, metric, Qm, qnorm, nq, &rows));
+    const uint64_t* keys = c->sort_keys.as<uint64_t>();
+    const uint32_t* ccnt = c->counts.as<uint32_t>();
     INNR_HIP_CHECK(hipMemsetAsync(d_unresolved, 0, nq * sizeof(uint32_t), c->stream));
     segment_topk_kernel<<<(unsigned)nq, kSelThreads, 0, c->stream>>>(keys, ccnt, kCollectCap, (uint32_t)kout, l2, b->index_base, d_out_idx,
                                                                     d_out_score, d_unresolved);
@@ -1333,19 +1351,15 @@ static float split_filter_scale(const innr_batch* b, int metric) {
            (metric == INNR_METRIC_COSINE ? 1.0f : b->max_norm);
 }
 
-// redo: the unproven queries (ascending), d_out_*: the first pass' output (its k-th score per query is read, the resolved
-// queries' rows are overwritten). *unresolved: those that still need the exact engine.
-static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, const std::vector<uint32_t>& redo, size_t kout,
-                                uint64_t* d_out_idx, float* d_out_score, std::vector<uint32_t>* unresolved, float* gemm_ms) {
+// One collect pass of the f32 GEMM filter (MODE 2) over nr queries Qr (row-major [nr][D]) with the FIXED per-query thresholds
+// x[j] - E (x: exact scores -- distances for squared L2 -- on the device): every site whose approximate score clears its query's
+// threshold goes to c->lists [Qpad][kCollectCap] (indices), c->counts [Qpad] (lengths; an overfull list keeps counting). Leaves the
+// exact query norms at c->q_norm, the thresholds at c->seed_score (0: x[j] - E is not finite, everything is collected) and the
+// pass between ev[2] and ev[3]. The completion pass of unproven kNN queries (x = x_k) and the range search (x = the caller's
+// thresholds) share it.
+static innr_status collect_pass(innr_batch* b, int metric, const float* Qr, size_t nr, size_t kout, const float* x) {
     innr_ctx* c = b->ctx;
-    const size_t nr = redo.size();
-    unresolved->clear();
-    if (nr == 0) return INNR_OK;
     const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
-    INNR_TRY(collect_gather(b, dQ, redo, kout, d_out_score));
-    innr_ctx::RedoBufs& rb = c->cmpl;
-    const float* kth = rb.qn.as<float>();  // x_k per unproven query
-    const float* Qr = rb.q.as<float>();
     GemmPlan p = plan_gemm(b, nr, kout, (!cos && !l2 && nr > 256) ? 8u : 4u, !cos && !l2);
     if (cos) INNR_TRY(ensure_invnorms(b));
     if (l2) INNR_TRY(ensure_sqnorms(b));
@@ -1354,10 +1368,10 @@ static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, cons
     float* Cj = nullptr;
     if (l2) INNR_TRY(l2_query_consts(b, p.Qpad, nr, invq, &Cj));
     const float err_scale = f32_filter_scale(b, metric);
-    // fixed thresholds: x_k - E (one key lower), in the kind's score space; 0 = "no bound" where that is not finite
+    // fixed thresholds: x - E (one key lower), in the kind's score space; 0 = "no bound" where that is not finite
     INNR_TRY(c->seed_score.ensure(p.Qpad * sizeof(uint32_t)));
     uint32_t* thr = c->seed_score.as<uint32_t>();
-    seed_thresholds_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(kth, (uint32_t)nr, 1u, metric_space(metric), err_scale,
+    seed_thresholds_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(x, (uint32_t)nr, 1u, metric_space(metric), err_scale,
                                                                                     c->q_norm.as<float>(), Cj, thr, (uint32_t)p.Qpad, 0u);
     INNR_HIP_CHECK(hipGetLastError());
     // global lists: [Qpad][kCollectCap] indices, [Qpad] lengths
@@ -1371,6 +1385,21 @@ static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, cons
     else if (l2) INNR_TRY((launch_gemm<kGemmL2, 2>(b, pl, nr, c->q_kmajor.as<float>(), b->sqn, invq, nullptr, 0, thr)));
     else INNR_TRY((launch_gemm<kGemmDot, 2>(b, pl, nr, c->q_kmajor.as<float>(), nullptr, nullptr, nullptr, 0, thr)));
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+    return INNR_OK;
+}
+
+// redo: the unproven queries (ascending), d_out_*: the first pass' output (its k-th score per query is read, the resolved
+// queries' rows are overwritten). *unresolved: those that still need the exact engine.
+static innr_status knn_complete(innr_batch* b, int metric, const float* dQ, const std::vector<uint32_t>& redo, size_t kout,
+                                uint64_t* d_out_idx, float* d_out_score, std::vector<uint32_t>* unresolved, float* gemm_ms) {
+    innr_ctx* c = b->ctx;
+    const size_t nr = redo.size();
+    unresolved->clear();
+    if (nr == 0) return INNR_OK;
+    INNR_TRY(collect_gather(b, dQ, redo, kout, d_out_score));
+    innr_ctx::RedoBufs& rb = c->cmpl;
+    const float* Qr = rb.q.as<float>();
+    INNR_TRY(collect_pass(b, metric, Qr, nr, kout, rb.qn.as<float>()));  // x_k per unproven query
     INNR_TRY(c->sel_cnt.ensure(nr * sizeof(uint32_t)));
     INNR_TRY(collect_finish(b, metric, Qr, c->q_norm.as<float>(), nr, kout, rb.idx.as<uint64_t>(), rb.sc.as<float>(), c->sel_cnt.as<uint32_t>()));
     return collect_scatter(b, redo, kout, d_out_idx, d_out_score, c->sel_cnt.as<uint32_t>(), unresolved, gemm_ms);  // (synchronises)
@@ -1794,7 +1823,8 @@ void innr_ctx_destroy(innr_ctx* c) {
                       &c->scores, &c->tmp_norms, &c->flags, &c->out_idx, &c->out_score, &c->misc, &c->seed_idx, &c->seed_score, &c->q_one, &c->sort_keys, &c->sort_tmp, &c->q_bf16, &c->q_pad, &c->q_hat,
                       &c->redo[0].q, &c->redo[0].idx, &c->redo[0].sc, &c->redo[0].map, &c->redo[0].qn,
                       &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
-                      &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan};
+                      &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan,
+                      &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off};
     for (DevBuf* b : bufs) b->release();
     if (c->pin) (void)hipHostFree(c->pin);
     for (auto& ev : c->ev)
@@ -4609,6 +4639,269 @@ innr_status innr_merge_topk_dev(innr_ctx* ctx, int metric, const uint64_t* d_idx
                                                           d_out_score);
     INNR_HIP_CHECK(hipGetLastError());
     INNR_HIP_CHECK(ctx_sync(ctx));
+    return INNR_OK;
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Range search: every vector within a per-query threshold (innr_batch_range_search)
+// =====================================================================================================================
+namespace innr {
+
+// Smallest batch INNR_KNN_AUTO sends through the collect pass: the smallest measured batch from which the collect path beats the
+// exact scan on both shapes by more than the spread of the repeats (tools/bench_range.py q0, squared L2, thresholds at the 100th best;
+// whole call, ms, exact / collect; profiles/range_search_*.txt):
+//      Q      1M x 128      10M x 768
+//     16    0.42 / 0.69    14.9 / 27.0
+//     32    0.73 / 0.75    28.0 / 27.2
+//     64    1.25 / 0.78    53.6 / 27.2
+//    128    2.40 / 0.92   104.4 / 27.7
+constexpr size_t kRangeAutoQ0 = 64;
+// Queries per round: their chunk counts, and on the collect path their bitmaps, lists and composites, stay within this
+// (10M vectors: ~2.2 MB per query on the collect path); never more than 4096 per collect launch
+constexpr size_t kRangeWorkspace = (size_t)2 << 30;
+constexpr size_t kRangeMaxRound = 4096;
+// Host-memory entry point: result staging up to this size is allocated for the caller's cap as it is; beyond it a count-only pass sizes it
+constexpr size_t kRangeStageDirect = (size_t)256 << 20;
+
+struct RangeScan {  // one launch of range_scan_kernel: nq queries (row-major, stride D) and where their counts / results go
+    const float* Q;
+    const float* qnorm;
+    const float* thr;
+    const uint32_t* qmap;
+    uint32_t nq;
+    uint32_t* cnt;
+    size_t ldc;
+    const uint64_t* qoff;
+    uint64_t* out_idx;
+    float* out_score;
+    uint64_t cap;
+};
+
+template <int QB, bool EMIT>
+static innr_status launch_range_scan_qb(innr_batch* b, int metric, const RangeScan& a) {
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kScanChunk;
+    // waves per CU as the exact kNN scan (knn_exact_range): 16 for eight queries a pass, 24 below
+    const unsigned bx = (unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * (QB == 8 ? 4 : 6));
+    const dim3 grid(bx, (a.nq + QB - 1) / QB);
+    log_launch(c, kLaunchRangeScan, QB, metric, EMIT ? 1 : 0, 0, grid.y);
+#define INNR_RANGE_LAUNCH(L2, COS)                                                                                              \
+    range_scan_kernel<QB, L2, COS, EMIT><<<grid, kScanThreads, 0, c->stream>>>(                                                 \
+        b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, a.Q, b->D, b->norms, a.qnorm, a.thr, a.qmap, a.nq, a.cnt, a.ldc, a.qoff, \
+        b->index_base, a.out_idx, a.out_score, a.cap)
+    if (metric == INNR_METRIC_COSINE) INNR_RANGE_LAUNCH(false, true);
+    else if (metric == INNR_METRIC_L2SQ) INNR_RANGE_LAUNCH(true, false);
+    else INNR_RANGE_LAUNCH(false, false);
+#undef INNR_RANGE_LAUNCH
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+// eight, four or one query per corpus pass, never more than there are queries (the kernel's last group ends on the last query)
+template <bool EMIT>
+static innr_status launch_range_scan(innr_batch* b, int metric, const RangeScan& a) {
+    if (a.nq >= 8) return launch_range_scan_qb<8, EMIT>(b, metric, a);
+    if (a.nq >= 4) return launch_range_scan_qb<4, EMIT>(b, metric, a);
+    return launch_range_scan_qb<1, EMIT>(b, metric, a);
+}
+
+static innr_status range_search_dev(innr_batch* b, int metric, const float* dQ, size_t Q, const float* dThr, int engine,
+                                    uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t cap, size_t* out_total,
+                                    innr_knn_stats* stats) {
+    innr_ctx* c = b->ctx;
+    const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
+    const size_t D = b->D, nchunks = b->ldN / kScanChunk, ldc = nchunks + 1, ldb = b->ldN / 32;
+    bool collect = engine != INNR_KNN_EXACT;  // (the bf16 / int8 requests: the f32 collect pass serves them)
+    if (engine == INNR_KNN_AUTO) collect = Q >= kRangeAutoQ0;
+    if (!gemm_addressable(b, std::min(Q, kRangeMaxRound)) || D == 0) collect = false;
+    uint32_t nfallback = 0, kept = 0;
+    float gemm_ms = 0.0f;
+    if (collect || cos) INNR_TRY(ensure_norms(b));
+    if (collect && !(b->max_norm >= 1e-12f && b->max_norm <= 1e18f)) {
+        // the corpus' largest norm outside the range the filter's error bound is good for (non-finite values included)
+        collect = false;
+        nfallback = (uint32_t)Q;
+    }
+    const size_t per_query = (ldc + 2) * sizeof(uint32_t) +
+                             (collect ? ldb * sizeof(uint32_t) + (size_t)kCollectCap * (sizeof(uint32_t) + sizeof(uint64_t)) : 0);
+    const size_t round = std::min(Q, std::max<size_t>(1, std::min(kRangeMaxRound, kRangeWorkspace / per_query)));
+    INNR_TRY(c->rs_cnt.ensure(round * ldc * sizeof(uint32_t)));
+    INNR_TRY(c->rs_tot.ensure(2 * round * sizeof(uint32_t)));
+    if (collect) INNR_TRY(c->rs_bits.ensure(round * ldb * sizeof(uint32_t)));
+    uint32_t* cnt = c->rs_cnt.as<uint32_t>();
+    uint32_t* tot = c->rs_tot.as<uint32_t>();
+    uint32_t* bad = tot + round;
+    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
+    INNR_HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), c->stream));  // the running base, carried in the offsets themselves
+    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+    for (size_t q0 = 0; q0 < Q; q0 += round) {
+        const size_t nq = std::min(round, Q - q0);
+        const float* Qp = dQ + q0 * D;
+        const float* thr = dThr + q0;
+        uint64_t* off = d_off + q0;
+        RangeScan a = {Qp, nullptr, thr, nullptr, (uint32_t)nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap};
+        const dim3 lg(kCollectCap / 256, (unsigned)nq);  // (blocks beyond a query's list length return at once)
+        if (collect) {
+            INNR_TRY(collect_pass(b, metric, Qp, nq, 1, thr));
+            bool rows = false;
+            INNR_TRY(collect_rescore(b, metric, Qp, c->q_norm.as<float>(), nq, &rows));
+            INNR_HIP_CHECK(hipMemsetAsync(c->rs_bits.p, 0, nq * ldb * sizeof(uint32_t), c->stream));
+            INNR_HIP_CHECK(hipMemsetAsync(cnt, 0, nq * ldc * sizeof(uint32_t), c->stream));
+            if (l2) range_mark_kernel<true><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr, c->seed_score.as<uint32_t>(), c->q_norm.as<float>(), c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
+            else range_mark_kernel<false><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr, c->seed_score.as<uint32_t>(), c->q_norm.as<float>(), c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
+            INNR_HIP_CHECK(hipGetLastError());
+            // which queries the exact scan finishes, and how long the lists got (one synchronisation per round)
+            std::vector<uint32_t> hb(2 * nq);
+            INNR_HIP_CHECK(hipMemcpyAsync(hb.data(), bad, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            INNR_HIP_CHECK(hipMemcpyAsync(hb.data() + nq, c->counts.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            INNR_HIP_CHECK(hipStreamSynchronize(c->stream));
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms += ms;
+            std::vector<uint32_t> redo;
+            for (size_t j = 0; j < nq; ++j) {
+                if (hb[j]) redo.push_back((uint32_t)j);
+                kept = std::max(kept, std::min(hb[nq + j], kCollectCap));
+            }
+            nfallback += (uint32_t)redo.size();
+            a.nq = (uint32_t)redo.size();
+            if (a.nq) {  // gathered: their rows (rb.q), thresholds (rb.qn) and exact norms (rb.sc); rb.map = the rows of cnt / off
+                innr_ctx::RedoBufs& rb = c->cmpl;
+                INNR_TRY(upload_redo(c, rb, redo, D, 1));
+                const uint32_t* map = rb.map.as<uint32_t>();
+                gather_rows_kernel<<<(unsigned)(((size_t)a.nq * D + 255) / 256), 256, 0, c->stream>>>(Qp, map, a.nq, (uint32_t)D, rb.q.as<float>());
+                gather_f32_kernel<<<(a.nq + 255) / 256, 256, 0, c->stream>>>(thr, map, a.nq, rb.qn.as<float>());
+                gather_f32_kernel<<<(a.nq + 255) / 256, 256, 0, c->stream>>>(c->q_norm.as<float>(), map, a.nq, rb.sc.as<float>());
+                INNR_HIP_CHECK(hipGetLastError());
+                a.Q = rb.q.as<float>();
+                a.thr = rb.qn.as<float>();
+                a.qnorm = rb.sc.as<float>();
+                a.qmap = map;
+            }
+        } else if (cos) {
+            INNR_TRY(c->q_norm.ensure(nq * sizeof(float)));
+            query_norms_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(Qp, (uint32_t)nq, (uint32_t)D, D, c->q_norm.as<float>());
+            INNR_HIP_CHECK(hipGetLastError());
+            a.qnorm = c->q_norm.as<float>();
+        }
+        if (a.nq) INNR_TRY(launch_range_scan<false>(b, metric, a));
+        range_chunk_scan_kernel<<<(unsigned)nq, 1024, 0, c->stream>>>(cnt, ldc, (uint32_t)nchunks, tot);
+        range_offsets_kernel<<<1, 1024, 0, c->stream>>>(tot, (uint32_t)nq, off);
+        INNR_HIP_CHECK(hipGetLastError());
+        if (cap == 0) continue;  // a count-only call
+        if (a.nq) INNR_TRY(launch_range_scan<true>(b, metric, a));
+        if (collect) {
+            range_scatter_kernel<<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, l2,
+                                                            c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx, d_sc,
+                                                            (uint64_t)cap);
+            INNR_HIP_CHECK(hipGetLastError());
+        }
+    }
+    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
+    uint64_t total = 0;
+    INNR_HIP_CHECK(copy_out(c, &total, d_off + Q, sizeof(total)));
+    INNR_TRY(check_errflag(c));  // (synchronises)
+    *out_total = (size_t)total;
+    if (stats) {
+        float ms = 0.0f;
+        if (!collect && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms = ms;
+        stats->engine = collect ? INNR_KNN_MFMA : INNR_KNN_EXACT;
+        stats->queries_fallback = nfallback;
+        stats->candidates_kept = kept;
+        stats->gemm_ms = gemm_ms;
+        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
+    }
+    return INNR_OK;
+}
+
+// the argument checks both entry points share; *empty: nothing to search, the offsets are all zero
+static innr_status range_search_args(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const float* thresholds,
+                                     uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
+                                     innr_knn_stats* stats, bool* empty) {
+    if (b && !b->V) {
+        set_error("this entry point needs an f32 batch (got a u8 code batch)");
+        return INNR_E_BAD_ARG;
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!b || !metric_ok(metric) || !out_total) {
+        set_error("bad batch/metric/out_total");
+        return INNR_E_BAD_ARG;
+    }
+    if (D != b->D) {  // batch.rs:325
+        set_error("dimension mismatch: query.len()=%zu, batch.dimension=%zu", D, b->D);
+        return INNR_E_DIM_MISMATCH;
+    }
+    *out_total = 0;
+    if (!out_offsets || Q >= 0xFFFFFFFFull) {
+        set_error("out_offsets is null, or more than 2^32 - 2 queries");
+        return INNR_E_BAD_ARG;
+    }
+    *empty = b->N == 0 || Q == 0;
+    if (*empty) return INNR_OK;
+    if (!thresholds || (!queries && D) || (cap && (!out_idx || !out_score))) {
+        set_error("thresholds / queries / output buffers are null");
+        return INNR_E_BAD_ARG;
+    }
+    return INNR_OK;
+}
+
+}  // namespace innr
+
+extern "C" {
+
+innr_status innr_batch_range_search_dev(innr_batch* b, int metric, const float* d_queries, size_t Q, size_t D, const float* d_thresholds,
+                                        int engine, uint64_t* d_out_offsets, uint64_t* d_out_idx, float* d_out_score, size_t cap,
+                                        size_t* out_total, innr_knn_stats* stats) {
+    bool empty = false;
+    INNR_TRY(range_search_args(b, metric, d_queries, Q, D, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats, &empty));
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    if (empty) {
+        INNR_HIP_CHECK(hipMemsetAsync(d_out_offsets, 0, (Q + 1) * sizeof(uint64_t), c->stream));
+        INNR_HIP_CHECK(ctx_sync(c));
+        return INNR_OK;
+    }
+    return range_search_dev(b, metric, d_queries, Q, d_thresholds, engine, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+}
+
+innr_status innr_batch_range_search(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
+                                    uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
+                                    innr_knn_stats* stats) {
+    bool empty = false;
+    INNR_TRY(range_search_args(b, metric, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total, stats, &empty));
+    if (empty) {
+        memset(out_offsets, 0, (Q + 1) * sizeof(uint64_t));
+        return INNR_OK;
+    }
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    // Staged on the device: queries, thresholds, offsets, and room for min(cap, Q * N) results. Where that room is large (beyond
+    // kRangeStageDirect bytes) a count-only pass comes first and the room shrinks to what the result needs: a generous cap costs a
+    // second search, not memory for results that do not exist.
+    size_t room = std::min(cap, Q * b->N);
+    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
+    INNR_TRY(c->rs_thr.ensure(Q * sizeof(float)));
+    INNR_TRY(c->rs_off.ensure((Q + 1) * sizeof(uint64_t)));
+    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
+    INNR_HIP_CHECK(copy_in(c, c->rs_thr.p, thresholds, Q * sizeof(float)));
+    if (room * (sizeof(uint64_t) + sizeof(float)) > kRangeStageDirect) {
+        INNR_TRY(range_search_dev(b, metric, c->q_row.as<float>(), Q, c->rs_thr.as<float>(), engine, c->rs_off.as<uint64_t>(), nullptr,
+                                  nullptr, 0, out_total, stats));
+        room = std::min(room, *out_total);
+    }
+    INNR_TRY(c->out_idx.ensure(std::max<size_t>(room, 1) * sizeof(uint64_t)));
+    INNR_TRY(c->out_score.ensure(std::max<size_t>(room, 1) * sizeof(float)));
+    INNR_TRY(range_search_dev(b, metric, c->q_row.as<float>(), Q, c->rs_thr.as<float>(), engine, c->rs_off.as<uint64_t>(),
+                              c->out_idx.as<uint64_t>(), c->out_score.as<float>(), room, out_total, stats));
+    INNR_HIP_CHECK(copy_out(c, out_offsets, c->rs_off.p, (Q + 1) * sizeof(uint64_t)));
+    const size_t m = std::min<size_t>(*out_total, room);
+    if (m) {
+        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, m * sizeof(uint64_t)));
+        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, m * sizeof(float)));
+    }
+    INNR_HIP_CHECK(ctx_sync(c));
     return INNR_OK;
 }
 

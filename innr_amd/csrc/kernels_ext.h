@@ -108,4 +108,108 @@ __global__ __launch_bounds__(256) void prune_scatter_kernel(const float* __restr
     }
 }
 
+// ---- range search (innr_batch_range_search): the scans, and the finish of the queries a collect pass served -----------------
+// Per query (one workgroup each), in place: cnt[q][0..n) survivors per chunk -> their exclusive prefix, cnt[q][n] = tot[q] = the
+// query's total. 32-bit: a query has at most N < 2^32 survivors.
+__global__ __launch_bounds__(1024) void range_chunk_scan_kernel(uint32_t* __restrict__ cnt, size_t ldc, uint32_t n,
+                                                                 uint32_t* __restrict__ tot) {
+    __shared__ uint32_t part[1024];
+    uint32_t* row = cnt + (size_t)blockIdx.x * ldc;
+    const uint32_t per = (n + 1023) / 1024;
+    const uint32_t b = threadIdx.x * per < n ? threadIdx.x * per : n, e = (b + per < n) ? b + per : n;
+    uint32_t s = 0;
+    for (uint32_t i = b; i < e; ++i) s += row[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan of the partials
+        const uint32_t v = (threadIdx.x >= off) ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t run = (threadIdx.x == 0) ? 0 : part[threadIdx.x - 1];
+    for (uint32_t i = b; i < e; ++i) {
+        const uint32_t c = row[i];
+        row[i] = run;
+        run += c;
+    }
+    if (threadIdx.x == 1023) {
+        row[n] = part[1023];
+        tot[blockIdx.x] = part[1023];
+    }
+}
+
+// The 64-bit scan over the totals of one chunk of nq <= 4096 queries (single workgroup): off[0] is the running base the chunk
+// before left (the first chunk's: 0), off[j + 1] = off[0] + tot[0] + ... + tot[j], so off[nq] carries the base on.
+__global__ __launch_bounds__(1024) void range_offsets_kernel(const uint32_t* __restrict__ tot, uint32_t nq, uint64_t* __restrict__ off) {
+    __shared__ uint64_t part[1024];
+    const uint32_t per = (nq + 1023) / 1024;
+    const uint32_t b = threadIdx.x * per < nq ? threadIdx.x * per : nq, e = (b + per < nq) ? b + per : nq;
+    uint64_t s = 0;
+    for (uint32_t i = b; i < e; ++i) s += tot[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024; o <<= 1) {
+        const uint64_t v = (threadIdx.x >= o) ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint64_t run = off[0] + ((threadIdx.x == 0) ? 0 : part[threadIdx.x - 1]);
+    for (uint32_t i = b; i < e; ++i) {
+        run += tot[i];
+        off[i + 1] = run;
+    }
+}
+
+// A collect pass (MODE 2 of the GEMM filter, thresholds from seed_thresholds_kernel) left query q's candidates in its list and
+// their exact composites in keys[q][0..ccnt[q]). The list holds every survivor only if it did not overflow and the filter's error
+// bound held for the query: bad[q] = 1 otherwise (list past `cap`; no finite collect threshold, seed[q] == 0; a query norm outside
+// {0} + [1e-12, 1e18], where the approximate scores may overflow or lose products to flushing) and the exact scan finishes it.
+// For the others the exact predicate marks each survivor in the query's bitmap over the corpus (bit i % 32 of word i / 32) and
+// counts it in its 256-vector chunk. A corpus index occurs once per list, and OR / ADD do not depend on the order of arrival.
+template <bool L2>
+__global__ __launch_bounds__(256) void range_mark_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ccnt, uint32_t cap,
+                                                          const float* __restrict__ thr, const uint32_t* __restrict__ seed,
+                                                          const float* __restrict__ qnorm, uint32_t* __restrict__ bitmap, size_t ldb,
+                                                          uint32_t* __restrict__ cnt, size_t ldc, uint32_t* __restrict__ bad) {
+    const uint32_t q = blockIdx.y;
+    const uint32_t n = ccnt[q];
+    const float qn = qnorm[q];
+    const bool fb = n > cap || seed[q] == 0u || !(qn == 0.0f || (qn >= 1e-12f && qn <= 1e18f));
+    if (blockIdx.x == 0 && threadIdx.x == 0) bad[q] = fb ? 1u : 0u;
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (fb || slot >= n) return;
+    const uint64_t key = keys[(size_t)q * cap + slot];
+    const float s = pref_score(cand_pref(key), L2), t = thr[q];
+    if (L2 ? (s > t) : (s < t)) return;
+    const uint32_t i = cand_idx(key), bit = 1u << (i & 31);
+    const uint32_t old = atomicOr(bitmap + (size_t)q * ldb + (i >> 5), bit);
+    if (!(old & bit)) atomicAdd(cnt + (size_t)q * ldc + (i >> 8), 1u);
+}
+
+// ... and after the scans each marked candidate goes to its place in index order: the query's offset, its chunk's prefix, the
+// marked vectors of the chunk below it (popcounts of the bitmap). Only positions < outcap are written.
+__global__ __launch_bounds__(256) void range_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ccnt, uint32_t cap,
+                                                             bool l2, const uint32_t* __restrict__ bitmap, size_t ldb,
+                                                             const uint32_t* __restrict__ pref, size_t ldc, const uint32_t* __restrict__ bad,
+                                                             const uint64_t* __restrict__ qoff, uint64_t index_base,
+                                                             uint64_t* __restrict__ out_idx, float* __restrict__ out_score, uint64_t outcap) {
+    const uint32_t q = blockIdx.y;
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (bad[q] || slot >= ccnt[q]) return;
+    const uint64_t key = keys[(size_t)q * cap + slot];
+    const uint32_t i = cand_idx(key), bit = 1u << (i & 31);
+    const uint32_t* words = bitmap + (size_t)q * ldb + ((i >> 8) << 3);  // the chunk's eight words
+    const uint32_t w = (i >> 5) & 7;
+    if (!(words[w] & bit)) return;
+    uint32_t rank = (uint32_t)__popc(words[w] & (bit - 1u));
+    for (uint32_t u = 0; u < w; ++u) rank += (uint32_t)__popc(words[u]);
+    const uint64_t pos = qoff[q] + pref[(size_t)q * ldc + (i >> 8)] + rank;
+    if (pos < outcap) {
+        out_idx[pos] = index_base + i;
+        out_score[pos] = pref_score(cand_pref(key), l2);
+    }
+}
+
 }  // namespace innr

@@ -205,4 +205,85 @@ __global__ __launch_bounds__(kScanThreads) void scan_filter_kernel(
     }
 }
 
+// ---- range search: every vector within a per-query threshold, in index order (innr_batch_range_search) ---------------
+// The predicate of batch_l2_squared_pruning (batch.rs:351) per query: squared L2 keeps !(dist > thr), dot / cosine keep
+// !(score < thr), so a NaN score survives either way. Two launches of the same arithmetic around a scan of the counts:
+//   EMIT = false: cnt[row][ch] = survivors of query `row` in the 256-vector chunk ch (every chunk is written);
+//   EMIT = true : cnt holds each row's exclusive prefix over the chunks, the row's total at [nchunks]. A chunk where no query
+//     of the group has a survivor is skipped before its corpus rows are read (wave-uniform test), the others are scored again
+//     and survivor i lands at qoff[row] + cnt[row][ch] + (survivors of the chunk below i); only positions < cap are written.
+// Query groups of QB on blockIdx.y. The last group of a ragged batch is moved back to end on the last query (nq >= QB): the
+// queries it shares with the group before are scored twice and written by the earlier group only, so no row is read past nq.
+// qmap: cnt / qoff row of local query q (null: q itself) -- the queries of a batch that the exact path finishes.
+template <int QB, bool L2, bool COS, bool EMIT>
+__global__ __launch_bounds__(kScanThreads) void range_scan_kernel(
+    const float* __restrict__ V, size_t ldN, uint32_t N, uint32_t D, const float* __restrict__ Qm, size_t ldq,
+    const float* __restrict__ norms, const float* __restrict__ qnorm, const float* __restrict__ thr,
+    const uint32_t* __restrict__ qmap, uint32_t nq, uint32_t* __restrict__ cnt, size_t ldc,
+    const uint64_t* __restrict__ qoff, uint64_t index_base, uint64_t* __restrict__ out_idx, float* __restrict__ out_score,
+    uint64_t cap) {
+    const uint32_t g0 = blockIdx.y * QB;                      // first query this group writes
+    const uint32_t qb0 = g0 + QB <= nq ? g0 : nq - QB;        // first query it scores
+    Qm += (size_t)qb0 * ldq;
+    uint32_t row[QB];
+#pragma unroll
+    for (int j = 0; j < QB; ++j) row[j] = qmap ? qmap[qb0 + j] : qb0 + j;
+    const size_t nchunks = ldN / kScanChunk;
+    const size_t wave = ((size_t)blockIdx.x * kScanThreads + threadIdx.x) >> 6;
+    const size_t nwaves = ((size_t)gridDim.x * kScanThreads) >> 6;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (size_t ch = wave; ch < nchunks; ch += nwaves) {
+        if (EMIT) {
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < QB; ++j)
+                if (qb0 + j >= g0) any |= cnt[row[j] * ldc + ch + 1] != cnt[row[j] * ldc + ch];
+            if (!any) continue;
+        }
+        const size_t col = ch * kScanChunk + (size_t)lane * 4;
+        float acc[QB][4];
+        scan_accumulate<QB, L2>(V, ldN, D, col, Qm, ldq, acc);
+        float vn[4] = {0, 0, 0, 0};
+        if (COS) {
+            const float4 t = *reinterpret_cast<const float4*>(norms + col);
+            vn[0] = t.x; vn[1] = t.y; vn[2] = t.z; vn[3] = t.w;
+        }
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
+            if (qb0 + j < g0) continue;  // scored for the group before (wave-uniform)
+            const float t = thr[qb0 + j];
+            const float qn = COS ? qnorm[qb0 + j] : 0.0f;
+            float s[4];
+            bool keep[4];
+            unsigned long long m[4];
+            uint32_t total = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                s[c] = COS ? cosine_epilogue(acc[j][c], qn, vn[c]) : acc[j][c];
+                keep[c] = col + c < N && (L2 ? !(s[c] > t) : !(s[c] < t));
+                m[c] = __ballot(keep[c]);
+                total += (uint32_t)__popcll(m[c]);
+            }
+            if (!EMIT) {
+                if (lane == 0) cnt[row[j] * ldc + ch] = total;
+            } else if (total) {
+                uint64_t pos = qoff[row[j]] + cnt[row[j] * ldc + ch];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) pos += (uint32_t)__popcll(m[c] & below);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (keep[c]) {
+                        if (pos < cap) {
+                            out_idx[pos] = index_base + col + c;
+                            out_score[pos] = s[c];
+                        }
+                        ++pos;
+                    }
+                }
+            }
+        }
+    }
+}
+
 }  // namespace innr

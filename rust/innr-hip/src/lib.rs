@@ -94,6 +94,8 @@ pub mod ffi {
         pub fn innr_batch_knn_filtered_multi_dev(b: *mut InnrBatch, metric: c_int, d_queries: *const f32, q: usize, d: usize, k: usize, d_mask: *const u8, engine: c_int, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_knn_reordered(b: *mut InnrBatch, q: *const f32, d: usize, k: usize, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize) -> c_int;
         pub fn innr_batch_l2_squared_pruning(b: *mut InnrBatch, q: *const f32, d: usize, threshold: f32, out_idx: *mut u64, out_dist: *mut f32, cap: usize, out_n: *mut usize) -> c_int;
+        pub fn innr_batch_range_search(b: *mut InnrBatch, metric: c_int, queries: *const f32, q: usize, d: usize, thresholds: *const f32, engine: c_int, out_offsets: *mut u64, out_idx: *mut u64, out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_range_search_dev(b: *mut InnrBatch, metric: c_int, d_queries: *const f32, q: usize, d: usize, d_thresholds: *const f32, engine: c_int, d_out_offsets: *mut u64, d_out_idx: *mut u64, d_out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_dot_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_cosine_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_l2sq_f32(a: *const f32, b: *const f32, n: usize) -> f32;
@@ -383,6 +385,30 @@ pub mod batch {
         check(unsafe { ffi::innr_batch_l2_squared_pruning(batch.handle(), query.as_ptr(), query.len(), threshold,
                                                           idx.as_mut_ptr(), d.as_mut_ptr(), cap, &mut n) });
         (0..n.min(cap)).map(|i| (idx[i] as usize, d[i])).collect()
+    }
+
+    /// Range search (an addition; include/innr_hip.h: innr_batch_range_search): batch.rs:320-365 for Q row-major queries at once,
+    /// each with its own threshold, any metric and engine (ffi::INNR_KNN_*). Query j keeps every vector with
+    /// !(distance > thresholds[j]) (squared L2) or !(score < thresholds[j]) (dot, cosine), as (index, score) in index order.
+    /// One counting call, then one call with room for everything.
+    #[must_use] pub fn batch_range_search(engine: i32, metric: i32, queries: &[f32], dimension: usize, batch: &VerticalBatch,
+                                          thresholds: &[f32]) -> Vec<Vec<(usize, f32)>> {
+        assert_eq!(dimension, batch.dimension);
+        let q = thresholds.len();
+        assert_eq!(queries.len(), q * dimension);
+        let mut off = vec![0u64; q + 1];
+        let mut total = 0usize;
+        check(unsafe { ffi::innr_batch_range_search(batch.handle(), metric, queries.as_ptr(), q, dimension, thresholds.as_ptr(), engine,
+                                                    off.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total,
+                                                    std::ptr::null_mut()) });
+        let cap = total;
+        let (mut idx, mut sc) = (vec![0u64; cap.max(1)], vec![0f32; cap.max(1)]);
+        if cap > 0 {
+            check(unsafe { ffi::innr_batch_range_search(batch.handle(), metric, queries.as_ptr(), q, dimension, thresholds.as_ptr(), engine,
+                                                        off.as_mut_ptr(), idx.as_mut_ptr(), sc.as_mut_ptr(), cap, &mut total,
+                                                        std::ptr::null_mut()) });
+        }
+        (0..q).map(|j| (off[j] as usize..off[j + 1] as usize).map(|i| (idx[i] as usize, sc[i])).collect()).collect()
     }
 }
 
