@@ -109,7 +109,8 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * gemm_waves, gemm_blocks_per_cu, gemm_qt_group, gemm_seed_n, gemm_no_seed, gemm_no_kp_retry, i8_two_limb, no_auto_bf16,
  * no_auto_i8, u8_no_i8, rescore_all, maxsim_generic, no_k_rule, no_completion, no_rows_copy, i8_slices_per_cu, i8_no_small, i8_no_small4, i8_small_max_q, i8_small_free, trace, fail_local_search (a test
  * switch of the sharded calls), filter_keep_selection (default 1; 0: innr_batch_knn_filtered_multi frees its selection at the end
- * of every call) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
+ * of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
+ * innr_batch_set_copy_budget) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
 const char* innr_last_error(void);
@@ -368,6 +369,82 @@ innr_status innr_batch_rerank_dev(innr_batch* b, int metric, const float* d_quer
  * with the queries' first prefix_dims values (row stride = prefix_dims), the fine stage innr_batch_rerank on the
  * parent. The parent must outlive the view; free the view with innr_batch_free. prefix_dims == 0 is INNR_E_BAD_ARG. */
 innr_status innr_batch_prefix_view(innr_batch* parent, size_t prefix_dims, innr_batch** out);
+
+/* ---- device memory: report, release, prebuild and bound what a batch derives from its corpus (an addition) ------------
+ * The reference's quantised store reports memory_bytes() (scalar.rs:205-208); here a batch owns more than its store. Beside the
+ * corpus it keeps DERIVED allocations, each built by the first call that wants it and kept for the batch's lifetime; one bit
+ * names each kind (DESIGN.md 3 has the table: which call builds it, under which policy, its size):
+ *   INNR_COPY_ROWS          the row-major copy (N * round_up(D, 4) * 4 bytes): many candidates per query re-scored exactly
+ *   INNR_COPY_BF16_*        the K-packed bf16 filter copies of INNR_KNN_MFMA_BF16, one per metric
+ *   INNR_COPY_BF16LO_*      the lo limbs of the dot / cosine copy: with the BF16 copy of that metric, INNR_KNN_MFMA's split filter
+ *   INNR_COPY_I8_*          the K-packed int8 filter copies of INNR_KNN_MFMA_I8 (a u8 code batch has the DOT kind only)
+ *   INNR_COPY_SELECTION     the kept selection of innr_batch_knn_filtered_multi: its compact store, mask and map, and every
+ *                           copy the selection batch built for itself (its cached norms, 12 bytes per vector at most, are not
+ *                           counted)
+ * A prefix view is a batch of its own here: it shares the parent's store (corpus_bytes = 0), owns its copies and has its OWN
+ * budget -- the context option's value when the view is created, not its parent's. A view's copies are not reported by, and do
+ * not count against the budget of, the parent: a caller that bounds a batch with innr_batch_set_copy_budget and searches views
+ * of it (the coarse stage of a matryoshka search) sets each view's budget too, or the views' copies come on top. */
+#define INNR_COPY_ROWS (1u << 0)
+#define INNR_COPY_BF16_DOT (1u << 1)
+#define INNR_COPY_BF16_COS (1u << 2)
+#define INNR_COPY_BF16_L2 (1u << 3)
+#define INNR_COPY_BF16LO_DOT (1u << 4)
+#define INNR_COPY_BF16LO_COS (1u << 5)
+#define INNR_COPY_I8_DOT (1u << 6)
+#define INNR_COPY_I8_COS (1u << 7)
+#define INNR_COPY_I8_L2 (1u << 8)
+#define INNR_COPY_SELECTION (1u << 9)
+#define INNR_COPY_ALL 0x3FFu
+/* What the batch holds on the device NOW, in bytes exactly as they were asked of hipMalloc: *corpus_bytes the store it owns (0 for
+ * a prefix view), *aux_bytes its cached norms and their by-products, *derived_bytes the sum over everything INNR_COPY_ALL names,
+ * *present_mask the kinds that exist. Any out pointer may be null. A null batch is INNR_E_BAD_ARG; the call touches no device
+ * state (host bookkeeping, read under the context's lock).
+ * Out of scope: the context's workspace (innr_ctx_memory), memory of other batches or of a view's parent, anything sharded. */
+innr_status innr_batch_memory(const innr_batch* b, uint64_t* corpus_bytes, uint64_t* aux_bytes, uint64_t* derived_bytes,
+                              uint32_t* present_mask);
+/* the sum over the kinds in `mask` (bits outside INNR_COPY_ALL are ignored); innr_batch_copy_bytes(b, INNR_COPY_ALL) is
+ * innr_batch_memory's *derived_bytes. Null batch or null `bytes`: INNR_E_BAD_ARG. */
+innr_status innr_batch_copy_bytes(const innr_batch* b, uint32_t mask, uint64_t* bytes);
+/* Free the kinds in `mask` (after synchronising the context's stream) and forget that any of them was ever refused for lack of
+ * memory -- a refusal under the "fits with room to spare" rule is otherwise remembered for the batch's lifetime, so this is also how
+ * a caller says "try again". Releasing a BF16 kind releases its BF16LO partner too (the split filter needs the pair). The next
+ * call that wants a released copy builds it again under the rules of that moment; results never change. Kinds that do not exist
+ * are skipped.
+ * Out of scope: automatic eviction under memory pressure, re-trying a refused copy every Nth call by itself, the batch's store
+ * and norms, a view's parent, sharded corpora (release on each rank's shard). */
+innr_status innr_batch_release_copies(innr_batch* b, uint32_t mask);
+/* Build the kinds in `mask` now instead of inside the first query that wants them (seconds at 30 GB), through the builders the
+ * engines use. The "fits with room to spare" rule does not apply -- the caller asked: a failed hipMalloc is INNR_E_OOM. Skipped,
+ * without an error: a kind that cannot exist for this batch (bf16 kinds and rows on a u8 code batch, int8 kinds other than DOT
+ * there, an int8 kind whose corpus has nothing to quantise against, every matrix-pipe copy of a view whose length has no
+ * matrix-pipe engine, of an empty batch), a kind the copy budget does not admit, and INNR_COPY_SELECTION (there is no mask to
+ * select with). *built_mask (may be null) = the kinds of `mask` present at return, already existing ones included.
+ * Out of scope: building in the background, choosing kinds from the call history (innr_batch_auto_engine stays a pure function
+ * of the batch and Q), sharded corpora. */
+innr_status innr_batch_build_copies(innr_batch* b, uint32_t mask, uint32_t* built_mask);
+/* The copy budget of a batch: a derived allocation is made only if derived_bytes + its size <= budget (UINT64_MAX = unlimited,
+ * the default, unless the context option copy_budget_mib -- INNR_COPY_BUDGET_MIB, -1 = unlimited -- said otherwise when the batch
+ * was created; batches that exist keep theirs). What a refused allocation means is what it meant already: an explicit
+ * INNR_KNN_MFMA_BF16 / _I8 request and INNR_KNN_AUTO are served by INNR_KNN_MFMA (stats->engine tells), the split filter by the
+ * f32-pipe filter, the rows copy by column gathers, the selection by the masked exact scan. A budget refusal is evaluated per
+ * call and never remembered: raise the budget and the next call builds. The selection's own copies count against its parent's
+ * budget. Lowering the budget below the current use frees nothing -- existing copies keep being used; the caller decides what to
+ * release. The squared-L2 int8 copy is admitted by its upper bound (D + 121 dimensions).
+ * Out of scope: automatic eviction, budgets for document corpora or the context's workspace, moving the free-memory query
+ * out of INNR_KNN_AUTO, one budget across several batches or ranks. */
+innr_status innr_batch_set_copy_budget(innr_batch* b, uint64_t bytes);
+innr_status innr_batch_get_copy_budget(const innr_batch* b, uint64_t* bytes);
+/* the same report for a document corpus: *corpus_bytes = tokens + doc_len, *derived_bytes = the token norms the MFMA engine
+ * builds on first use. Out pointers may be null; a null corpus is INNR_E_BAD_ARG. Out of scope: release, budget. */
+innr_status innr_docs_memory(const innr_docs* d, uint64_t* corpus_bytes, uint64_t* derived_bytes);
+/* *workspace_bytes = the device workspace of the context (grow-only buffers shared by every call on it). */
+innr_status innr_ctx_memory(innr_ctx* ctx, uint64_t* workspace_bytes);
+/* Give the workspace back (after synchronising the stream): every buffer a call sizes for itself is freed and grows again on
+ * demand; the 4 KiB flag block, which is set up once in innr_ctx_create, stays, and so do the pinned staging area, the stream
+ * and the events. Results never change; the next calls pay their hipMallocs again.
+ * Out of scope: trimming to a target size, trimming by itself. */
+innr_status innr_ctx_trim(innr_ctx* ctx);
 
 /* ---- multi-GPU merge (range partition + all-gather of per-shard top-k) --------- */
 /* in: G shards x Q queries x kin candidates (device pointers, layout [g][q][kin], global indices);

@@ -13,7 +13,7 @@ import os
 import sys
 import threading
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INNR_HIP_LIB_PATH") or os.path.join(_HERE, "lib", "libinnr_hip.so")  # (the override: A/B builds of tools/)
@@ -41,6 +41,20 @@ MAX_K = 240
 GEN_EXAMPLE_LCG = 0
 GEN_UNIFORM = 1
 
+# the derived allocations of a batch, one bit each (include/innr_hip.h: INNR_COPY_*; tests/test_memory_abi.py compares the values)
+COPY_ROWS = 1 << 0
+COPY_BF16_DOT = 1 << 1
+COPY_BF16_COS = 1 << 2
+COPY_BF16_L2 = 1 << 3
+COPY_BF16LO_DOT = 1 << 4
+COPY_BF16LO_COS = 1 << 5
+COPY_I8_DOT = 1 << 6
+COPY_I8_COS = 1 << 7
+COPY_I8_L2 = 1 << 8
+COPY_SELECTION = 1 << 9
+COPY_ALL = 0x3FF
+COPY_BUDGET_UNLIMITED = 2 ** 64 - 1  # UINT64_MAX
+
 
 class InnrError(RuntimeError):
     """A failure reported by the HIP library (status < 0 other than a dimension mismatch)."""
@@ -61,6 +75,7 @@ class KnnStats(C.Structure):
 
 _f32p = C.POINTER(C.c_float)
 _u64p = C.POINTER(C.c_uint64)
+_u32p = C.POINTER(C.c_uint32)
 _szp = C.POINTER(C.c_size_t)
 _vp = C.c_void_p
 _sz = C.c_size_t
@@ -149,6 +164,15 @@ SIGNATURES = {
     "innr_sharded_knn_dev": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
     "innr_sharded_knn": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
     "innr_sharded_maxsim": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_memory": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u32p]),
+    "innr_batch_copy_bytes": (C.c_int, [_vp, C.c_uint32, _u64p]),
+    "innr_batch_release_copies": (C.c_int, [_vp, C.c_uint32]),
+    "innr_batch_build_copies": (C.c_int, [_vp, C.c_uint32, _u32p]),
+    "innr_batch_set_copy_budget": (C.c_int, [_vp, C.c_uint64]),
+    "innr_batch_get_copy_budget": (C.c_int, [_vp, _u64p]),
+    "innr_docs_memory": (C.c_int, [_vp, _u64p, _u64p]),
+    "innr_ctx_memory": (C.c_int, [_vp, _u64p]),
+    "innr_ctx_trim": (C.c_int, [_vp]),
 }
 COMM_ID_BYTES = 128
 
@@ -226,6 +250,58 @@ def check(status: int) -> None:
     raise InnrError(status, msg)
 
 
+class BatchMemory(NamedTuple):
+    """innr_batch_memory: device bytes of a batch, exactly as allocated."""
+    corpus_bytes: int   # the store the batch owns (0 for a prefix view)
+    aux_bytes: int      # cached norms and their by-products
+    derived_bytes: int  # the sum over everything COPY_ALL names
+    present_mask: int   # COPY_* bits of the kinds that exist now
+
+
+class DocsMemory(NamedTuple):
+    """innr_docs_memory."""
+    corpus_bytes: int   # tokens + doc_len
+    derived_bytes: int  # the token norms of the MFMA engine
+
+
+class BatchMemoryMixin:
+    """Report, release, prebuild and bound the derived device memory of a batch handle `self._h` (include/innr_hip.h, "device
+    memory"): shared by batch.VerticalBatch and scalar.QuantizedCorpus. None of it changes a result."""
+
+    def memory(self) -> BatchMemory:
+        c, a, d, m = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        check(load().innr_batch_memory(self._h, C.byref(c), C.byref(a), C.byref(d), C.byref(m)))
+        return BatchMemory(int(c.value), int(a.value), int(d.value), int(m.value))
+
+    def copy_bytes(self, mask: int = COPY_ALL) -> int:
+        """Bytes of the derived kinds in `mask` (COPY_* bits)."""
+        v = C.c_uint64(0)
+        check(load().innr_batch_copy_bytes(self._h, int(mask), C.byref(v)))
+        return int(v.value)
+
+    def release_copies(self, mask: int = COPY_ALL) -> None:
+        """Free the kinds in `mask`; the next call that wants one builds it again."""
+        check(load().innr_batch_release_copies(self._h, int(mask)))
+
+    def build_copies(self, mask: int = COPY_ALL) -> int:
+        """Build the kinds in `mask` now; returns the mask of those present afterwards (kinds that cannot exist for this batch
+        or that the copy budget does not admit are skipped)."""
+        m = C.c_uint32(0)
+        check(load().innr_batch_build_copies(self._h, int(mask), C.byref(m)))
+        return int(m.value)
+
+    @property
+    def copy_budget(self) -> int:
+        """Most bytes the derived allocations may add up to (COPY_BUDGET_UNLIMITED = no limit)."""
+        v = C.c_uint64(0)
+        check(load().innr_batch_get_copy_budget(self._h, C.byref(v)))
+        return int(v.value)
+
+    @copy_budget.setter
+    def copy_budget(self, nbytes: Optional[int]) -> None:
+        check(load().innr_batch_set_copy_budget(self._h, C.c_uint64(COPY_BUDGET_UNLIMITED if nbytes is None else int(nbytes))))
+
+
 class Context:
     """One GPU (innr_ctx). One per process in the multi-GPU layout (one process per GPU)."""
 
@@ -272,6 +348,16 @@ class Context:
             yield
         finally:
             self.set_option(name, old)
+
+    def memory(self) -> int:
+        """Bytes of this context's device workspace (innr_ctx_memory)."""
+        v = C.c_uint64(0)
+        check(load().innr_ctx_memory(self.handle, C.byref(v)))
+        return int(v.value)
+
+    def trim(self) -> None:
+        """Give the workspace back; it grows again on demand (innr_ctx_trim)."""
+        check(load().innr_ctx_trim(self.handle))
 
     def close(self) -> None:
         """Free every batch created on this context, then the context (a batch must not outlive its ctx)."""

@@ -35,7 +35,7 @@ def _vp(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class VerticalBatch:
+class VerticalBatch(_lib.BatchMemoryMixin):
     """Vertical (columnar, PDX) storage: data[d * num_vectors + i] (batch.rs:88-95), resident on the GPU."""
 
     def __init__(self, handle: C.c_void_p, num_vectors: int, dimension: int, ctx: _lib.Context):

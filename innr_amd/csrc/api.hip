@@ -100,6 +100,7 @@ struct innr_tuning {
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi: keep the selection of the last mask for the next call (0: free it at the end of each call)
+    long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
 };
 struct TuneName { const char* name; long innr_tuning::*field; };
 static const TuneName kTuneNames[] = {
@@ -114,6 +115,7 @@ static const TuneName kTuneNames[] = {
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
     {"split_min_q", &innr_tuning::split_min_q}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
+    {"copy_budget_mib", &innr_tuning::copy_budget_mib},
 };
 static void tuning_from_env(innr_tuning* t) {
     for (const TuneName& n : kTuneNames) {
@@ -173,7 +175,7 @@ struct innr_ctx {
         size_t bytes;
     };
     std::vector<PendingOut> pending;
-    // workspace
+    // workspace (a DevBuf added here goes into workspace_bufs() below as well: destroy, innr_ctx_memory and innr_ctx_trim walk that list)
     DevBuf q_row;     // queries row-major [Q][ldq]
     DevBuf q_kmajor;  // queries K-major [Dpad][Qpad] for the GEMM engine
     DevBuf q_norm;    // [Q] exact query norms
@@ -216,6 +218,19 @@ struct innr_ctx {
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (log_launch; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
 };
+
+// Every workspace DevBuf of a context (innr_ctx_destroy, innr_ctx_memory, innr_ctx_trim). All but `flags` are sized by the calls
+// that use them (an ensure() in front of every use) and carry nothing from one call to the next; `flags` is allocated and zeroed
+// once, in innr_ctx_create, and the kernels' error words live there between the calls' own memsets: innr_ctx_trim keeps it.
+static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
+    return {&c->gthr, &c->sel_tmp[0], &c->sel_tmp[1], &c->selcnt_tmp[0], &c->selcnt_tmp[1],
+            &c->q_row, &c->q_kmajor, &c->q_norm, &c->lists, &c->counts, &c->sel, &c->sel_cnt,
+            &c->scores, &c->tmp_norms, &c->flags, &c->out_idx, &c->out_score, &c->misc, &c->seed_idx, &c->seed_score, &c->q_one, &c->sort_keys, &c->sort_tmp, &c->q_bf16, &c->q_pad, &c->q_hat,
+            &c->redo[0].q, &c->redo[0].idx, &c->redo[0].sc, &c->redo[0].map, &c->redo[0].qn,
+            &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
+            &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan,
+            &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off};
+}
 
 // record one templated launch (the caller holds the context's lock, as every dispatch site does): a few host stores
 static inline void log_launch(innr_ctx* c, int family, int a0, int a1 = 0, int a2 = 0, int a3 = 0, uint32_t groups = 1,
@@ -285,6 +300,7 @@ struct innr_batch {
     float* invn = nullptr;   // [ldN], 1/norm (0 for zero-norm vectors): GEMM engine's approximate cosine
     float* sqn = nullptr;    // [ldN], norm^2: GEMM engine's approximate L2
     uint32_t* max_norm_bits = nullptr;
+    size_t aux_bytes = 0;  // what norms, max_norm_bits, invn and sqn were allocated with, added up where each is allocated
     bool norms_ready = false;
     float max_norm = 0.0f;
     uint64_t index_base = 0;
@@ -326,6 +342,11 @@ struct innr_batch {
     uint8_t* fsel_mask = nullptr;  // [ldN] 0/1
     uint32_t* fsel_map = nullptr;  // [fsel->N]
     uint32_t fsel_builds = 0;      // selections built for this batch (read by a test hook)
+    size_t fsel_mask_bytes = 0, fsel_map_bytes = 0;  // what fsel_mask / fsel_map were allocated with
+    // memory accounting (innr_batch_memory): what V / C8 was allocated with (0 for a view), and the copy budget -- the most the
+    // derived allocations (copy[] and the selection) may add up to; see budget_admits
+    size_t corpus_bytes = 0;
+    uint64_t copy_budget = UINT64_MAX;
 };
 
 namespace innr {
@@ -342,12 +363,62 @@ static CopyKind i8_kind(int metric) {
 // The memory rule of every copy that is built unasked: it may be built when free memory is at least twice its size plus 8 GiB
 static bool copy_fits(size_t free_bytes, size_t copy_bytes) { return free_bytes >= 2 * copy_bytes + ((size_t)8 << 30); }
 
+// ---- memory accounting: every number is what was passed to hipMalloc ----
+// the public bit of a copy kind (INNR_COPY_ROWS .. INNR_COPY_I8_L2 are 1 << CopyKind, in CopyKind's order)
+static uint32_t copy_bit(int kind) { return 1u << kind; }
+static_assert(INNR_COPY_ROWS == 1u << kCopyRows && INNR_COPY_BF16_DOT == 1u << kCopyBfDot && INNR_COPY_BF16_COS == 1u << kCopyBfCos &&
+                  INNR_COPY_BF16_L2 == 1u << kCopyBfL2 && INNR_COPY_BF16LO_DOT == 1u << kCopyBfDotLo &&
+                  INNR_COPY_BF16LO_COS == 1u << kCopyBfCosLo && INNR_COPY_I8_DOT == 1u << kCopyI8Dot &&
+                  INNR_COPY_I8_COS == 1u << kCopyI8Cos && INNR_COPY_I8_L2 == 1u << kCopyI8L2 &&
+                  INNR_COPY_SELECTION == 1u << kCopyKinds && INNR_COPY_ALL == (2u << kCopyKinds) - 1,
+              "the INNR_COPY_* bits follow CopyKind");
+// one of a batch's auxiliary arrays (norms and their by-products), its size recorded for innr_batch_memory
+template <class T>
+static hipError_t alloc_aux(innr_batch* b, T** p, size_t bytes) {
+    const hipError_t e = hipMalloc((void**)p, bytes);
+    if (e == hipSuccess) b->aux_bytes += bytes;
+    return e;
+}
+static size_t corpus_copy_bytes(const innr_batch* b, uint32_t mask = INNR_COPY_ALL) {
+    size_t sum = 0;
+    for (int k = 0; k < kCopyKinds; ++k)
+        if ((mask & copy_bit(k)) && b->copy[k].p) sum += b->copy[k].bytes;
+    return sum;
+}
+// the selection without what the selection batch built for itself: its store, the mask and the map
+static size_t selection_base_bytes(const innr_batch* b) {
+    return b->fsel ? b->fsel->corpus_bytes + b->fsel_mask_bytes + b->fsel_map_bytes : 0;
+}
+// INNR_COPY_SELECTION: ... plus the selection batch's own copies (a selection has no selection of its own; its norms -- 12 bytes
+// per vector at most -- are not counted, like the batch's own)
+static size_t selection_bytes(const innr_batch* b) { return b->fsel ? selection_base_bytes(b) + corpus_copy_bytes(b->fsel) : 0; }
+static size_t derived_bytes(const innr_batch* b, uint32_t mask = INNR_COPY_ALL) {
+    return corpus_copy_bytes(b, mask) + ((mask & INNR_COPY_SELECTION) ? selection_bytes(b) : 0);
+}
+// The budget rule of every derived allocation, asked or unasked: it is made only if derived_bytes + its size <= the batch's copy
+// budget. Evaluated where the allocation is decided, never remembered (CorpusCopy::refused is about free memory, not about this);
+// nothing to allocate is always admitted, so copies that exist keep being used under a budget lowered below them.
+// `have`: what counts as derived already -- everything, except for a selection, which takes the place of the one it replaces.
+static bool budget_admits(const innr_batch* b, size_t bytes, size_t have) {
+    if (b->copy_budget == UINT64_MAX || bytes == 0) return true;
+    return have <= b->copy_budget && bytes <= b->copy_budget - have;
+}
+static bool budget_admits(const innr_batch* b, size_t bytes) { return budget_admits(b, bytes, derived_bytes(b)); }
+
 // Device memory for copy `kind` (`what` names it in the error message); the caller packs into copy[kind].p. Two policies:
 // hard (the bf16 and int8 filter copies, which a call cannot do without): a failed hipMalloc is INNR_E_OOM;
 // soft (the rows copy, the lo limbs): the memory rule first, and when it or hipMalloc says no the refusal sticks, the HIP error
 // is cleared and the call goes on without the copy -- INNR_OK with a null pointer.
+// Either way the budget comes first (budget_admits): a soft copy it does not admit is left out for this call, without the sticky
+// refusal; the hard sites resolve the budget where the engine is chosen (innr_batch_knn_dev, innr_batch_knn_u8_dev,
+// innr_batch_build_copies), so for them a refusal here is an internal error.
 static innr_status alloc_copy(innr_batch* b, CopyKind kind, size_t bytes, uint32_t nk, bool soft, const char* what) {
     CorpusCopy& cc = b->copy[kind];
+    if (!budget_admits(b, bytes)) {
+        if (soft) return INNR_OK;
+        set_error("internal: the %s (%zu bytes) is beyond the batch's copy budget", what, bytes);
+        return INNR_E_OOM;
+    }
     size_t free_b = 0, total_b = 0;
     const bool fits = !soft || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && copy_fits(free_b, bytes));
     const hipError_t e = fits ? hipMalloc((void**)&cc.p, bytes) : hipErrorOutOfMemory;
@@ -398,6 +469,12 @@ struct CtxGuard {
     ::innr::CtxGuard _guard(ctxp);  \
     INNR_TRY(::innr::bind_device(ctxp))
 
+// the copy budget a new batch starts with: the context option copy_budget_mib (< 0: unlimited)
+static uint64_t budget_from_option(const innr_ctx* ctx) {
+    const long mib = ctx->tune.copy_budget_mib;
+    return (mib < 0 || mib >= (1L << 43)) ? UINT64_MAX : (uint64_t)mib << 20;
+}
+
 static innr_status alloc_batch(innr_ctx* ctx, size_t N, size_t D, innr_batch** out) {
     if (!ctx || !out) {
         set_error("null ctx/out");
@@ -422,6 +499,8 @@ static innr_status alloc_batch(innr_ctx* ctx, size_t N, size_t D, innr_batch** o
         delete b;
         return INNR_E_OOM;
     }
+    b->corpus_bytes = bytes;
+    b->copy_budget = budget_from_option(ctx);
     e = hipMemsetAsync(b->V, 0, bytes, ctx->stream);
     if (e != hipSuccess) {
         set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
@@ -437,8 +516,8 @@ static innr_status ensure_norms(innr_batch* b) {
     if (b->norms_ready) return INNR_OK;
     innr_ctx* ctx = b->ctx;
     if (!b->norms) {
-        INNR_HIP_CHECK(hipMalloc((void**)&b->norms, b->ldN * sizeof(float)));
-        INNR_HIP_CHECK(hipMalloc((void**)&b->max_norm_bits, sizeof(uint32_t)));
+        INNR_HIP_CHECK(alloc_aux(b, &b->norms, b->ldN * sizeof(float)));
+        INNR_HIP_CHECK(alloc_aux(b, &b->max_norm_bits, sizeof(uint32_t)));
     }
     INNR_HIP_CHECK(hipMemsetAsync(b->max_norm_bits, 0, sizeof(uint32_t), ctx->stream));
     const unsigned blocks = (unsigned)((b->ldN / 4 + 255) / 256);
@@ -892,7 +971,7 @@ static innr_status launch_gemm(innr_batch* b, const GemmPlan& p, size_t nreal_q,
 static innr_status ensure_invnorms(innr_batch* b) {
     INNR_TRY(ensure_norms(b));
     if (b->invn) return INNR_OK;
-    INNR_HIP_CHECK(hipMalloc((void**)&b->invn, b->ldN * sizeof(float)));
+    INNR_HIP_CHECK(alloc_aux(b, &b->invn, b->ldN * sizeof(float)));
     inv_norms_kernel<<<(unsigned)((b->ldN + 255) / 256), 256, 0, b->ctx->stream>>>(b->norms, b->ldN, b->N, b->invn);
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
@@ -922,7 +1001,7 @@ static innr_status prep_queries(innr_batch* b, const GemmPlan& p, const float* d
 static innr_status ensure_sqnorms(innr_batch* b) {
     INNR_TRY(ensure_norms(b));
     if (b->sqn) return INNR_OK;
-    INNR_HIP_CHECK(hipMalloc((void**)&b->sqn, b->ldN * sizeof(float)));
+    INNR_HIP_CHECK(alloc_aux(b, &b->sqn, b->ldN * sizeof(float)));
     sq_norms_kernel<<<(unsigned)((b->ldN + 255) / 256), 256, 0, b->ctx->stream>>>(b->norms, b->ldN, b->N, b->sqn);
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
@@ -1178,13 +1257,16 @@ __global__ __launch_bounds__(kSelThreads) void segment_topk_kernel(const uint64_
     }
 }
 
-// the row-major copy of an f32 batch (kCopyRows), if it exists or fits with room to spare (copy_fits)
-static innr_status ensure_rowmajor(innr_batch* b, bool* have) {
+static size_t rows_copy_bytes(const innr_batch* b) { return b->N * round_up(b->D, 4) * sizeof(float); }
+
+// the row-major copy of an f32 batch (kCopyRows), if it exists or fits with room to spare (copy_fits); soft == false
+// (innr_batch_build_copies): the caller asked for it -- no memory rule, no remembered refusal, no no_rows_copy
+static innr_status ensure_rowmajor(innr_batch* b, bool* have, bool soft = true) {
     CorpusCopy& rows = b->copy[kCopyRows];
     *have = rows.p != nullptr && !b->ctx->tune.no_rows_copy;
-    if (rows.p || rows.refused || b->ctx->tune.no_rows_copy || !b->V || b->N == 0 || b->D == 0) return INNR_OK;
+    if (rows.p || (soft && (rows.refused || b->ctx->tune.no_rows_copy)) || !b->V || b->N == 0 || b->D == 0) return INNR_OK;
     const size_t Dr = round_up(b->D, 4);
-    INNR_TRY(alloc_copy(b, kCopyRows, b->N * Dr * sizeof(float), (uint32_t)Dr, true, "row-major copy"));
+    INNR_TRY(alloc_copy(b, kCopyRows, rows_copy_bytes(b), (uint32_t)Dr, soft, "row-major copy"));
     if (!rows.p) return INNR_OK;
     dim3 grid((unsigned)((b->N + 31) / 32), (unsigned)((Dr + 31) / 32));
     pdx_to_rows_kernel<<<grid, 256, 0, b->ctx->stream>>>(b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, reinterpret_cast<float*>(rows.p), (uint32_t)Dr);
@@ -1457,6 +1539,23 @@ enum LastFilter { kFilterNone = 0, kFilterF32 = 1, kFilterBf16 = 2, kFilterSplit
 // (two-wave tile), 256 queries 15.5 vs 28.8.
 constexpr size_t kSplitMinQ = 65;
 
+// the lo limbs of the dot / cosine kind (the cosine kind needs b->invn); soft: under the memory rule, else as a filter copy
+static innr_status ensure_bf16_lo(innr_batch* b, int metric, bool soft) {
+    const CopyKind hk = bf16_kind(metric), lk = bf16_kind(metric, true);
+    CorpusCopy& lo = b->copy[lk];
+    if (lo.p) return INNR_OK;
+    const uint32_t nk = bf16_nk(b, hk);
+    const size_t bytes = bf16_copy_bytes(b, hk);
+    INNR_TRY(alloc_copy(b, lk, bytes, nk, soft, "bf16 lo-limb copy"));
+    if (!lo.p) return INNR_OK;
+    const size_t units = bytes / 16;
+    pack_corpus_bf16_kernel<<<(unsigned)((units + 255) / 256), 256, 0, b->ctx->stream>>>(
+        b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(lo.p), hk == kCopyBfCos ? b->invn : nullptr,
+        nullptr, 1);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
 // The hi and lo limb copies of the dot / cosine kind. Each copy is built only when it fits (copy_fits, the rule of the other
 // filter copies); *ok == false: one did not fit, the call filters on the f32 kernel instead.
 static innr_status ensure_split_corpus(innr_batch* b, int metric, bool* ok) {
@@ -1464,8 +1563,9 @@ static innr_status ensure_split_corpus(innr_batch* b, int metric, bool* ok) {
     const CopyKind hk = bf16_kind(metric), lk = bf16_kind(metric, true);
     CorpusCopy &hi = b->copy[hk], &lo = b->copy[lk];  // (lo.refused stands for the pair)
     if (lo.refused) return INNR_OK;
-    const uint32_t nk = bf16_nk(b, hk);
     const size_t bytes = bf16_copy_bytes(b, hk);
+    // the budget has to admit what is missing of the PAIR, before either limb is built (not remembered: the next call asks again)
+    if (!budget_admits(b, (hi.p ? 0 : bytes) + (lo.p ? 0 : bytes))) return INNR_OK;
     if (!hi.p) {  // (the rule like a lo limb; once it passes, a filter copy like any other: INNR_E_OOM when hipMalloc fails)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !copy_fits(free_b, bytes)) {
@@ -1474,16 +1574,8 @@ static innr_status ensure_split_corpus(innr_batch* b, int metric, bool* ok) {
         }
         INNR_TRY(ensure_bf16_corpus(b, hk));
     }
-    if (!lo.p) {
-        INNR_TRY(alloc_copy(b, lk, bytes, nk, true, "bf16 lo-limb copy"));
-        if (!lo.p) return INNR_OK;
-        const size_t units = bytes / 16;
-        pack_corpus_bf16_kernel<<<(unsigned)((units + 255) / 256), 256, 0, b->ctx->stream>>>(
-            b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk, units, reinterpret_cast<uint4*>(lo.p), hk == kCopyBfCos ? b->invn : nullptr,
-            nullptr, 1);
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    *ok = true;
+    INNR_TRY(ensure_bf16_lo(b, metric, true));
+    *ok = lo.p != nullptr;
     return INNR_OK;
 }
 
@@ -1761,6 +1853,7 @@ static void free_selection(innr_batch* b) {
     b->fsel = nullptr;
     b->fsel_mask = nullptr;
     b->fsel_map = nullptr;
+    b->fsel_mask_bytes = b->fsel_map_bytes = 0;
 }
 
 }  // namespace innr
@@ -1818,14 +1911,7 @@ void innr_ctx_destroy(innr_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)ctx_sync(c);
-    DevBuf* bufs[] = {&c->gthr, &c->sel_tmp[0], &c->sel_tmp[1], &c->selcnt_tmp[0], &c->selcnt_tmp[1],
-                      &c->q_row, &c->q_kmajor, &c->q_norm, &c->lists, &c->counts, &c->sel, &c->sel_cnt,
-                      &c->scores, &c->tmp_norms, &c->flags, &c->out_idx, &c->out_score, &c->misc, &c->seed_idx, &c->seed_score, &c->q_one, &c->sort_keys, &c->sort_tmp, &c->q_bf16, &c->q_pad, &c->q_hat,
-                      &c->redo[0].q, &c->redo[0].idx, &c->redo[0].sc, &c->redo[0].map, &c->redo[0].qn,
-                      &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
-                      &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan,
-                      &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off};
-    for (DevBuf* b : bufs) b->release();
+    for (DevBuf* b : workspace_bufs(c)) b->release();
     if (c->pin) (void)hipHostFree(c->pin);
     for (auto& ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -2459,13 +2545,21 @@ innr_status innr_batch_knn_dev(innr_batch* b, int metric, const float* d_queries
             //  with its fourth call: 1.6 ms per query from then on instead of 5.3)
             const bool worth = Q >= 4 || (!i8c.p && ++b->auto_small_calls >= 4);
             if (f32_i8_eligible(b, metric, Q, kout) && !b->ctx->tune.no_auto_i8 && !weak &&
-                (i8c.p || (worth && have_mem && copy_fits(free_b, f32_i8_copy_bytes(b, metric)))))
+                (i8c.p || (worth && have_mem && copy_fits(free_b, f32_i8_copy_bytes(b, metric)) &&
+                           budget_admits(b, f32_i8_copy_bytes(b, metric)))))
                 engine = INNR_KNN_MFMA_I8;
-            else if (Q >= 9 && (bfc.p || (have_mem && copy_fits(free_b, bf16_copy_bytes(b, bf16_kind(metric))))))
+            else if (Q >= 9 && (bfc.p || (have_mem && copy_fits(free_b, bf16_copy_bytes(b, bf16_kind(metric))) &&
+                                          budget_admits(b, bf16_copy_bytes(b, bf16_kind(metric))))))
                 engine = INNR_KNN_MFMA_BF16;
         }
     }
     if (engine == INNR_KNN_MFMA_I8 && !f32_i8_eligible(b, metric, Q, kout))  // k > 240, a view, a u8 batch ...
+        engine = INNR_KNN_MFMA;
+    // an explicit low-precision request whose copy is missing and beyond the copy budget (the squared-L2 int8 copy: by its upper
+    // bound): the f32 engine serves the call, as the header promises for every call these filters do not take
+    if (engine == INNR_KNN_MFMA_I8 && !b->copy[i8_kind(metric)].p && !budget_admits(b, f32_i8_copy_bytes(b, metric)))
+        engine = INNR_KNN_MFMA;
+    if (engine == INNR_KNN_MFMA_BF16 && !b->copy[bf16_kind(metric)].p && !budget_admits(b, bf16_copy_bytes(b, bf16_kind(metric))))
         engine = INNR_KNN_MFMA;
     if ((engine == INNR_KNN_MFMA || engine == INNR_KNN_MFMA_BF16 || engine == INNR_KNN_MFMA_I8) && !gemm_addressable(b, Q)) engine = INNR_KNN_EXACT;
     if (kout > INNR_MAX_K) engine = INNR_KNN_EXACT;  // the full-sort path below: exact by construction
@@ -2546,6 +2640,8 @@ static innr_status alloc_batch_u8(innr_ctx* ctx, size_t N, size_t D, float alpha
     b->offset = offset;
     const size_t bytes = b->ldN * b->Dpad;
     hipError_t e = hipMalloc((void**)&b->C8, bytes);
+    if (e == hipSuccess) b->corpus_bytes = bytes;
+    b->copy_budget = budget_from_option(ctx);
     if (e == hipSuccess) e = hipMemsetAsync(b->C8, 0, bytes, ctx->stream);
     if (e != hipSuccess) {
         set_error("u8 corpus allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
@@ -2657,6 +2753,9 @@ innr_status innr_batch_prefix_view(innr_batch* parent, size_t prefix_dims, innr_
     b->offset = parent->offset;
     b->index_base = parent->index_base;
     b->is_view = true;
+    // a batch of its own to the accounting: it owns its copies, not the store, and its budget is its own -- from the context
+    // option like any new batch's, NOT the parent's, whose budget the view's copies do not count against (the header says so)
+    b->copy_budget = budget_from_option(parent->ctx);
     b->gemm_ok = parent->gemm_ok && (b->D == parent->D || b->D % 32 == 0);
     *out = b;
     return INNR_OK;
@@ -2956,12 +3055,14 @@ static bool i8_eligible(const innr_batch* b, size_t Q) {
            b->ldN < ((size_t)1 << 31) && Q < ((size_t)1 << 24);
 }
 
+static size_t u8_i8_copy_bytes(const innr_batch* b) { return (b->ldN / 128) * (size_t)i8_nk(b) * kI8StageBytes; }
+
 static innr_status ensure_i8_corpus(innr_batch* b) {
     const CorpusCopy& cc = b->copy[kCopyI8Dot];
     if (cc.p) return INNR_OK;
     const uint32_t nk = i8_nk(b);
     const size_t ntiles = b->ldN / 128;
-    INNR_TRY(alloc_copy(b, kCopyI8Dot, ntiles * nk * (size_t)kI8StageBytes, nk, false, "int8 corpus copy"));
+    INNR_TRY(alloc_copy(b, kCopyI8Dot, u8_i8_copy_bytes(b), nk, false, "int8 corpus copy"));
     const size_t nthreads = ntiles * nk * 128;
     pack_corpus_i8_kernel<<<(unsigned)((nthreads + 255) / 256), 256, 0, b->ctx->stream>>>(b->C8, b->ldN, (uint32_t)b->N, (uint32_t)b->D, nk,
                                                                                       nthreads, reinterpret_cast<uint4*>(cc.p));
@@ -3283,6 +3384,18 @@ static innr_status ensure_f32_i8_corpus(innr_batch* b, CopyKind kind, bool* usab
     return INNR_OK;
 }
 
+// The int8 copy of a metric with what it is built from (norms, 1/norm, norm^2); *usable = false: the filter does not apply to this
+// corpus (a norm outside the bound's range, constant or non-finite values)
+static innr_status ensure_f32_i8_filter(innr_batch* b, int metric, bool* usable) {
+    const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
+    *usable = false;
+    INNR_TRY(ensure_norms(b));
+    if (!(b->max_norm - b->max_norm == 0.0f) || !(b->max_norm >= 1e-12f) || (l2 && !(b->max_norm <= 1e15f))) return INNR_OK;
+    if (cos) INNR_TRY(ensure_invnorms(b));
+    if (l2) INNR_TRY(ensure_sqnorms(b));
+    return ensure_f32_i8_corpus(b, i8_kind(metric), usable);
+}
+
 // *served = false: the engine does not apply to this corpus (constant values): the caller takes the f32 engine
 // collect_kth != null: the COMPLETION pass of this filter (cf. knn_complete): dQ are the unproven queries (gathered), collect_kth[j]
 // = the k-th best EXACT score query j has so far (a lower bound of the true one); the kernel runs in collect mode with the fixed
@@ -3294,13 +3407,9 @@ innr_status innr::knn_f32_i8(innr_batch* b, int metric, const float* dQ, size_t 
     innr_ctx* c = b->ctx;
     const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
     *served = false;
-    INNR_TRY(ensure_norms(b));
-    if (!(b->max_norm - b->max_norm == 0.0f) || !(b->max_norm >= 1e-12f) || (l2 && !(b->max_norm <= 1e15f))) return INNR_OK;
-    if (cos) INNR_TRY(ensure_invnorms(b));
-    if (l2) INNR_TRY(ensure_sqnorms(b));
     bool usable = true;
     const CopyKind kind = i8_kind(metric);
-    INNR_TRY(ensure_f32_i8_corpus(b, kind, &usable));
+    INNR_TRY(ensure_f32_i8_filter(b, metric, &usable));
     if (!usable) return INNR_OK;
     *served = true;
     const float alpha = b->i8_range(kind).alpha, offset = b->i8_range(kind).offset;
@@ -3462,14 +3571,16 @@ innr_status innr_batch_knn_u8_dev(innr_batch* b, const float* d_queries, size_t 
             // exists, from four when it has to be built and fits with room to spare; larger batches as before.
             size_t free_b = 0, total_b = 0;
             const bool have_mem = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-            const size_t copy_b = (b->ldN / 128) * (size_t)i8_nk(b) * kI8StageBytes;
+            const size_t copy_b = u8_i8_copy_bytes(b);
             const bool have_copy = b->copy[kCopyI8Dot].p != nullptr;
             const bool worth = Q >= 4 || (Q >= 2 && !have_copy && ++b->auto_small_calls >= 4);  // (the fourth small call builds the copy)
-            if (have_copy ? Q >= 2 : (worth && have_mem && copy_fits(free_b, copy_b))) engine = INNR_KNN_MFMA_I8;
+            if (have_copy ? Q >= 2 : (worth && have_mem && copy_fits(free_b, copy_b) && budget_admits(b, copy_b))) engine = INNR_KNN_MFMA_I8;
         }
     }
     if (engine == INNR_KNN_MFMA_BF16) engine = INNR_KNN_MFMA;  // codes are exact in 8 bits: the low-precision filter is the int8 one
     if (engine == INNR_KNN_MFMA_I8 && !i8_eligible(b, Q)) engine = INNR_KNN_MFMA;  // alpha <= 0 / non-finite params / D beyond the limbs
+    if (engine == INNR_KNN_MFMA_I8 && !b->copy[kCopyI8Dot].p && !budget_admits(b, u8_i8_copy_bytes(b)))  // beyond the copy budget
+        engine = INNR_KNN_MFMA;
     if (engine == INNR_KNN_MFMA && !gemm_addressable(b, Q)) engine = INNR_KNN_EXACT;
     if (kout > INNR_MAX_K) engine = INNR_KNN_EXACT;
     uint32_t nfallback = 0, kept = kout > INNR_MAX_K ? (uint32_t)b->N : pick_kp(kout, 0);
@@ -3507,6 +3618,7 @@ struct innr_docs {
     float* tok = nullptr;          // [ndocs][T][dim]
     uint32_t* doc_len = nullptr;   // [ndocs] or null (every document has T tokens)
     float* tok_inv = nullptr;      // [ndocs*T] 1/|token| (0 for zero-norm tokens), built on first MFMA-engine use
+    size_t tok_bytes = 0, doc_len_bytes = 0, tok_inv_bytes = 0;  // what each was allocated with (innr_docs_memory)
     float max_norm = 0.0f;         // max |token| over the corpus
     uint64_t index_base = 0;
 };
@@ -3531,6 +3643,7 @@ static innr_status alloc_docs(innr_ctx* ctx, size_t ndocs, size_t T, size_t dim,
         delete d;
         return INNR_E_OOM;
     }
+    d->tok_bytes = bytes;
     *out = d;
     return INNR_OK;
 }
@@ -3545,6 +3658,7 @@ innr_status innr_maxsim_upload(innr_ctx* ctx, const float* tokens, const uint32_
     if (ndocs * T * dim) e = hipMemcpy(d->tok, tokens, ndocs * T * dim * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess && doc_len && ndocs) {
         e = hipMalloc((void**)&d->doc_len, ndocs * sizeof(uint32_t));
+        if (e == hipSuccess) d->doc_len_bytes = ndocs * sizeof(uint32_t);
         if (e == hipSuccess) e = hipMemcpy(d->doc_len, doc_len, ndocs * sizeof(uint32_t), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
@@ -3742,6 +3856,7 @@ static innr_status maxsim_ensure_token_norms(innr_docs* d) {
         set_error("hipMalloc(%zu bytes) for token norms failed: %s", ntok * sizeof(float), hipGetErrorString(e));
         return INNR_E_OOM;
     }
+    d->tok_inv_bytes = (ntok + 64) * sizeof(float);
     INNR_TRY(c->misc.ensure(4096));
     INNR_HIP_CHECK(hipMemsetAsync(c->misc.p, 0, 4, c->stream));
     maxsim_token_norms_kernel<<<(unsigned)((ntok + 255) / 256), 256, 0, c->stream>>>(d->tok, ntok, (uint32_t)d->dim, d->tok_inv,
@@ -4423,6 +4538,12 @@ static innr_status filter_mask(innr_batch* b, const uint8_t* d_mask, size_t* npa
 static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
     innr_ctx* c = b->ctx;
     *built = false;
+    // The copy budget, for the store, the mask and the map (alloc_batch's and the two hipMallocs' sizes below) in the place of the
+    // selection they replace. Not admitted: the selection of the last mask stays (the library frees nothing by itself), the
+    // masked exact scan serves this call.
+    const size_t store_bytes = round_up(npass ? npass : 1, 256) * round_up(b->D ? b->D : 1, 32) * sizeof(float);
+    const size_t mask_bytes = b->ldN, map_bytes = npass * sizeof(uint32_t);
+    if (!budget_admits(b, store_bytes + mask_bytes + map_bytes, corpus_copy_bytes(b))) return INNR_OK;
     free_selection(b);
     innr_batch* s = nullptr;
     const innr_status st = alloc_batch(c, npass, b->D, &s);
@@ -4432,11 +4553,13 @@ static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
     }
     INNR_TRY(st);
     b->fsel = s;
-    if (hipMalloc((void**)&b->fsel_mask, b->ldN) != hipSuccess || hipMalloc((void**)&b->fsel_map, npass * sizeof(uint32_t)) != hipSuccess) {
+    if (hipMalloc((void**)&b->fsel_mask, mask_bytes) != hipSuccess || hipMalloc((void**)&b->fsel_map, map_bytes) != hipSuccess) {
         (void)hipGetLastError();
         free_selection(b);
         return INNR_OK;
     }
+    b->fsel_mask_bytes = mask_bytes;
+    b->fsel_map_bytes = map_bytes;
     const size_t nchunks = b->ldN / kSelChunk;
     const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
     const size_t D = b->D;
@@ -4519,6 +4642,9 @@ innr_status innr_batch_knn_filtered_multi_dev(innr_batch* b, int metric, const f
         bool have = same;
         if (engine != INNR_KNN_EXACT && !same) INNR_TRY(build_selection(b, npass, &have));
         if (engine != INNR_KNN_EXACT && have) {
+            // the selection's copies count against this batch's budget: it gets what this batch's copies and its own store leave
+            const size_t used = corpus_copy_bytes(b) + selection_base_bytes(b);
+            b->fsel->copy_budget = b->copy_budget == UINT64_MAX ? UINT64_MAX : (b->copy_budget > used ? b->copy_budget - used : 0);
             // the caller's engine on the selection (its own index_base is 0), then selection indices -> this batch's
             INNR_TRY(innr_batch_knn_dev(b->fsel, metric, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
             const size_t n = Q * *out_k;
@@ -4571,6 +4697,166 @@ innr_status innr_batch_knn_filtered_multi(innr_batch* b, int metric, const float
     return knn_from_host(c, queries, Q, D, std::min(k, b->N), out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
         return innr_batch_knn_filtered_multi_dev(b, metric, dQ, Q, D, k, c->flt_in.as<uint8_t>(), engine, di, ds, out_k, stats);
     });
+}
+
+// ---- device memory: report, release, prebuild, budget (the accounting lives beside copy_fits) ------------------------------
+innr_status innr_batch_memory(const innr_batch* b, uint64_t* corpus_bytes, uint64_t* aux, uint64_t* derived, uint32_t* present_mask) {
+    if (!b) {
+        set_error("batch is null");
+        return INNR_E_BAD_ARG;
+    }
+    CtxGuard _guard(b->ctx);  // host bookkeeping only: no device is bound, no HIP call made
+    if (corpus_bytes) *corpus_bytes = b->is_view ? 0 : b->corpus_bytes;
+    if (aux) *aux = b->aux_bytes;
+    if (derived) *derived = derived_bytes(b);
+    if (present_mask) {
+        uint32_t m = b->fsel ? INNR_COPY_SELECTION : 0u;
+        for (int k = 0; k < kCopyKinds; ++k)
+            if (b->copy[k].p) m |= copy_bit(k);
+        *present_mask = m;
+    }
+    return INNR_OK;
+}
+
+innr_status innr_batch_copy_bytes(const innr_batch* b, uint32_t mask, uint64_t* bytes) {
+    if (!b || !bytes) {
+        set_error("batch or bytes is null");
+        return INNR_E_BAD_ARG;
+    }
+    CtxGuard _guard(b->ctx);
+    *bytes = derived_bytes(b, mask);
+    return INNR_OK;
+}
+
+innr_status innr_batch_set_copy_budget(innr_batch* b, uint64_t bytes) {
+    if (!b) {
+        set_error("batch is null");
+        return INNR_E_BAD_ARG;
+    }
+    CtxGuard _guard(b->ctx);
+    b->copy_budget = bytes;
+    return INNR_OK;
+}
+
+innr_status innr_batch_get_copy_budget(const innr_batch* b, uint64_t* bytes) {
+    if (!b || !bytes) {
+        set_error("batch or bytes is null");
+        return INNR_E_BAD_ARG;
+    }
+    CtxGuard _guard(b->ctx);
+    *bytes = b->copy_budget;
+    return INNR_OK;
+}
+
+innr_status innr_batch_release_copies(innr_batch* b, uint32_t mask) {
+    if (!b) {
+        set_error("batch is null");
+        return INNR_E_BAD_ARG;
+    }
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(ctx_sync(c));  // nothing queued may still read what is freed below
+    if (mask & INNR_COPY_BF16_DOT) mask |= INNR_COPY_BF16LO_DOT;  // the split filter needs the pair
+    if (mask & INNR_COPY_BF16_COS) mask |= INNR_COPY_BF16LO_COS;
+    for (int k = 0; k < kCopyKinds; ++k) {
+        if (!(mask & copy_bit(k))) continue;
+        CorpusCopy& cc = b->copy[k];
+        if (cc.p) (void)hipFree(cc.p);
+        cc.p = nullptr;
+        cc.bytes = 0;
+        cc.nk = 0;
+        cc.refused = false;  // "try again": the next call that wants the copy asks the memory rule anew (weak is about the data: kept)
+    }
+    if (mask & INNR_COPY_SELECTION) free_selection(b);
+    return INNR_OK;
+}
+
+innr_status innr_batch_build_copies(innr_batch* b, uint32_t mask, uint32_t* built_mask) {
+    if (built_mask) *built_mask = 0;
+    if (!b) {
+        set_error("batch is null");
+        return INNR_E_BAD_ARG;
+    }
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    mask &= INNR_COPY_ALL & ~INNR_COPY_SELECTION;  // (no mask to select with)
+    const auto wants = [&](CopyKind k) { return (mask & copy_bit(k)) && !b->copy[k].p; };
+    const int metrics[3] = {INNR_METRIC_DOT, INNR_METRIC_COSINE, INNR_METRIC_L2SQ};
+    if (b->N && b->D && b->C8) {
+        // a code batch has one derived copy: the K-packed signed codes of its int8 engine
+        if (wants(kCopyI8Dot) && i8_eligible(b, 1) && budget_admits(b, u8_i8_copy_bytes(b))) INNR_TRY(ensure_i8_corpus(b));
+    } else if (b->N && b->D && b->V) {
+        if (wants(kCopyRows) && budget_admits(b, rows_copy_bytes(b))) {
+            bool have = false;
+            INNR_TRY(ensure_rowmajor(b, &have, false));
+        }
+        if (gemm_addressable(b, 1)) {  // (a view whose length is no multiple of 32 has no matrix-pipe engine)
+            INNR_TRY(ensure_norms(b));
+            const float mn = b->max_norm;
+            const bool mfin = mn - mn == 0.0f;
+            for (int metric : metrics) {  // the gates are choose_f32_filter's and knn_f32_i8's
+                const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
+                const CopyKind hk = bf16_kind(metric);
+                const size_t bytes = bf16_copy_bytes(b, hk);
+                const bool bf_ok = mfin && mn >= 1e-12f && (!l2 || mn <= 1e15f);
+                if (wants(hk) && bf_ok && budget_admits(b, bytes)) {
+                    if (cos) INNR_TRY(ensure_invnorms(b));
+                    if (l2) INNR_TRY(ensure_sqnorms(b));
+                    INNR_TRY(ensure_bf16_corpus(b, hk));
+                }
+                // a lo-limb kind brings its partner: the budget has to admit what is missing of the pair
+                if (!l2 && wants(bf16_kind(metric, true)) && mfin && mn >= 1e-12f && mn <= 1e18f &&
+                    budget_admits(b, (b->copy[hk].p ? 0 : bytes) + bytes)) {
+                    if (cos) INNR_TRY(ensure_invnorms(b));
+                    INNR_TRY(ensure_bf16_corpus(b, hk));
+                    INNR_TRY(ensure_bf16_lo(b, metric, false));
+                }
+                if (wants(i8_kind(metric)) && f32_i8_eligible(b, metric, 1, 1) && budget_admits(b, f32_i8_copy_bytes(b, metric))) {
+                    bool usable = false;
+                    INNR_TRY(ensure_f32_i8_filter(b, metric, &usable));
+                }
+            }
+        }
+    }
+    if (built_mask)
+        for (int k = 0; k < kCopyKinds; ++k)
+            if ((mask & copy_bit(k)) && b->copy[k].p) *built_mask |= copy_bit(k);
+    return INNR_OK;
+}
+
+innr_status innr_docs_memory(const innr_docs* d, uint64_t* corpus_bytes, uint64_t* derived) {
+    if (!d) {
+        set_error("corpus is null");
+        return INNR_E_BAD_ARG;
+    }
+    CtxGuard _guard(d->ctx);
+    if (corpus_bytes) *corpus_bytes = d->tok_bytes + d->doc_len_bytes;
+    if (derived) *derived = d->tok_inv_bytes;
+    return INNR_OK;
+}
+
+innr_status innr_ctx_memory(innr_ctx* c, uint64_t* workspace_bytes) {
+    if (!c) {
+        set_error("ctx is null");
+        return INNR_E_BAD_ARG;
+    }
+    CtxGuard _guard(c);
+    size_t sum = 0;
+    for (const DevBuf* buf : workspace_bufs(c)) sum += buf->bytes;
+    if (workspace_bytes) *workspace_bytes = sum;
+    return INNR_OK;
+}
+
+innr_status innr_ctx_trim(innr_ctx* c) {
+    if (!c) {
+        set_error("ctx is null");
+        return INNR_E_BAD_ARG;
+    }
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(ctx_sync(c));
+    for (DevBuf* buf : workspace_bufs(c))
+        if (buf != &c->flags) buf->release();  // (flags: set up once in innr_ctx_create, see workspace_bufs)
+    return INNR_OK;
 }
 
 innr_status innr_batch_l2_squared_pruning(innr_batch* b, const float* q, size_t D, float threshold, uint64_t* out_idx,
@@ -5081,8 +5367,11 @@ struct innr_comm {
     DevBuf block, all, loc_idx, loc_sc, hdr;  // this rank's block, the gathered blocks, the local top-k
     // Vectors in all shards, learnt from the first exchange's headers: shard sizes are fixed once the shards are attached, so
     // later calls launch the merge without a host round trip; the merge kernel re-checks the sum and flags a stale figure.
+    // A stale figure LARGER than the truth would let that first merge write min(k, total) entries per query into buffers the
+    // caller sized for the true total: the figure is dropped here, on the host, whenever this rank's own shard is not the one
+    // it was learnt with (total_shard_n) -- e.g. one communicator serving a large and then a small shard.
     bool have_total = false;
-    uint64_t total = 0;
+    uint64_t total = 0, total_shard_n = 0;
     bool broken = false;  // a collective failed: the communicator is aborted, not destroyed
 };
 
@@ -5265,6 +5554,7 @@ static innr_status sharded_exchange(innr_comm* cm, innr_status local_status, int
     }
     INNR_TRY(innr_allgather_topk_dev(cm, cm->block.as<uint64_t>(), Q, k, cm->all.as<uint64_t>()));
     const size_t G = (size_t)cm->world;
+    if (cm->have_total && cm->total_shard_n != shard_n) cm->have_total = false;  // another shard than the cached total was learnt with
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (!cm->have_total) {  // first exchange (or the cached figure went stale): learn the shard sizes from the headers
             std::vector<uint64_t> hdr(2 * G);
@@ -5277,6 +5567,7 @@ static innr_status sharded_exchange(innr_comm* cm, innr_status local_status, int
             INNR_TRY(failed_rank_error(hdr.data(), G));
             cm->total = 0;
             for (size_t g = 0; g < G; ++g) cm->total += hdr[2 * g + 1];
+            cm->total_shard_n = shard_n;
             cm->have_total = true;
         }
         const size_t kout = (size_t)std::min<uint64_t>(k, cm->total);

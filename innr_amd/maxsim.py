@@ -80,6 +80,12 @@ class DocumentCorpus:
                                         C.byref(h)))
         return cls(h, n, T, dim, ctx)
 
+    def memory(self) -> _lib.DocsMemory:
+        """Device bytes of this corpus (innr_docs_memory): tokens + doc_len, and the token norms the MFMA engine builds."""
+        c, d = C.c_uint64(0), C.c_uint64(0)
+        check(load().innr_docs_memory(self._h, C.byref(c), C.byref(d)))
+        return _lib.DocsMemory(int(c.value), int(d.value))
+
     @classmethod
     def generate(cls, ndocs: int, T: int, dim: int, seed: int = 0, row0: int = 0, ctx: Optional[_lib.Context] = None):
         """Synthetic corpus made on the device: token (doc, t) = normalised uniform row (row0 + doc*T + t)."""

@@ -140,7 +140,7 @@ def asymmetric_dot_u8(query, quantized: QuantizedU8, params: QuantizationParams)
     return asymmetric_dot_u8_precomputed(q, quantized, params, query_context(q))
 
 
-class QuantizedCorpus:
+class QuantizedCorpus(_lib.BatchMemoryMixin):
     """Device-resident packed code array of a &[QuantizedU8] (addition; see module docstring)."""
 
     def __init__(self, handle, n: int, dim: int, params: QuantizationParams, ctx: _lib.Context):

@@ -41,6 +41,18 @@ pub mod ffi {
     pub const INNR_E_OOM: c_int = -3;
     pub const INNR_E_HIP: c_int = -4;
     pub const INNR_E_UNSUPPORTED: c_int = -6;
+    // the derived allocations of a batch, one bit each (innr_batch_memory and its neighbours)
+    pub const INNR_COPY_ROWS: u32 = 1 << 0;
+    pub const INNR_COPY_BF16_DOT: u32 = 1 << 1;
+    pub const INNR_COPY_BF16_COS: u32 = 1 << 2;
+    pub const INNR_COPY_BF16_L2: u32 = 1 << 3;
+    pub const INNR_COPY_BF16LO_DOT: u32 = 1 << 4;
+    pub const INNR_COPY_BF16LO_COS: u32 = 1 << 5;
+    pub const INNR_COPY_I8_DOT: u32 = 1 << 6;
+    pub const INNR_COPY_I8_COS: u32 = 1 << 7;
+    pub const INNR_COPY_I8_L2: u32 = 1 << 8;
+    pub const INNR_COPY_SELECTION: u32 = 1 << 9;
+    pub const INNR_COPY_ALL: u32 = 0x3FF;
     extern "C" {
         // ---- generated from include/innr_hip.h by tools/gen_rust_ffi.py: begin
         pub fn innr_ctx_create(device: c_int, out: *mut *mut InnrCtx) -> c_int;
@@ -106,6 +118,15 @@ pub mod ffi {
         pub fn innr_batch_rerank(b: *mut InnrBatch, metric: c_int, queries: *const f32, q: usize, d: usize, cand: *const u64, kc: usize, k: usize, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize) -> c_int;
         pub fn innr_batch_rerank_dev(b: *mut InnrBatch, metric: c_int, d_queries: *const f32, q: usize, d: usize, d_cand: *const u64, kc: usize, k: usize, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize) -> c_int;
         pub fn innr_batch_prefix_view(parent: *mut InnrBatch, prefix_dims: usize, out: *mut *mut InnrBatch) -> c_int;
+        pub fn innr_batch_memory(b: *const InnrBatch, corpus_bytes: *mut u64, aux_bytes: *mut u64, derived_bytes: *mut u64, present_mask: *mut u32) -> c_int;
+        pub fn innr_batch_copy_bytes(b: *const InnrBatch, mask: u32, bytes: *mut u64) -> c_int;
+        pub fn innr_batch_release_copies(b: *mut InnrBatch, mask: u32) -> c_int;
+        pub fn innr_batch_build_copies(b: *mut InnrBatch, mask: u32, built_mask: *mut u32) -> c_int;
+        pub fn innr_batch_set_copy_budget(b: *mut InnrBatch, bytes: u64) -> c_int;
+        pub fn innr_batch_get_copy_budget(b: *const InnrBatch, bytes: *mut u64) -> c_int;
+        pub fn innr_docs_memory(d: *const InnrDocs, corpus_bytes: *mut u64, derived_bytes: *mut u64) -> c_int;
+        pub fn innr_ctx_memory(ctx: *mut InnrCtx, workspace_bytes: *mut u64) -> c_int;
+        pub fn innr_ctx_trim(ctx: *mut InnrCtx) -> c_int;
         pub fn innr_merge_topk_dev(ctx: *mut InnrCtx, metric: c_int, d_idx: *const u64, d_score: *const f32, g: usize, q: usize, kin: usize, kout: usize, d_out_idx: *mut u64, d_out_score: *mut f32) -> c_int;
         pub fn innr_comm_unique_id(id_out: *mut c_void) -> c_int;
         pub fn innr_comm_create(ctx: *mut InnrCtx, id: *const c_void, rank: c_int, world: c_int, out: *mut *mut InnrComm) -> c_int;
@@ -155,6 +176,53 @@ fn check(st: i32) {
         panic!("assertion `left == right` failed: {}", last_error()); // the reference's assert_eq! (batch.rs:251,285,386,743,778)
     }
     assert!(st == ffi::INNR_OK, "innr_hip: {}", last_error());
+}
+
+/// Device memory of a batch (an addition; the reference's quantised store has `memory_bytes()`, scalar.rs:205-208): what it holds,
+/// giving derived copies back, building them ahead of the first query, and a budget for them. `COPY_*` = the header's INNR_COPY_* bits.
+pub mod memory {
+    use super::*;
+    pub use super::ffi::{INNR_COPY_ALL as COPY_ALL, INNR_COPY_BF16LO_COS as COPY_BF16LO_COS, INNR_COPY_BF16LO_DOT as COPY_BF16LO_DOT,
+                         INNR_COPY_BF16_COS as COPY_BF16_COS, INNR_COPY_BF16_DOT as COPY_BF16_DOT, INNR_COPY_BF16_L2 as COPY_BF16_L2,
+                         INNR_COPY_I8_COS as COPY_I8_COS, INNR_COPY_I8_DOT as COPY_I8_DOT, INNR_COPY_I8_L2 as COPY_I8_L2,
+                         INNR_COPY_ROWS as COPY_ROWS, INNR_COPY_SELECTION as COPY_SELECTION};
+
+    /// innr_batch_memory: bytes exactly as allocated
+    #[derive(Default, Clone, Copy, Debug, PartialEq, Eq)]
+    pub struct BatchMemory { pub corpus_bytes: u64, pub aux_bytes: u64, pub derived_bytes: u64, pub present_mask: u32 }
+
+    pub(crate) fn batch_memory(h: *mut ffi::InnrBatch) -> BatchMemory {
+        let mut m = BatchMemory::default();
+        check(unsafe { ffi::innr_batch_memory(h, &mut m.corpus_bytes, &mut m.aux_bytes, &mut m.derived_bytes, &mut m.present_mask) });
+        m
+    }
+    pub(crate) fn copy_bytes(h: *mut ffi::InnrBatch, mask: u32) -> u64 {
+        let mut v = 0u64;
+        check(unsafe { ffi::innr_batch_copy_bytes(h, mask, &mut v) });
+        v
+    }
+    pub(crate) fn release_copies(h: *mut ffi::InnrBatch, mask: u32) { check(unsafe { ffi::innr_batch_release_copies(h, mask) }) }
+    pub(crate) fn build_copies(h: *mut ffi::InnrBatch, mask: u32) -> u32 {
+        let mut built = 0u32;
+        check(unsafe { ffi::innr_batch_build_copies(h, mask, &mut built) });
+        built
+    }
+    pub(crate) fn set_copy_budget(h: *mut ffi::InnrBatch, bytes: Option<u64>) {
+        check(unsafe { ffi::innr_batch_set_copy_budget(h, bytes.unwrap_or(u64::MAX)) })
+    }
+    pub(crate) fn copy_budget(h: *mut ffi::InnrBatch) -> Option<u64> {
+        let mut v = 0u64;
+        check(unsafe { ffi::innr_batch_get_copy_budget(h, &mut v) });
+        if v == u64::MAX { None } else { Some(v) }
+    }
+    /// bytes of the process-wide context's device workspace (innr_ctx_memory)
+    #[must_use] pub fn workspace_bytes() -> u64 {
+        let mut v = 0u64;
+        check(unsafe { ffi::innr_ctx_memory(ctx(), &mut v) });
+        v
+    }
+    /// give the workspace back; it grows again on demand (innr_ctx_trim)
+    pub fn trim_workspace() { check(unsafe { ffi::innr_ctx_trim(ctx()) }) }
 }
 
 pub mod batch {
@@ -228,6 +296,17 @@ pub mod batch {
         /// range-partitioned corpus (sharded::Comm): this batch holds rows [base, base + num_vectors) of the global
         /// corpus; every index it reports is `base + local index`
         pub fn set_index_base(&self, base: u64) { check(unsafe { ffi::innr_batch_set_index_base(self.h, base) }) }
+        /// device bytes of this batch (innr_batch_memory)
+        #[must_use] pub fn memory(&self) -> crate::memory::BatchMemory { crate::memory::batch_memory(self.h) }
+        /// bytes of the derived kinds in `mask` (`memory::COPY_*`)
+        #[must_use] pub fn copy_bytes(&self, mask: u32) -> u64 { crate::memory::copy_bytes(self.h, mask) }
+        /// free the kinds in `mask`; the next call that wants one builds it again (innr_batch_release_copies)
+        pub fn release_copies(&self, mask: u32) { crate::memory::release_copies(self.h, mask) }
+        /// build the kinds in `mask` now; returns those present afterwards (innr_batch_build_copies)
+        pub fn build_copies(&self, mask: u32) -> u32 { crate::memory::build_copies(self.h, mask) }
+        /// the most the derived allocations may add up to; `None` = unlimited (innr_batch_set_copy_budget)
+        pub fn set_copy_budget(&self, bytes: Option<u64>) { crate::memory::set_copy_budget(self.h, bytes) }
+        #[must_use] pub fn copy_budget(&self) -> Option<u64> { crate::memory::copy_budget(self.h) }
     }
 
     fn scores_into(metric: i32, query: &[f32], batch: &VerticalBatch, norms: Option<&[f32]>, out: &mut Vec<f32>) {
@@ -486,6 +565,17 @@ pub mod scalar {
         pub fn len(&self) -> usize { self.n }
         pub fn is_empty(&self) -> bool { self.n == 0 }
         pub fn dimension(&self) -> usize { self.dim }
+        /// device bytes of this batch (innr_batch_memory)
+        #[must_use] pub fn memory(&self) -> crate::memory::BatchMemory { crate::memory::batch_memory(self.h) }
+        /// bytes of the derived kinds in `mask` (`memory::COPY_*`)
+        #[must_use] pub fn copy_bytes(&self, mask: u32) -> u64 { crate::memory::copy_bytes(self.h, mask) }
+        /// free the kinds in `mask`; the next call that wants one builds it again (innr_batch_release_copies)
+        pub fn release_copies(&self, mask: u32) { crate::memory::release_copies(self.h, mask) }
+        /// build the kinds in `mask` now; returns those present afterwards (innr_batch_build_copies)
+        pub fn build_copies(&self, mask: u32) -> u32 { crate::memory::build_copies(self.h, mask) }
+        /// the most the derived allocations may add up to; `None` = unlimited (innr_batch_set_copy_budget)
+        pub fn set_copy_budget(&self, bytes: Option<u64>) { crate::memory::set_copy_budget(self.h, bytes) }
+        #[must_use] pub fn copy_budget(&self) -> Option<u64> { crate::memory::copy_budget(self.h) }
     }
 
     /// scalar.rs:370-393, reference signature (uploads the corpus for this one call)
@@ -521,6 +611,12 @@ pub mod maxsim {
     impl Drop for DocumentCorpus { fn drop(&mut self) { unsafe { ffi::innr_docs_free(self.h) } } }
     impl DocumentCorpus {
         pub(crate) fn handle(&self) -> *mut ffi::InnrDocs { self.h }
+        /// device bytes of this corpus: `(tokens + doc_len, token norms of the MFMA engine)` (innr_docs_memory)
+        #[must_use] pub fn memory(&self) -> (u64, u64) {
+            let (mut c, mut d) = (0u64, 0u64);
+            check(unsafe { ffi::innr_docs_memory(self.h, &mut c, &mut d) });
+            (c, d)
+        }
         /// this shard holds documents [base, base + count) of a range-partitioned corpus (reported indices are global)
         pub fn set_index_base(&mut self, base: usize) { check(unsafe { ffi::innr_docs_set_index_base(self.h, base as u64) }); }
         /// `tokens`: `[docs][max_tokens][dim]` flattened, `doc_len[i]` valid tokens of document i
