@@ -128,7 +128,7 @@ static void tuning_from_env(innr_tuning* t) {
 }
 
 // One templated kernel launch of the filter and scan families, as its dispatch site chose it (innr_ctx::launch_log). Written by
-// plain host stores at the dispatch sites of every build; read only by the test hooks (innrdbg_launch_log), which
+// plain host stores in launch_kernel, in every build; read only by the test hooks (innrdbg_launch_log), which
 // tests/test_gpu_kernel_variants.py decodes: its table names every instantiation a call may reach.
 enum LaunchFamily {
     kLaunchGemmF32 = 1,    // gemm_filter_kernel<KIND, RR, MODE, WV>
@@ -215,7 +215,7 @@ struct innr_ctx {
     DevBuf rs_thr;     // ... the thresholds and [Q + 1] offsets of the host-memory entry point, staged on the device
     DevBuf rs_off;
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
-    LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (log_launch; read by a test hook)
+    LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
 };
 
@@ -232,17 +232,76 @@ static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
             &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off};
 }
 
-// record one templated launch (the caller holds the context's lock, as every dispatch site does): a few host stores
-static inline void log_launch(innr_ctx* c, int family, int a0, int a1 = 0, int a2 = 0, int a3 = 0, uint32_t groups = 1,
-                              bool lockstep = false) {
-    LaunchRec& r = c->launch_log[c->launch_total++ % kLaunchLogCap];
-    r.family = (uint8_t)family;
-    r.lockstep = lockstep ? 1 : 0;
-    r.arg[0] = (int16_t)a0;
-    r.arg[1] = (int16_t)a1;
-    r.arg[2] = (int16_t)a2;
-    r.arg[3] = (int16_t)a3;
-    r.groups = groups;
+// ---- choosing a kernel instantiation from run-time values ------------------------------------------------------------
+// One instantiation of a recorded family, as compile-time constants: the family and the template arguments in the order of
+// LaunchFamily's comments (bool parameters as 0 / 1). kernel_of(Inst) is the kernel they name.
+template <int N> using IntC = std::integral_constant<int, N>;
+template <int FAMILY, int... ARGS> struct Inst {};
+template <int KIND, int RR, int MODE, int WV> constexpr auto kernel_of(Inst<kLaunchGemmF32, KIND, RR, MODE, WV>) { return &gemm_filter_kernel<KIND, RR, MODE, WV>; }
+template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmBf16, RR, MODE, 1>) { return &gemm_bf16_filter_kernel<RR, MODE, 1>; }
+template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmSplit, RR, MODE, 3>) { return &gemm_bf16_filter_kernel<RR, MODE, 3>; }
+template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8One, RR, MODE>) { return &gemm_i8h_filter_kernel<RR, MODE>; }
+template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Two, RR, MODE>) { return &gemm_i8_filter_kernel<RR, MODE>; }
+template <int NK, int CT, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Small, NK, CT, MODE>) { return &gemm_i8s_filter_kernel<12, NK, CT, MODE>; }
+template <int COS, int NQ, int MULTI> constexpr auto kernel_of(Inst<kLaunchMsScan, COS, NQ, MULTI>) { return &maxsim_scan_kernel<COS != 0, NQ, MULTI != 0>; }
+template <int COS, int NB, int NQ> constexpr auto kernel_of(Inst<kLaunchMsTile, COS, NB, NQ>) { return &maxsim_mfma_tile_kernel<COS != 0, NB, NQ>; }
+template <int COS> constexpr auto kernel_of(Inst<kLaunchMsGeneric, COS>) { return &maxsim_mfma_kernel<COS != 0>; }
+template <int COS, int NQ, int MULTI> constexpr auto kernel_of(Inst<kLaunchMsRerank, COS, NQ, MULTI>) { return &maxsim_rerank_kernel<COS != 0, NQ, MULTI != 0>; }
+template <int QB, int MET, int EMIT> constexpr auto kernel_of(Inst<kLaunchRangeScan, QB, MET, EMIT>) {
+    return &range_scan_kernel<QB, MET == INNR_METRIC_L2SQ, MET == INNR_METRIC_COSINE, EMIT != 0>;
+}
+
+// Record an instantiation (the caller holds the context's lock, as every dispatch site does: a few host stores) and launch it on
+// the context's stream. The record is written from the constants that name the kernel, so it cannot name another one.
+struct LaunchDims {
+    dim3 grid, block;
+    size_t lds = 0;
+    uint32_t groups = 1;    // LaunchRec::groups
+    bool lockstep = false;  // LaunchRec::lockstep
+};
+template <int FAMILY, int... ARGS, class... KernelArgs>
+static void launch_kernel(innr_ctx* c, Inst<FAMILY, ARGS...> inst, const LaunchDims& d, KernelArgs... args) {
+    c->launch_log[c->launch_total++ % kLaunchLogCap] = LaunchRec{(uint8_t)FAMILY, (uint8_t)d.lockstep, {ARGS...}, d.groups};
+    kernel_of(inst)<<<d.grid, d.block, d.lds, c->stream>>>(args...);
+}
+
+// A run-time value that selects one of the constants Vs; any other value selects the LAST of them (a switch's `default:`).
+// dispatch(f, one_of<..>(a), one_of<..>(b), ...) calls f(IntC<A>(), IntC<B>(), ...) with the selected constants and returns what it
+// returns: f is a generic lambda, instantiated once per combination, and excludes the combinations that must not exist by
+// `if constexpr` on its arguments.
+template <int... Vs> struct OneOf { int v; };
+template <int... Vs> static OneOf<Vs...> one_of(long v) { return {(int)v}; }
+template <class F> static auto dispatch(F&& f) { return f(); }
+template <class F, int V, int... Vs, class... Rest>
+static auto dispatch(F&& f, OneOf<V, Vs...> o, Rest... rest) {
+    const auto bound = [&](auto... cs) { return f(IntC<V>(), cs...); };
+    if constexpr (sizeof...(Vs) == 0) return dispatch(bound, rest...);
+    else return o.v == V ? dispatch(bound, rest...) : dispatch(f, OneOf<Vs...>{o.v}, rest...);
+}
+static auto flag(bool on) { return one_of<1, 0>(on); }
+static auto metric_of(int metric) { return one_of<INNR_METRIC_COSINE, INNR_METRIC_L2SQ, INNR_METRIC_DOT>(metric); }
+// RR (R in the kernels) of a list capacity of 64 RR entries: the GEMM-type filters have lists of 32 / 64 / 128 / 256 candidates
+// (cand_cap: 384 / 512 / 768 / 1280 entries), the exact scans of 32 / 128 / 256 (exact_cap)
+static auto rr_gemm(uint32_t cap) { return one_of<6, 8, 12, 20>(cap / 64); }
+static auto rr_scan(uint32_t cap) { return one_of<6, 12, 20>(cap / 64); }
+
+// The score space of a proof: rescore_kernel's MET, seed_thresholds_kernel's and kmargin_kernel's kind.
+enum ScoreSpace : int { kSpaceDot = 0, kSpaceCos = 1, kSpaceL2 = 2, kSpaceEq = 3, kSpaceCode = 4 };
+static ScoreSpace metric_space(int metric) {
+    return metric == INNR_METRIC_L2SQ ? kSpaceL2 : (metric == INNR_METRIC_COSINE ? kSpaceCos : kSpaceDot);
+}
+// the template arguments of the exact kernels: MET of a metric's score space, RK (rounds of candidates) of lists of KP
+template <class F>
+static void with_space(ScoreSpace space, F&& f) {
+    if (space == kSpaceCos) f(IntC<kSpaceCos>());
+    else if (space == kSpaceL2) f(IntC<kSpaceL2>());
+    else f(IntC<kSpaceDot>());
+}
+template <class F>
+static void with_rk(uint32_t KP, F&& f) {
+    if (KP <= 64) f(IntC<1>());
+    else if (KP <= 128) f(IntC<2>());
+    else f(IntC<4>());
 }
 
 namespace innr {
@@ -582,55 +641,23 @@ struct ScanExt {
     uint32_t nvalid = 0xFFFFFFFFu;    // query slots of the launch beyond this one are padding (zero rows): nothing is admitted for them
 };
 
-template <int QB, int R>
-static innr_status launch_scan_filter_r(innr_batch* b, int metric, const float* dQ, size_t ldq, const float* dQn,
-                                        uint32_t nblocks, uint32_t qstride, uint32_t KP, uint32_t cps,
-                                        const ScanExt& ext, uint32_t groups) {
+// one launch of scan_filter_kernel: `groups` groups of qb (8, 4 or 1) queries. (The exact scans are not a recorded family: one runs
+// inside most recorded calls -- threshold seeding, the redo of unproven queries -- and the record's readers decode a closed set.)
+static innr_status launch_scan_filter(innr_batch* b, int metric, uint32_t qb, const float* dQ, size_t ldq, const float* dQn,
+                                      uint32_t nblocks, uint32_t qstride, uint32_t KP, uint32_t cap, uint32_t cps,
+                                      const ScanExt& ext, uint32_t groups) {
     innr_ctx* c = b->ctx;
-    uint64_t* lists = c->lists.as<uint64_t>();
-    uint32_t* counts = c->counts.as<uint32_t>();
-    uint32_t* err = c->flags.as<uint32_t>();
-    const uint32_t N = (uint32_t)b->N, D = (uint32_t)b->D;
-    switch (metric) {
-        case INNR_METRIC_DOT:
-            if (ext.mask)  // innr_batch_knn_filtered_multi
-                scan_filter_kernel<QB, false, false, R, true><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                    b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, ext.mask, nullptr, ext.nvalid);
-            else
-                scan_filter_kernel<QB, false, false, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                    b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
-            break;
-        case INNR_METRIC_L2SQ:
-            if (ext.mask || ext.order)
-                scan_filter_kernel<QB, true, false, R, true><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                    b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, ext.mask,
-                    ext.order, ext.nvalid);
-            else
-                scan_filter_kernel<QB, true, false, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                    b->V, b->ldN, N, D, dQ, ldq, nullptr, nullptr, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
-            break;
-        default:
-            if (ext.mask)
-                scan_filter_kernel<QB, false, true, R, true><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                    b->V, b->ldN, N, D, dQ, ldq, b->norms, dQn, lists, counts, qstride, KP, cps, err, ext.mask, nullptr, ext.nvalid);
-            else
-                scan_filter_kernel<QB, false, true, R><<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
-                    b->V, b->ldN, N, D, dQ, ldq, b->norms, dQn, lists, counts, qstride, KP, cps, err, nullptr, nullptr, ext.nvalid);
-            break;
-    }
+    const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
+    // the extended kernel: a mask (innr_batch_knn_filtered_multi, every metric) or a dimension order (squared L2 only)
+    const uint32_t* order = l2 ? ext.order : nullptr;
+    dispatch([&](auto QB, auto met, auto rr, auto extended) {
+        scan_filter_kernel<QB, met == INNR_METRIC_L2SQ, met == INNR_METRIC_COSINE, rr, extended != 0>
+            <<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
+                b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, dQ, ldq, cos ? b->norms : nullptr, cos ? dQn : nullptr, c->lists.as<uint64_t>(),
+                c->counts.as<uint32_t>(), qstride, KP, cps, c->flags.as<uint32_t>(), ext.mask, order, ext.nvalid);
+    }, one_of<8, 4, 1>(qb), metric_of(metric), rr_scan(cap), flag(ext.mask || order));
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
-}
-
-template <int QB>
-static innr_status launch_scan_filter(innr_batch* b, int metric, const float* dQ, size_t ldq, const float* dQn,
-                                      uint32_t nblocks, uint32_t qstride, uint32_t KP, uint32_t cap, uint32_t cps,
-                                      const ScanExt& ext, uint32_t groups = 1) {
-    switch (cap) {
-        case 384: return launch_scan_filter_r<QB, 6>(b, metric, dQ, ldq, dQn, nblocks, qstride, KP, cps, ext, groups);
-        case 768: return launch_scan_filter_r<QB, 12>(b, metric, dQ, ldq, dQn, nblocks, qstride, KP, cps, ext, groups);
-        default: return launch_scan_filter_r<QB, 20>(b, metric, dQ, ldq, dQn, nblocks, qstride, KP, cps, ext, groups);
-    }
 }
 
 // A ragged group of an exact scan: rows [nreal, nql) of *q (row stride ldq) are zero queries, with a zero per-query value (*aux,
@@ -716,11 +743,7 @@ static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* 
         if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qn));
         ScanExt ext2 = ext;
         if (nreal < nql) ext2.nvalid = nreal;
-        switch (qb) {
-            case 8: INNR_TRY(launch_scan_filter<8>(b, metric, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2, groups)); break;
-            case 4: INNR_TRY(launch_scan_filter<4>(b, metric, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2)); break;
-            default: INNR_TRY(launch_scan_filter<1>(b, metric, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2)); break;
-        }
+        INNR_TRY(launch_scan_filter(b, metric, qb, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2, groups));
         INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, l2, d_out_idx + (q0 + done) * kout,
                                  d_out_score + (q0 + done) * kout));
         done += nreal;
@@ -757,12 +780,6 @@ static innr_status prep_gthr(innr_ctx* c, size_t Qpad, uint32_t KP, const uint32
 // the final bounds of the last launch's queries (what the re-score proves against)
 static const uint32_t* gthr_bounds(const innr_ctx* c, size_t Qpad, uint32_t KP) { return c->gthr.as<uint32_t>() + Qpad * (size_t)kSlotMul * KP; }
 
-// The score space of a proof: rescore_kernel's MET, seed_thresholds_kernel's and kmargin_kernel's kind.
-enum ScoreSpace : int { kSpaceDot = 0, kSpaceCos = 1, kSpaceL2 = 2, kSpaceEq = 3, kSpaceCode = 4 };
-static ScoreSpace metric_space(int metric) {
-    return metric == INNR_METRIC_L2SQ ? kSpaceL2 : (metric == INNR_METRIC_COSINE ? kSpaceCos : kSpaceDot);
-}
-
 // E per query by kind -> the k rule's margin 2E (+ rounding room); +inf where E is not finite and for padding queries.
 // kind 0: err_scale * qnorm[j] (dot), 1: err_scale (cosine), 2: err_scale * aux[j] (squared L2 in score space, aux = C_j),
 // 3: eq[j] (int8 filter of an f32 corpus), 4: err_scale * qnorm[j] + 4.8e-7 |offset * qsum[j]| + eq[j] (code corpus; eq nullable)
@@ -797,20 +814,6 @@ static innr_status make_kmargin(innr_ctx* c, ScoreSpace kind, float err_scale, c
 }
 
 // ---- exact re-score + proof of the selected lists (c->sel [Q][KP], c->sel_cnt [Q]) ----
-// the template arguments of the exact kernels: MET of a metric's score space, RK (rounds of candidates) of lists of KP
-template <int N> using IntC = std::integral_constant<int, N>;
-template <class F>
-static void with_space(ScoreSpace space, F&& f) {
-    if (space == kSpaceCos) f(IntC<kSpaceCos>());
-    else if (space == kSpaceL2) f(IntC<kSpaceL2>());
-    else f(IntC<kSpaceDot>());
-}
-template <class F>
-static void with_rk(uint32_t KP, F&& f) {
-    if (KP <= 64) f(IntC<1>());
-    else if (KP <= 128) f(IntC<2>());
-    else f(IntC<4>());
-}
 // f32 corpus (rescore_kernel); qaux: C_j in the squared-L2 space, eq: per-query bounds instead of err_scale (int8 filter)
 static innr_status launch_rescore(innr_batch* b, ScoreSpace space, const float* dQ, size_t Q, const float* qaux, uint32_t KP,
                                   size_t kout, float err_scale, uint64_t* d_out_idx, float* d_out_score, uint32_t* fallback,
@@ -935,35 +938,21 @@ static innr_status launch_gemm(innr_batch* b, const GemmPlan& p, size_t nreal_q,
     size_t nslot = 0;
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, MODE == 2 ? 32u : p.KP, seed, nreal_q, kmargin, &gslots, &nslot));  // (MODE 2: only the bounds are used)
-#define INNR_GEMM_LAUNCH_W(RR, WV)                                                                               \
-    do {                                                                                                         \
-        log_launch(c, kLaunchGemmF32, KIND, RR, MODE, WV, p.nqt);                                                \
-        gemm_filter_kernel<KIND, RR, MODE, WV><<<p.nblocks, 64 * WV, 0, c->stream>>>(                              \
-            KIND == kGemmU8 ? (const void*)b->C8 : (const void*)b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->Dpad, Qt, p.Qpad, \
-            p.nqt, p.qtg, p.tps, invn, invq, b->alpha / 255.0f, lists, counts, p.KP, kk, err, gslots, gslots + nslot, dump, \
-            ld_dump);                                                                                            \
-    } while (0)
-    // the 8-, 2- and 1-wave tiles exist for the product path only (MODE 0; the narrow ones not for the u8 kind); the
-    // layout-dump hook stays on 4 waves
-#define INNR_GEMM_LAUNCH(RR)                                                                                    \
-    do {                                                                                                        \
-        if (MODE == 0 && p.waves == 8) INNR_GEMM_LAUNCH_W(RR, (MODE == 0 ? 8 : 4));                              \
-        else if (MODE == 0 && KIND != kGemmU8 && p.waves == 2) INNR_GEMM_LAUNCH_W(RR, ((MODE == 0 && KIND != kGemmU8) ? 2 : 4)); \
-        else if (MODE == 0 && KIND != kGemmU8 && p.waves == 1) INNR_GEMM_LAUNCH_W(RR, ((MODE == 0 && KIND != kGemmU8) ? 1 : 4)); \
-        else INNR_GEMM_LAUNCH_W(RR, 4);                                                                         \
-    } while (0)
-    if constexpr (MODE == 2) {  // collect (knn_complete): the list geometry plays no part; 8-wave tiles for the dot kind only
-        if (KIND == kGemmDot && p.waves == 8) INNR_GEMM_LAUNCH_W(6, ((MODE == 2 && KIND == kGemmDot) ? 8 : 4));
-        else INNR_GEMM_LAUNCH_W(6, 4);
-    } else
-    switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
-        case 384: INNR_GEMM_LAUNCH(6); break;
-        case 512: INNR_GEMM_LAUNCH(8); break;
-        case 768: INNR_GEMM_LAUNCH(12); break;
-        default: INNR_GEMM_LAUNCH(20); break;
-    }
-#undef INNR_GEMM_LAUNCH
-#undef INNR_GEMM_LAUNCH_W
+    const auto launch = [&](auto rr, auto wv) {
+        launch_kernel(c, Inst<kLaunchGemmF32, KIND, rr, MODE, wv>(), {p.nblocks, 64 * wv, 0, p.nqt},
+                      KIND == kGemmU8 ? (const void*)b->C8 : (const void*)b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->Dpad, Qt, p.Qpad, p.nqt,
+                      p.qtg, p.tps, invn, invq, b->alpha / 255.0f, lists, counts, p.KP, kk, err, gslots, gslots + nslot, dump, ld_dump);
+    };
+    // The 2- and 1-wave tiles exist for the product path (MODE 0) of the f32 kinds only, the 8-wave tile for the product path and
+    // for the dot kind's collect pass (knn_complete); everything else, the layout-dump hook included, stays on 4 waves.
+    const auto pick = [&](auto rr, auto wv) {
+        constexpr bool exists = wv == 4 || (wv == 8 ? (MODE == 0 || (MODE == 2 && KIND == kGemmDot)) : (MODE == 0 && KIND != kGemmU8));
+        if constexpr (exists) launch(rr, wv);
+        else launch(rr, IntC<4>());
+    };
+    // (every instantiation has a row in tests/test_gpu_kernel_variants.py: GEMM_F32)
+    if constexpr (MODE == 0) dispatch(pick, rr_gemm(p.cap), one_of<8, 2, 1, 4>(p.waves));
+    else dispatch([&](auto wv) { pick(IntC<6>(), wv); }, one_of<8, 4>(p.waves));  // collect, dump: lists of 32 at most (RR 6), no narrow tiles
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
@@ -1515,18 +1504,15 @@ static innr_status launch_gemm_bf16(innr_batch* b, const GemmPlan& p, size_t nre
     size_t nslot = 0;
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
-#define INNR_BF16_LAUNCH(RR)                                                                                              \
-    log_launch(c, kLaunchGemmBf16, RR, 0, 1, 0, p.nqt);                                                                   \
-    gemm_bf16_filter_kernel<RR, 0, 1><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                          \
-        cc.p, nullptr, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N, cc.nk, p.Qpad, p.nqt, p.qtg, p.tps,  \
-        c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, nullptr, 0)
-    switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
-        case 384: INNR_BF16_LAUNCH(6); break;
-        case 512: INNR_BF16_LAUNCH(8); break;
-        case 768: INNR_BF16_LAUNCH(12); break;
-        default: INNR_BF16_LAUNCH(20); break;
+    if (p.cap < 768) {  // choose_f32_filter: lists of pick_kp(4k + 64), 128 or 256 candidates
+        set_error("internal: the bf16 filter has no lists of %u candidates", p.KP);
+        return INNR_E_BAD_ARG;
     }
-#undef INNR_BF16_LAUNCH
+    dispatch([&](auto rr) {  // (every instantiation has a row in tests/test_gpu_kernel_variants.py: GEMM_BF16)
+        launch_kernel(c, Inst<kLaunchGemmBf16, rr, 0, 1>(), {p.nblocks, 64 * kBfWaves, 0, p.nqt}, cc.p, nullptr, c->q_bf16.as<char>(),
+                      (uint32_t)(b->ldN / 128), (uint32_t)b->N, cc.nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(),
+                      c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, nullptr, 0);
+    }, one_of<12, 20>(p.cap / 64));
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
@@ -1602,23 +1588,13 @@ static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nr
     size_t nslot = 0;
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
-#define INNR_SPLIT_LAUNCH(RR)                                                                                             \
-    log_launch(c, kLaunchGemmSplit, RR, MODE, 3, 0, p.nqt);                                                               \
-    gemm_bf16_filter_kernel<RR, MODE, 3><<<p.nblocks, 64 * kBfWaves, 0, c->stream>>>(                                      \
-        hi.p, lo.p, c->q_bf16.as<char>(), (uint32_t)(b->ldN / 128), (uint32_t)b->N,                                       \
-        hi.nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk,                  \
-        c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump)
-    if constexpr (MODE == 1) {  // the dense-score dump: the list geometry plays no part
-        INNR_SPLIT_LAUNCH(6);
-    } else {
-        switch (p.cap) {  // (launches are recorded for tests/test_gpu_kernel_variants.py; this family has no table there yet)
-            case 384: INNR_SPLIT_LAUNCH(6); break;
-            case 512: INNR_SPLIT_LAUNCH(8); break;
-            case 768: INNR_SPLIT_LAUNCH(12); break;
-            default: INNR_SPLIT_LAUNCH(20); break;
-        }
-    }
-#undef INNR_SPLIT_LAUNCH
+    const auto launch = [&](auto rr) {
+        launch_kernel(c, Inst<kLaunchGemmSplit, rr, MODE, 3>(), {p.nblocks, 64 * kBfWaves, 0, p.nqt}, hi.p, lo.p, c->q_bf16.as<char>(),
+                      (uint32_t)(b->ldN / 128), (uint32_t)b->N, hi.nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(),
+                      c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump);
+    };
+    if constexpr (MODE == 1) launch(IntC<6>());  // the dense-score dump: the list geometry plays no part
+    else dispatch(launch, rr_gemm(p.cap));       // (every instantiation has a row in tests/test_gpu_kernel_variants.py: GEMM_SPLIT)
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
@@ -2101,7 +2077,7 @@ innr_status innrdbg_gemm_scores(innr_batch* b, int metric, const float* queries,
     innr_ctx* c = b->ctx;
     INNR_ENTER(c);
     const bool cos = metric == INNR_METRIC_COSINE;
-    const GemmPlan p = plan_gemm(b, Q, 1, /*waves=*/4);
+    const GemmPlan p = plan_gemm(b, Q, 1, /*waves=*/4);  // (k = 1: lists of 32, the RR 6 that launch_gemm pins for MODE 1)
     INNR_TRY(ensure_norms(b));
     if (cos) INNR_TRY(ensure_invnorms(b));
     INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
@@ -2917,23 +2893,16 @@ innr_status innr_batch_scores_u8(innr_batch* b, const float* q, size_t D, float*
     return INNR_OK;
 }
 
-template <int QB>
-static innr_status launch_scan_u8(innr_batch* b, const float* dQ, size_t ldq, const float* qsum, uint32_t nblocks,
-                                  uint32_t KP, uint32_t cap, uint32_t cps, uint32_t groups = 1, size_t limit_n = 0,
-                                  uint32_t nvalid_q = 0xFFFFFFFFu) {
+static innr_status launch_scan_u8(innr_batch* b, uint32_t qb, const float* dQ, size_t ldq, const float* qsum, uint32_t nblocks,
+                                  uint32_t KP, uint32_t cap, uint32_t cps, uint32_t groups, size_t limit_n, uint32_t nvalid_q) {
     innr_ctx* c = b->ctx;
     const uint32_t nvalid = (uint32_t)((limit_n && limit_n < b->N) ? limit_n : b->N);
     const float a255 = b->alpha / 255.0f;  // scalar.rs:299 (params.alpha / 255.0), f32
-#define INNR_U8_LAUNCH(RR)                                                                                          \
-    scan_u8_filter_kernel<QB, RR><<<dim3(nblocks, groups), 256, 0, c->stream>>>(                                    \
-        b->C8, b->ldN, nvalid, (uint32_t)b->D, dQ, ldq, qsum, a255, b->offset, c->lists.as<uint64_t>(),              \
-        c->counts.as<uint32_t>(), QB * groups, KP, cps, c->flags.as<uint32_t>(), nvalid_q)
-    switch (cap) {
-        case 384: INNR_U8_LAUNCH(6); break;
-        case 768: INNR_U8_LAUNCH(12); break;
-        default: INNR_U8_LAUNCH(20); break;
-    }
-#undef INNR_U8_LAUNCH
+    dispatch([&](auto QB, auto rr) {
+        scan_u8_filter_kernel<QB, rr><<<dim3(nblocks, groups), 256, 0, c->stream>>>(
+            b->C8, b->ldN, nvalid, (uint32_t)b->D, dQ, ldq, qsum, a255, b->offset, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(),
+            QB * groups, KP, cps, c->flags.as<uint32_t>(), nvalid_q);
+    }, one_of<8, 4, 1>(qb), rr_scan(cap));
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
@@ -2970,9 +2939,7 @@ static innr_status knn_u8_exact_range(innr_batch* b, const float* dQ, size_t ldq
         const float* q = dQ + (q0 + done) * ldq;
         const float* qs = qsum + q0 + done;
         if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qs));
-        if (qb == 8) INNR_TRY(launch_scan_u8<8>(b, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu));
-        else if (qb == 4) INNR_TRY(launch_scan_u8<4>(b, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu));
-        else INNR_TRY(launch_scan_u8<1>(b, q, ldq, qs, nblocks, KP, cap, cps, 1, limit_n));
+        INNR_TRY(launch_scan_u8(b, qb, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu));
         INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, false, d_out_idx + (q0 + done) * kout,
                                  d_out_score + (q0 + done) * kout));
         done += nreal;
@@ -3142,18 +3109,11 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
     size_t nslot = 0;
     if (!kmargin) kk = 0;
     INNR_TRY(prep_gthr(c, p.Qpad, MODE == 2 ? 32u : p.KP, seed, nreal_q, kmargin, &gslots, &nslot));  // (MODE 2: only the bounds are used)
-    const bool two = p.two;
-#define INNR_I8_ARGS                                                                                                      \
-    p.corpus, c->q_bf16.as<char>(), p.ntiles, (uint32_t)b->N, p.nk, p.Qpad, p.nqt, p.qtg, p.tps, qc, c->lists.as<uint64_t>(), \
-        c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump
-#define INNR_I8_LAUNCH(RR)                                                                                                \
-    do {                                                                                                                  \
-        log_launch(c, two ? kLaunchI8Two : kLaunchI8One, RR, MODE, 0, 0, p.nqt);                                          \
-        if (two) gemm_i8_filter_kernel<RR, MODE><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);                  \
-        else gemm_i8h_filter_kernel<RR, MODE><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);                     \
-    } while (0)
     if (p.small) {
-        if constexpr (MODE == 0 || MODE == 2) {
+        if constexpr (MODE == 1) {
+            set_error("internal: the small-batch int8 kernel has no mode %d", MODE);
+            return INNR_E_BAD_ARG;
+        } else {
             const size_t dyn = i8s_dyn_lds_bytes(p.nk, p.small_ct);
             uint32_t* prog = nullptr;
             if (p.nqt > 1 && !c->tune.i8_small_free) {
@@ -3161,60 +3121,43 @@ static innr_status launch_gemm_i8(innr_batch* b, const I8Plan& p, size_t nreal_q
                 INNR_HIP_CHECK(hipMemsetAsync(c->i8s_prog.p, 0, (size_t)p.nslices * p.nqt * sizeof(uint32_t), c->stream));
                 prog = c->i8s_prog.as<uint32_t>();
             }
-#define INNR_I8S_LAUNCH(NKV, CTV)                                                                                                    \
-    do {                                                                                                                            \
-        if (dyn > 48 * 1024) /* (per device and call: no process-wide state) */                                                      \
-            INNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_i8s_filter_kernel<12, NKV, CTV, MODE>),           \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)i8s_dyn_lds_bytes(NKV, CTV)));      \
-        log_launch(c, kLaunchI8Small, NKV, CTV, MODE, 0, p.nqt, prog != nullptr);                                                   \
-        gemm_i8s_filter_kernel<12, NKV, CTV, MODE><<<p.nblocks, 64 * kI8sWaves, dyn, c->stream>>>(                                   \
-            p.corpus, c->q_bf16.as<char>(), 4 * p.ntiles, (uint32_t)b->N, p.Qpad, p.nqt, p.tps, qc, c->lists.as<uint64_t>(),          \
-            c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, prog);                             \
-    } while (0)
-            // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: I8_SMALL)
-            if (p.small_ct == 4) {
-                switch (p.nk) {  // (plan_i8_small: even, 8 .. 16)
-                    case 8: INNR_I8S_LAUNCH(8, 4); break;
-                    case 10: INNR_I8S_LAUNCH(10, 4); break;
-                    case 12: INNR_I8S_LAUNCH(12, 4); break;
-                    case 14: INNR_I8S_LAUNCH(14, 4); break;
-                    default: INNR_I8S_LAUNCH(16, 4); break;
+            // (plan_i8_small: K-steps even and <= 16, lists of 128 = capacity 768 = R 12; four column tiles from 8 K-steps on. Every
+            // instantiation has a row in tests/test_gpu_kernel_variants.py: I8_SMALL)
+            INNR_TRY(dispatch([&](auto ct, auto nk) -> innr_status {
+                if constexpr (ct == 4 && nk < 8) {
+                    set_error("internal: the small-batch int8 kernel has no four-tile form of %d K-steps", (int)nk);
+                    return INNR_E_BAD_ARG;
+                } else {
+                    constexpr auto inst = Inst<kLaunchI8Small, nk, ct, MODE>();
+                    if (dyn > 48 * 1024) /* (per device and call: no process-wide state) */
+                        INNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(inst)),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)i8s_dyn_lds_bytes(nk, ct)));
+                    launch_kernel(c, inst, {p.nblocks, 64 * kI8sWaves, dyn, p.nqt, prog != nullptr}, p.corpus, c->q_bf16.as<char>(),
+                                  4 * p.ntiles, (uint32_t)b->N, p.Qpad, p.nqt, p.tps, qc, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(),
+                                  p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, prog);
+                    return INNR_OK;
                 }
-            } else {
-                switch (p.nk) {  // (plan_i8_small: even, <= 16, lists of 128 = capacity 768 = R 12)
-                    case 2: INNR_I8S_LAUNCH(2, 2); break;
-                    case 4: INNR_I8S_LAUNCH(4, 2); break;
-                    case 6: INNR_I8S_LAUNCH(6, 2); break;
-                    case 8: INNR_I8S_LAUNCH(8, 2); break;
-                    case 10: INNR_I8S_LAUNCH(10, 2); break;
-                    case 12: INNR_I8S_LAUNCH(12, 2); break;
-                    case 14: INNR_I8S_LAUNCH(14, 2); break;
-                    default: INNR_I8S_LAUNCH(16, 2); break;
-                }
-            }
-#undef INNR_I8S_LAUNCH
-        } else {
-            set_error("internal: the small-batch int8 kernel has no mode %d", MODE);
-            return INNR_E_BAD_ARG;
+            }, one_of<4, 2>(p.small_ct), one_of<2, 4, 6, 8, 10, 12, 14, 16>(p.nk)));
         }
-    } else if constexpr (MODE == 1) {
-        INNR_I8_LAUNCH(6);
-    } else if constexpr (MODE == 2) {  // collect (the completion pass): one-limb kernel, the list geometry plays no part
-        log_launch(c, kLaunchI8One, 6, 2, 0, 0, p.nqt);
-        gemm_i8h_filter_kernel<6, 2><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);
     } else {
-        switch (p.cap) {  // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: I8_TILES)
-            case 384: INNR_I8_LAUNCH(6); break;
-            case 512: INNR_I8_LAUNCH(8); break;
-            case 768: INNR_I8_LAUNCH(12); break;
-            default:  // lists of 256 candidates: the two-limb kernel only (plan_i8)
-                log_launch(c, kLaunchI8Two, 20, MODE, 0, 0, p.nqt);
-                gemm_i8_filter_kernel<20, MODE><<<p.nblocks, 64 * kI8Waves, 0, c->stream>>>(INNR_I8_ARGS);
-                break;
+        // the 512-query one-limb tile (gemm_i8h_filter_kernel) or the 256-query two-limb tile (gemm_i8_filter_kernel): one argument list
+        const auto tile = [&](auto family, auto rr) {
+            launch_kernel(c, Inst<family, rr, MODE>(), {p.nblocks, 64 * kI8Waves, 0, p.nqt}, p.corpus, c->q_bf16.as<char>(), p.ntiles,
+                          (uint32_t)b->N, p.nk, p.Qpad, p.nqt, p.qtg, p.tps, qc, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, kk,
+                          c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump);
+        };
+        const auto limbs = one_of<kLaunchI8Two, kLaunchI8One>(p.two ? kLaunchI8Two : kLaunchI8One);
+        if constexpr (MODE == 2) {  // collect (the completion pass): one-limb kernel, the list geometry plays no part
+            tile(IntC<kLaunchI8One>(), IntC<6>());
+        } else if constexpr (MODE == 1) {  // the dense-score dump: the list geometry plays no part
+            dispatch([&](auto family) { tile(family, IntC<6>()); }, limbs);
+        } else {  // (every instantiation has a row in tests/test_gpu_kernel_variants.py: I8_TILES)
+            dispatch([&](auto family, auto rr) {
+                if constexpr (rr == 20) tile(IntC<kLaunchI8Two>(), rr);  // lists of 256 candidates: the two-limb kernel only (plan_i8)
+                else tile(family, rr);
+            }, limbs, rr_gemm(p.cap));
         }
     }
-#undef INNR_I8_LAUNCH
-#undef INNR_I8_ARGS
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
@@ -3767,28 +3710,14 @@ static innr_status maxsim_scan_exact(innr_docs* d, int cosine, size_t Tq, const 
         const float* qp = c->q_row.as<float>() + p0 * dim;
         const float* aa = c->q_norm.as<float>() + p0;
         if (cosine) sqrt_kernel<<<1, kMsQ, 0, c->stream>>>(aa, nq, saa);
-#define INNR_MS_LAUNCH(COSV, NQV)                                                                                       \
-    do {                                                                                                                \
-        const unsigned npk = (unsigned)(dim / 4) * NQV * 4;                                                             \
-        if (npk)                                                                                                        \
-            maxsim_pack_query_kernel<<<(npk + 255) / 256, 256, 0, c->stream>>>(qp, NQV, (uint32_t)dim, qpk);            \
-        log_launch(c, kLaunchMsScan, COSV, NQV, d->T > 64);                                                             \
-        if (d->T > 64)                                                                                                  \
-            maxsim_scan_kernel<COSV, NQV, true><<<blocks, kMsThreads, 0, c->stream>>>(                                  \
-                d->tok, d->doc_len, (uint32_t)nslots, (uint32_t)d->T, Tp, (uint32_t)dim, qp, qpk, nq,                   \
-                COSV ? aa : nullptr, out, out, p0 == 0, doc_ids, COSV ? saa : nullptr);                                 \
-        else                                                                                                            \
-            maxsim_scan_kernel<COSV, NQV, false><<<blocks, kMsThreads, 0, c->stream>>>(                                 \
-                d->tok, d->doc_len, (uint32_t)nslots, (uint32_t)d->T, Tp, (uint32_t)dim, qp, qpk, nq,                   \
-                COSV ? aa : nullptr, out, out, p0 == 0, doc_ids, COSV ? saa : nullptr);                                 \
-    } while (0)
-        // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: MS_SCAN)
-        if (cosine) {
-            if (nq <= 8) INNR_MS_LAUNCH(true, 8); else if (nq <= 16) INNR_MS_LAUNCH(true, 16); else INNR_MS_LAUNCH(true, 32);
-        } else {
-            if (nq <= 8) INNR_MS_LAUNCH(false, 8); else if (nq <= 16) INNR_MS_LAUNCH(false, 16); else INNR_MS_LAUNCH(false, 32);
-        }
-#undef INNR_MS_LAUNCH
+        // (every instantiation has a row in tests/test_gpu_kernel_variants.py: MS_SCAN)
+        dispatch([&](auto cosv, auto nqv, auto multi) {
+            const unsigned npk = (unsigned)(dim / 4) * nqv * 4;
+            if (npk) maxsim_pack_query_kernel<<<(npk + 255) / 256, 256, 0, c->stream>>>(qp, (uint32_t)nqv, (uint32_t)dim, qpk);
+            launch_kernel(c, Inst<kLaunchMsScan, cosv, nqv, multi>(), {blocks, kMsThreads}, d->tok, d->doc_len, (uint32_t)nslots,
+                          (uint32_t)d->T, Tp, (uint32_t)dim, qp, qpk, nq, cosine ? aa : nullptr, out, out, p0 == 0, doc_ids,
+                          cosine ? saa : nullptr);
+        }, flag(cosine), one_of<8, 16, 32>(nq <= 8 ? 8 : (nq <= 16 ? 16 : 32)), flag(d->T > 64));
         INNR_HIP_CHECK(hipGetLastError());
     }
     return INNR_OK;
@@ -3936,41 +3865,23 @@ static innr_status maxsim_approx(innr_docs* d, int cosine, const float* const* q
         }
         INNR_HIP_CHECK(copy_in(c, nq_dev + 4 * (p0 / kMsQ), nq_host, sizeof(nq_host)));
         const uint32_t* nqp = nq_dev + 4 * (p0 / kMsQ);
-#define INNR_MS_TILE(COSV, NBV, NQV)                                                                                    \
-    log_launch(c, kLaunchMsTile, COSV, NBV, NQV, 0, (uint32_t)nqr);                                                     \
-    maxsim_mfma_tile_kernel<COSV, NBV, NQV><<<blocks, kMsThreads, lds, c->stream>>>(                                     \
-        d->tok, d->doc_len, COSV ? d->tok_inv : nullptr, (uint32_t)d->ndocs, (uint32_t)d->T, qB, nqp,                     \
-        COSV ? qscale + p0 : nullptr, approx, approx, p0 == 0)
-#define INNR_MS_TILE_NB(COSV, NQV)                                                                                      \
-    switch (dim / 32) {                                                                                                 \
-        case 1: INNR_MS_TILE(COSV, 1, NQV); break;                                                                      \
-        case 2: INNR_MS_TILE(COSV, 2, NQV); break;                                                                      \
-        case 3: INNR_MS_TILE(COSV, 3, NQV); break;                                                                      \
-        default: INNR_MS_TILE(COSV, 4, NQV); break;                                                                     \
-    }
-        // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: MS_TILE, MS_GENERIC)
-        if (tiled && nqr == 4) {
-            if (cosine) { INNR_MS_TILE_NB(true, 4) } else { INNR_MS_TILE_NB(false, 4) }
-        } else if (tiled && nqr == 2) {
-            if (cosine) { INNR_MS_TILE_NB(true, 2) } else { INNR_MS_TILE_NB(false, 2) }
-        } else if (tiled) {
-            if (cosine) { INNR_MS_TILE_NB(true, 1) } else { INNR_MS_TILE_NB(false, 1) }
+        const float* tok_inv = cosine ? d->tok_inv : nullptr;
+        const float* qsc = cosine ? qscale + p0 : nullptr;
+        // (every instantiation has a row in tests/test_gpu_kernel_variants.py: MS_TILE, MS_GENERIC)
+        if (tiled) {  // NB = dim / 32 K-blocks; four, two or one query a pass
+            dispatch([&](auto cosv, auto nb, auto nqv) {
+                launch_kernel(c, Inst<kLaunchMsTile, cosv, nb, nqv>(), {blocks, kMsThreads, lds, (uint32_t)nqr}, d->tok, d->doc_len, tok_inv,
+                              (uint32_t)d->ndocs, (uint32_t)d->T, qB, nqp, qsc, approx, approx, p0 == 0);
+            }, flag(cosine), one_of<1, 2, 3, 4>(dim / 32), one_of<4, 2, 1>(nqr));
         } else if (nqr != 1) {
             set_error("internal: multi-query maxsim needs the tile-unrolled kernel");
             return INNR_E_UNSUPPORTED;
-        } else if (cosine) {
-            log_launch(c, kLaunchMsGeneric, 1);
-            maxsim_mfma_kernel<true><<<blocks, kMsThreads, lds, c->stream>>>(d->tok, d->doc_len, d->tok_inv, (uint32_t)d->ndocs,
-                                                                             (uint32_t)d->T, (uint32_t)dim, qB, nq_host[0],
-                                                                             qscale + p0, approx, approx, p0 == 0);
         } else {
-            log_launch(c, kLaunchMsGeneric, 0);
-            maxsim_mfma_kernel<false><<<blocks, kMsThreads, lds, c->stream>>>(d->tok, d->doc_len, nullptr, (uint32_t)d->ndocs,
-                                                                              (uint32_t)d->T, (uint32_t)dim, qB, nq_host[0],
-                                                                              nullptr, approx, approx, p0 == 0);
+            dispatch([&](auto cosv) {
+                launch_kernel(c, Inst<kLaunchMsGeneric, cosv>(), {blocks, kMsThreads, lds}, d->tok, d->doc_len, tok_inv, (uint32_t)d->ndocs,
+                              (uint32_t)d->T, (uint32_t)dim, qB, nq_host[0], qsc, approx, approx, p0 == 0);
+            }, flag(cosine));
         }
-#undef INNR_MS_TILE_NB
-#undef INNR_MS_TILE
         INNR_HIP_CHECK(hipGetLastError());
     }
     return INNR_OK;
@@ -4279,27 +4190,12 @@ innr_status innr_maxsim_rerank_dev(innr_docs* d, int cosine, const float* d_qtok
     float* partial = c->scores.as<float>();
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     for (size_t pass = 0; pass < npass; ++pass) {
-#define INNR_MS_RERANK(COSV, NQV, MULTIV)                                                                                \
-    log_launch(c, kLaunchMsRerank, COSV, NQV, MULTIV, 0, (uint32_t)Q);                                                   \
-    maxsim_rerank_kernel<COSV, NQV, MULTIV><<<blocks, kMsThreads, 0, c->stream>>>(                                       \
-        d->tok, d->doc_len, (uint32_t)d->ndocs, (uint32_t)d->T, Tp, (uint32_t)dim, d_qtoks, (uint32_t)Tq_stride, d_tq, qpk, \
-        (uint32_t)npass, (uint32_t)pass, aa, saa, d_cand, (uint32_t)Q, (uint32_t)kc, d->index_base, partial, keys, bad)
-#define INNR_MS_RERANK_NQ(COSV, MULTIV)                                       \
-    do {                                                                      \
-        switch (ms_pass_nq((uint32_t)tq_max, (uint32_t)pass)) {               \
-            case 8: INNR_MS_RERANK(COSV, 8, MULTIV); break;                   \
-            case 16: INNR_MS_RERANK(COSV, 16, MULTIV); break;                 \
-            default: INNR_MS_RERANK(COSV, 32, MULTIV); break;                 \
-        }                                                                     \
-    } while (0)
-        // (every instantiation below has a row in tests/test_gpu_kernel_variants.py: MS_RERANK)
-        if (cosine) {
-            if (d->T > 64) INNR_MS_RERANK_NQ(true, true); else INNR_MS_RERANK_NQ(true, false);
-        } else {
-            if (d->T > 64) INNR_MS_RERANK_NQ(false, true); else INNR_MS_RERANK_NQ(false, false);
-        }
-#undef INNR_MS_RERANK_NQ
-#undef INNR_MS_RERANK
+        // (every instantiation has a row in tests/test_gpu_kernel_variants.py: MS_RERANK)
+        dispatch([&](auto cosv, auto nqv, auto multi) {
+            launch_kernel(c, Inst<kLaunchMsRerank, cosv, nqv, multi>(), {blocks, kMsThreads, 0, (uint32_t)Q}, d->tok, d->doc_len,
+                          (uint32_t)d->ndocs, (uint32_t)d->T, Tp, (uint32_t)dim, d_qtoks, (uint32_t)Tq_stride, d_tq, qpk, (uint32_t)npass,
+                          (uint32_t)pass, aa, saa, d_cand, (uint32_t)Q, (uint32_t)kc, d->index_base, partial, keys, bad);
+        }, flag(cosine), one_of<8, 16, 32>(ms_pass_nq((uint32_t)tq_max, (uint32_t)pass)), flag(d->T > 64));
         INNR_HIP_CHECK(hipGetLastError());
     }
     INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
@@ -4965,31 +4861,22 @@ struct RangeScan {  // one launch of range_scan_kernel: nq queries (row-major, s
     uint64_t cap;
 };
 
-template <int QB, bool EMIT>
-static innr_status launch_range_scan_qb(innr_batch* b, int metric, const RangeScan& a) {
-    innr_ctx* c = b->ctx;
-    const size_t nchunks = b->ldN / kScanChunk;
-    // waves per CU as the exact kNN scan (knn_exact_range): 16 for eight queries a pass, 24 below
-    const unsigned bx = (unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * (QB == 8 ? 4 : 6));
-    const dim3 grid(bx, (a.nq + QB - 1) / QB);
-    log_launch(c, kLaunchRangeScan, QB, metric, EMIT ? 1 : 0, 0, grid.y);
-#define INNR_RANGE_LAUNCH(L2, COS)                                                                                              \
-    range_scan_kernel<QB, L2, COS, EMIT><<<grid, kScanThreads, 0, c->stream>>>(                                                 \
-        b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, a.Q, b->D, b->norms, a.qnorm, a.thr, a.qmap, a.nq, a.cnt, a.ldc, a.qoff, \
-        b->index_base, a.out_idx, a.out_score, a.cap)
-    if (metric == INNR_METRIC_COSINE) INNR_RANGE_LAUNCH(false, true);
-    else if (metric == INNR_METRIC_L2SQ) INNR_RANGE_LAUNCH(true, false);
-    else INNR_RANGE_LAUNCH(false, false);
-#undef INNR_RANGE_LAUNCH
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
-}
 // eight, four or one query per corpus pass, never more than there are queries (the kernel's last group ends on the last query)
 template <bool EMIT>
 static innr_status launch_range_scan(innr_batch* b, int metric, const RangeScan& a) {
-    if (a.nq >= 8) return launch_range_scan_qb<8, EMIT>(b, metric, a);
-    if (a.nq >= 4) return launch_range_scan_qb<4, EMIT>(b, metric, a);
-    return launch_range_scan_qb<1, EMIT>(b, metric, a);
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kScanChunk;
+    const uint32_t qb = a.nq >= 8 ? 8 : (a.nq >= 4 ? 4 : 1);
+    // waves per CU as the exact kNN scan (knn_exact_range): 16 for eight queries a pass, 24 below
+    const unsigned bx = (unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * (qb == 8 ? 4 : 6));
+    const dim3 grid(bx, (a.nq + qb - 1) / qb);
+    dispatch([&](auto QB, auto met) {
+        launch_kernel(c, Inst<kLaunchRangeScan, QB, met, EMIT>(), {grid, kScanThreads, 0, grid.y}, b->V, b->ldN, (uint32_t)b->N,
+                      (uint32_t)b->D, a.Q, b->D, b->norms, a.qnorm, a.thr, a.qmap, a.nq, a.cnt, a.ldc, a.qoff, b->index_base, a.out_idx,
+                      a.out_score, a.cap);
+    }, one_of<8, 4, 1>(qb), metric_of(metric));
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
 }
 
 static innr_status range_search_dev(innr_batch* b, int metric, const float* dQ, size_t Q, const float* dThr, int engine,

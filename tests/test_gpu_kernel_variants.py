@@ -1,12 +1,13 @@
-"""GPU tests of the kernel INSTANTIATIONS behind the int8 filter and the maxsim entry points: one case per instantiation a public
-call can reach. Every case (1) compares the call's answer with the CPU oracle bit for bit and (2) asserts, through the context's
+"""GPU tests of the kernel INSTANTIATIONS behind the f32 / bf16 / split-bf16 GEMM filters, the int8 filter and the maxsim entry
+points: one case per instantiation a public call (or, for the dense-score dump mode, a hook of the test-hooks library) can reach.
+Every case (1) compares the call's answer with the CPU oracle bit for bit and (2) asserts, through the context's
 launch record (api.hip: innr_ctx::launch_log, written at every templated dispatch, read by the hook innrdbg_launch_log of the
 test-hooks library), that the instantiation it is named after really served the call -- a dispatch that silently declines (an
 unseeded corpus, a K-step count without an instantiation, ...) fails the case instead of passing on another kernel's answer.
 
-The table (I8_SMALL, I8_TILES, MS_SCAN, MS_TILE, MS_GENERIC, MS_RERANK) names every instantiation of those families; the last test
-of the file checks that nothing outside it was launched by any case here, so a new instantiation cannot appear without a row.
-The f32 / bf16 / split-bf16 GEMM families are recorded as well but have no table yet."""
+The table (GEMM_F32, GEMM_BF16, GEMM_SPLIT, I8_SMALL, I8_TILES, MS_SCAN, MS_TILE, MS_GENERIC, MS_RERANK) names every instantiation of
+those families; the last test of the file checks that nothing outside it was launched by any case here, so a new instantiation
+cannot appear without a row. The range scan is recorded as well (and decoded) but has no table."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +22,8 @@ pytestmark = pytest.mark.gpu
 import oracle
 from test_gpu_exact import _corpus, _queries, bits_equal, same_knn
 from test_gpu_maxsim import _oracle_scores, _tokens
+from test_gpu_mfma import _dense_scores
+from test_gpu_split_filter import _split_scores
 from test_gpu_maxsim_rerank import PairOracle, _check as _check_rerank, _rank
 
 
@@ -35,7 +38,7 @@ def _oracle_knn_u8(q, codes, alpha, offset, k):
 
 # ------------------------------------------------------------------------------- the launch record
 FAMILIES = {1: "gemm_f32", 2: "gemm_bf16", 3: "gemm_split", 4: "i8_one", 5: "i8_two", 6: "i8_small", 7: "ms_scan", 8: "ms_tile",
-            9: "ms_generic", 10: "ms_rerank"}  # api.hip LaunchFamily
+            9: "ms_generic", 10: "ms_rerank", 11: "range_scan"}  # api.hip LaunchFamily
 _REC = np.dtype({"names": ["family", "lockstep", "arg", "groups"], "formats": ["u1", "u1", ("<i2", (4,)), "<u4"],
                  "offsets": [0, 1, 2, 12], "itemsize": 16})  # api.hip LaunchRec (the C layout: groups aligned to 4 bytes)
 LOG_CAP = 64  # api.hip kLaunchLogCap
@@ -53,7 +56,7 @@ class Launch(NamedTuple):
 
 
 _NARGS = {"gemm_f32": 4, "gemm_bf16": 3, "gemm_split": 3, "i8_one": 2, "i8_two": 2, "i8_small": 3, "ms_scan": 3, "ms_tile": 3,
-          "ms_generic": 1, "ms_rerank": 3}
+          "ms_generic": 1, "ms_rerank": 3, "range_scan": 3}
 
 
 def _hook():
@@ -89,6 +92,14 @@ def logged(call):
 
 
 # ------------------------------------------------------------------------------- the table
+DOT, COS, U8, L2 = 0, 1, 2, 3  # kernels_gemm.h kGemmDot / kGemmCos / kGemmU8 / kGemmL2
+RR_OF_K = {10: 6, 40: 8, 100: 12, 200: 20}  # lists of pick_kp(k, 16) = 32 / 64 / 128 / 256 candidates: capacity 64 RR
+GEMM_F32 = [("gemm_f32", kind, rr, 0, wv) for kind in (DOT, COS, L2) for rr in (6, 8, 12, 20) for wv in (1, 2, 4, 8)] + \
+           [("gemm_f32", U8, rr, 0, wv) for rr in (6, 8, 12, 20) for wv in (4, 8)] + \
+           [("gemm_f32", kind, 6, 2, 4) for kind in (DOT, COS, L2)] + [("gemm_f32", DOT, 6, 2, 8)] + \
+           [("gemm_f32", kind, 6, 1, 4) for kind in (DOT, COS)]                                # gemm_filter_kernel<KIND, RR, MODE, WV>
+GEMM_BF16 = [("gemm_bf16", rr, 0, 1) for rr in (12, 20)]                                     # gemm_bf16_filter_kernel<RR, 0, 1>
+GEMM_SPLIT = [("gemm_split", rr, 0, 3) for rr in (6, 8, 12, 20)] + [("gemm_split", 6, 1, 3)]  # gemm_bf16_filter_kernel<RR, MODE, 3>
 I8_SMALL = [("i8_small", nk, ct, mode) for mode in (0, 2) for nk, ct in
             [(nk, 2) for nk in range(2, 17, 2)] + [(nk, 4) for nk in range(8, 17, 2)]]          # gemm_i8s_filter_kernel<12, NK, CT, MODE>
 I8_TILES = [("i8_one", rr, 0) for rr in (6, 8, 12)] + [("i8_one", 6, 2)] + \
@@ -97,7 +108,7 @@ MS_SCAN = [("ms_scan", c, nq, m) for c in (0, 1) for nq in (8, 16, 32) for m in 
 MS_TILE = [("ms_tile", c, nb, nq) for c in (0, 1) for nb in (1, 2, 3, 4) for nq in (1, 2, 4)]  # maxsim_mfma_tile_kernel<COS, NB, NQ>
 MS_GENERIC = [("ms_generic", c) for c in (0, 1)]                                              # maxsim_mfma_kernel<COS>
 MS_RERANK = [("ms_rerank", c, nq, m) for c in (0, 1) for nq in (8, 16, 32) for m in (0, 1)]   # maxsim_rerank_kernel<COS, NQ, MULTI>
-TABLE = set(I8_SMALL + I8_TILES + MS_SCAN + MS_TILE + MS_GENERIC + MS_RERANK)
+TABLE = set(GEMM_F32 + GEMM_BF16 + GEMM_SPLIT + I8_SMALL + I8_TILES + MS_SCAN + MS_TILE + MS_GENERIC + MS_RERANK)
 TABLE_FAMILIES = {t[0] for t in TABLE}
 _SEEN: set = set()      # every instantiation a case of this file launched
 _ASSERTED: set = set()  # ... and the ones a case asserted by name
@@ -193,13 +204,15 @@ def _i8_batch(B, dim, kind):
     return _VB[(dim, kind)]
 
 
-def _knn_vs_oracle(B, innr, metric, dim, kind, nq, k, stats=None):
-    """one INNR_KNN_MFMA_I8 call on the f32 corpus, compared with the oracle exactly; returns (idx, scores), launches"""
+def _knn_vs_oracle(B, innr, metric, dim, kind, nq, k, stats=None, engine=None):
+    """one call of `engine` (INNR_KNN_MFMA_I8 unless given) on the f32 corpus, compared with the oracle exactly; returns
+    (idx, scores), launches"""
     fn = {"dot": B.batch_knn_dot_multi, "cos": B.batch_knn_cosine_multi, "l2": B.batch_knn_multi}[metric]
+    engine = innr.KNN_MFMA_I8 if engine is None else engine
     vb, qs = _i8_batch(B, dim, kind), _i8_queries(dim, nq)
     st = stats if stats is not None else innr.KnnStats()
-    (idx, sc), log = _run(lambda: fn(qs, vb, k, engine=innr.KNN_MFMA_I8, stats=st))
-    assert st.engine == innr.KNN_MFMA_I8
+    (idx, sc), log = _run(lambda: fn(qs, vb, k, engine=engine, stats=st))
+    assert st.engine == engine
     for j, (oi, os_) in enumerate(_i8_oracle(dim, kind, metric, nq, k)):
         assert same_knn(metric, idx[j], sc[j], oi, os_), (metric, j, idx[j], oi, sc[j], os_)
     return (idx, sc), log
@@ -303,6 +316,128 @@ def test_i8_one_limb_tile_f32_corpus_and_its_collect_pass(B, innr, ctx_option):
     _expect(log, ("i8_one", 12, 0), groups=1)
     _expect(log, ("i8_one", 6, 2), groups=1)
     assert not any(e.family == "i8_small" for e in log), log
+
+
+# ------------------------------------------------------------------------------- f32 / bf16 / split-bf16 GEMM families
+D_GEMM = 123  # ragged: no multiple of the kernels' K-steps; with N_I8 rows the last 128-row corpus tile is partly full
+KIND_OF = {"dot": DOT, "cos": COS, "l2": L2}
+
+
+@pytest.mark.parametrize("wv", [1, 2, 4, 8])
+@pytest.mark.parametrize("k", sorted(RR_OF_K))
+@pytest.mark.parametrize("metric", ["dot", "cos", "l2"])
+def test_gemm_f32_filter(B, innr, ctx_option, metric, k, wv):
+    """gemm_filter_kernel<KIND, RR, 0, WV>: 3 queries on a tile of 64 WV (gemm_waves; the rest of the tile is padding), lists of
+    32 / 64 / 128 / 256 candidates; no_split_filter keeps dot and cosine on this kernel"""
+    ctx_option("gemm_seed_n", 256)
+    ctx_option("no_split_filter", 1)
+    ctx_option("gemm_waves", wv)
+    _, log = _knn_vs_oracle(B, innr, metric, D_GEMM, "uniform", 3, k, engine=innr.KNN_MFMA)
+    _expect(log, ("gemm_f32", KIND_OF[metric], RR_OF_K[k], 0, wv), groups=1)
+    assert not any(e.family in ("gemm_bf16", "gemm_split") for e in log), log
+
+
+def test_gemm_f32_three_query_tiles(B, innr, ctx_option):
+    """130 queries on one-wave tiles of 64: three query tiles, the last one mostly padding"""
+    ctx_option("gemm_seed_n", 256)
+    ctx_option("no_split_filter", 1)
+    ctx_option("gemm_waves", 1)
+    _, log = _knn_vs_oracle(B, innr, "dot", D_GEMM, "uniform", 130, 10, engine=innr.KNN_MFMA)
+    _expect(log, ("gemm_f32", DOT, 6, 0, 1), groups=3)
+
+
+@pytest.mark.parametrize("metric,nq,wv", [("dot", 9, 4), ("cos", 9, 4), ("l2", 9, 4), ("dot", 260, 8)])
+def test_gemm_f32_collect(B, innr, ctx_option, metric, nq, wv):
+    """the collect twin <KIND, 6, 2, WV> of the completion pass: k = 100 on the corpus with more near-ties at the top than a list
+    of 128 holds, so no query is proven by the first pass. 9 queries: up to 8 unproven ones take the exact engine instead (knn_mfma);
+    the 8-wave tile serves the dot kind from 257 unproven queries on"""
+    ctx_option("gemm_seed_n", 256)
+    ctx_option("no_split_filter", 1)
+    st = innr.KnnStats()
+    _, log = _knn_vs_oracle(B, innr, metric, D_GEMM, "dup", nq, 100, stats=st, engine=innr.KNN_MFMA)
+    print(f"{metric}: {st.queries_fallback} of {nq} queries unproven after the first pass; launches {log}")
+    _expect(log, ("gemm_f32", KIND_OF[metric], 12, 0, wv if nq > 256 else 1), groups=1)
+    _expect(log, ("gemm_f32", KIND_OF[metric], 6, 2, wv), groups=1)
+
+
+@functools.lru_cache(maxsize=None)
+def _u8_case(k):
+    """the code corpus, the queries and the oracle's answers of the u8-kind cases (shared by the tile widths)"""
+    codes = _codes(N_I8, D_GEMM, 13)
+    qs = oracle.generate_uniform(3, D_GEMM, 323)
+    return codes, qs, [_oracle_knn_u8(q, codes, 2.0, -1.0, k) for q in qs]
+
+
+@pytest.mark.parametrize("wv", [4, 8])
+@pytest.mark.parametrize("k", sorted(RR_OF_K))
+def test_gemm_f32_filter_code_corpus(S, innr, ctx_option, k, wv):
+    """the u8 kind <kGemmU8, RR, 0, WV> (innr_batch_knn_u8 on INNR_KNN_MFMA): 4- and 8-wave tiles only"""
+    ctx_option("gemm_seed_n", 256)
+    ctx_option("gemm_waves", wv)
+    codes, qs, expect = _u8_case(k)
+    qc = S.QuantizedCorpus.from_codes(codes, N_I8, D_GEMM, S.QuantizationParams(2.0, -1.0))
+    st = innr.KnnStats()
+    (idx, sc), log = _run(lambda: qc.knn_multi(qs, k, engine=innr.KNN_MFMA, stats=st))
+    assert st.engine == innr.KNN_MFMA
+    for j, (oi, os_) in enumerate(expect):
+        assert same_knn("dot", idx[j], sc[j], oi, os_), (j, idx[j], oi)
+    _expect(log, ("gemm_f32", U8, RR_OF_K[k], 0, wv), groups=1)
+    qc.close()
+
+
+def _small_integers(n, nq, dim):
+    """rows and queries of small integers: every product and partial sum is exact in f32 (and every value in bf16), so a dense
+    score must EQUAL the integer product; asymmetric, so a transposed operand or accumulator map shows"""
+    rows = ((np.arange(n)[:, None] * 7 + np.arange(dim)[None, :] * 3) % 11 - 5).astype(np.float32)
+    qs = ((np.arange(nq)[:, None] * 5 + np.arange(dim)[None, :]) % 7 - 3).astype(np.float32)
+    return rows, qs, (qs.astype(np.int64) @ rows.astype(np.int64).T).astype(np.float32)
+
+
+@pytest.mark.parametrize("metric", ["dot", "cos"])
+def test_gemm_f32_dump(B, innr, metric):
+    """the dense-score mode <KIND, 6, 1, 4> behind the layout hook innrdbg_gemm_scores (lists of 32, four waves, whatever the call)"""
+    rows, qs, exact = _small_integers(300, 3, D_GEMM)
+    vb = B.VerticalBatch.from_rows(rows)
+    if metric == "dot":
+        got, log = _run(lambda: _dense_scores(vb, innr.METRIC_DOT, qs))
+        assert np.array_equal(got, exact)
+    else:  # the approximate cosine: the bound of test_gpu_mfma.py's dense check
+        got, log = _run(lambda: _dense_scores(vb, innr.METRIC_COSINE, qs))
+        data = oracle.from_rows(rows)
+        norms = oracle.batch_norms(data)
+        for j in range(len(qs)):
+            assert np.all(np.abs(got[j] - oracle.batch_cosine(qs[j], data, norms)) <= 2e-4), j
+    _expect(log, ("gemm_f32", KIND_OF[metric], 6, 1, 4), groups=1)
+
+
+@pytest.mark.parametrize("k,rr", [(10, 12), (40, 20)])
+def test_gemm_bf16_filter(B, innr, ctx_option, k, rr):
+    """gemm_bf16_filter_kernel<RR, 0, 1> (INNR_KNN_MFMA_BF16): lists of pick_kp(4k + 64), never below 128, so RR is 12 or 20;
+    every metric has a packed copy of its own"""
+    ctx_option("gemm_seed_n", 256)
+    for metric in ("dot", "cos", "l2"):
+        _, log = _knn_vs_oracle(B, innr, metric, D_GEMM, "uniform", 3, k, engine=innr.KNN_MFMA_BF16)
+        _expect(log, ("gemm_bf16", rr, 0, 1), groups=1)
+
+
+@pytest.mark.parametrize("k", sorted(RR_OF_K))
+def test_gemm_split_filter(B, innr, ctx_option, k):
+    """gemm_bf16_filter_kernel<RR, 0, 3>: INNR_KNN_MFMA's dot / cosine filter, taken at 3 queries with split_min_q = 1"""
+    ctx_option("gemm_seed_n", 256)
+    ctx_option("split_min_q", 1)
+    for metric in ("dot", "cos"):
+        _, log = _knn_vs_oracle(B, innr, metric, D_GEMM, "uniform", 3, k, engine=innr.KNN_MFMA)
+        _expect(log, ("gemm_split", RR_OF_K[k], 0, 3), groups=1)
+        assert not any(e.family == "gemm_f32" and e.args[2] == 0 for e in log), log  # no first pass on the f32 kernel
+
+
+def test_gemm_split_dump(B, innr):
+    """the dense-score mode <6, 1, 3> behind innrdbg_split_scores: small integers have no lo limb, the sum is exact"""
+    rows, qs, exact = _small_integers(300, 3, D_GEMM)
+    vb = B.VerticalBatch.from_rows(rows)
+    got, log = _run(lambda: _split_scores(vb, innr.METRIC_DOT, qs))
+    assert np.array_equal(got, exact)
+    _expect(log, ("gemm_split", 6, 1, 3), groups=1)
 
 
 # ------------------------------------------------------------------------------- maxsim family
