@@ -34,11 +34,14 @@ __global__ __launch_bounds__(64) void dimension_variance_kernel(const float* __r
 #pragma unroll 4
     for (uint32_t i = 0; i < n4; ++i) {
         const float4 v = r4[i];
-        const float a = ex::sub(v.x, mean), b = ex::sub(v.y, mean), c = ex::sub(v.z, mean), e = ex::sub(v.w, mean);
+        // (sub_keepnan: a NaN mean -- a column that holds a NaN -- keeps its sign, like the reference's x - mean on the host ISAs;
+        // variance_order sorts by total_cmp, which puts +NaN first and -NaN last)
+        const float a = ex::sub_keepnan(v.x, mean), b = ex::sub_keepnan(v.y, mean), c = ex::sub_keepnan(v.z, mean),
+                    e = ex::sub_keepnan(v.w, mean);
         acc = ex::mad2(ex::mad2(ex::mad2(ex::mad2(acc, a, a), b, b), c, c), e, e);
     }
     for (uint32_t i = n4 * 4; i < N; ++i) {
-        const float a = ex::sub(row[i], mean);
+        const float a = ex::sub_keepnan(row[i], mean);
         acc = ex::mad2(acc, a, a);
     }
     var[d] = ex::div(acc, nf);
