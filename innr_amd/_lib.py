@@ -191,7 +191,7 @@ def _preload_torch_rccl() -> None:
             return
         path = os.path.join(list(spec.submodule_search_locations)[0], "lib", "librccl.so")
         if os.path.exists(path) and "INNR_RCCL_LIB" not in os.environ:
-            os.environ["INNR_RCCL_LIB"] = path  # load_rccl() in api.hip opens this path first
+            os.environ["INNR_RCCL_LIB"] = path  # load_rccl() in comm.hip opens this path first
     except Exception:
         pass
 

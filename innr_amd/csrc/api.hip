@@ -1,19 +1,13 @@
-// api.hip -- the extern "C" boundary (include/innr_hip.h) over the gfx950 kernels.
-#include <dlfcn.h>
+// api.hip -- the extern "C" boundary (include/innr_hip.h) over the gfx950 kernels: contexts, batches, the kNN engines, the u8 and
+// int8 paths, range search, memory. maxsim lives in maxsim.hip, the multi-GPU layer in comm.hip, the full sort in sort_full.hip;
+// what they share with this file is api_internal.h.
 #include <ctype.h>
 #include <stdarg.h>
 #include <stdio.h>
-#include <string.h>
 
-#include <rccl/rccl.h>  // types and enums only: the library is bound at run time (load_rccl), not linked
-
-#include <algorithm>
-#include <mutex>
 #include <memory>
-#include <new>
-#include <vector>
 
-#include "common.h"
+#include "api_internal.h"
 #include "kernels_prep.h"
 #include "kernels_scan.h"
 #include "kernels_topk.h"
@@ -22,18 +16,7 @@
 #include "kernels_ext.h"
 #include "kernels_u8.h"
 #include "kernels_gemm_i8.h"
-#include "kernels_maxsim.h"
 #include "kernels_select.h"
-
-namespace innr {  // sort_full.hip
-hipError_t full_sort_scratch_bytes(size_t n, size_t* bytes);
-size_t full_topk_out_capacity(size_t k);  // keys the `sorted` buffer must hold for the best k (the next power of two)
-hipError_t full_sort_scores(const float* scores, size_t n, bool smaller_is_better, uint64_t* keys, uint64_t* sorted,
-                            void* scratch, size_t scratch_bytes, hipStream_t stream, const uint8_t* mask, size_t k);
-hipError_t segmented_sort_scratch_bytes(size_t nseg, size_t len, size_t* bytes);
-hipError_t segmented_topk_keys(const uint64_t* keys, uint64_t* sorted, size_t nseg, size_t len, size_t k, uint64_t* tmp, void* scratch,
-                               hipStream_t stream);
-}  // namespace innr
 
 namespace innr {
 
@@ -46,62 +29,8 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// A device buffer that only grows (workspace; never reallocated inside a steady-state call).
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    innr_status ensure(size_t need) {
-        if (need <= bytes) return INNR_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        INNR_HIP_CHECK(hipMalloc(&p, need));
-        bytes = need;
-        return INNR_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 }  // namespace innr
 
-using namespace innr;
-
-// Tuning / experiment switches of a context. Read from the environment ONCE, in innr_ctx_create (INNR_<NAME IN CAPITALS>), and
-// changed afterwards only through innr_ctx_set_option: no entry point reads the environment on the call path.
-struct innr_tuning {
-    long gemm_waves = 0;         // force the f32 GEMM engine's block shape (1, 2, 4, 8 waves); 0 = by batch size
-    long gemm_blocks_per_cu = 0; // resident blocks per CU of the f32 GEMM engine; 0 = by block shape
-    long gemm_qt_group = 1;      // query tiles per XCD group (plan_gemm)
-    long gemm_seed_n = 0;        // rows of the corpus prefix that seeds the chip-wide bounds; 0 = by engine
-    long gemm_no_seed = 0;       // no threshold seeding
-    long gemm_no_kp_retry = 0;   // unproven minority: straight to the exact engine, no second pass with longer lists
-    long i8_two_limb = 0;        // batch_knn_u8 on the int8 pipe: both limbs on the matrix pipe (the cross-check kernel)
-    long no_auto_bf16 = 0;       // INNR_KNN_AUTO never picks the bf16 filter
-    long no_auto_i8 = 0;         // INNR_KNN_AUTO never picks the int8 filter for an f32 corpus
-    long u8_no_i8 = 0;           // INNR_KNN_AUTO never picks the int8 engine for a code corpus
-    long rescore_all = 0;        // re-score every candidate (no progressive rounds)
-    long maxsim_generic = 0;     // maxsim MFMA engine: the generic kernel instead of the tile-unrolled one
-    long no_k_rule = 0;          // chip-wide bounds by the KP rule only (topk_dev.h): A/B of the k rule
-    long fail_local_search = 0;  // TEST switch of the sharded calls: this rank's local search reports a failure
-    long no_completion = 0;      // unproven queries of the f32 engine: straight to the KP retry / exact engine (no completion pass)
-    long trace = 0;              // diagnostics of the redo paths on stderr (list lengths of the completion pass, ...)
-    long no_rows_copy = 0;       // never build the row-major copy: the completion pass re-scores by column gathers (what a full HBM does)
-    long i8_slices_per_cu = 0;   // corpus slices (= blocks) per CU and query tile of the int8 filters; 0 = by metric (plan_i8)
-    long i8_no_small = 0;        // never the small-batch int8 kernel (gemm_i8s_filter_kernel): A/B against the 512-query tile
-    long i8_no_small4 = 0;       // ... never its four-column-tile form (65 .. 128 queries)
-    long i8_small_max_q = 0;     // ... its largest batch (groups of 128 queries beyond 128); 0 = the default
-    long i8_small_free = 0;      // ... its query groups run free (no soft lockstep): A/B
-    long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
-    long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
-    long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi: keep the selection of the last mask for the next call (0: free it at the end of each call)
-    long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
-};
 struct TuneName { const char* name; long innr_tuning::*field; };
 static const TuneName kTuneNames[] = {
     {"gemm_waves", &innr_tuning::gemm_waves}, {"gemm_blocks_per_cu", &innr_tuning::gemm_blocks_per_cu},
@@ -127,98 +56,6 @@ static void tuning_from_env(innr_tuning* t) {
     }
 }
 
-// One templated kernel launch of the filter and scan families, as its dispatch site chose it (innr_ctx::launch_log). Written by
-// plain host stores in launch_kernel, in every build; read only by the test hooks (innrdbg_launch_log), which
-// tests/test_gpu_kernel_variants.py decodes: its table names every instantiation a call may reach.
-enum LaunchFamily {
-    kLaunchGemmF32 = 1,    // gemm_filter_kernel<KIND, RR, MODE, WV>
-    kLaunchGemmBf16 = 2,   // gemm_bf16_filter_kernel<RR, 0, 1>: args RR, MODE, LIMBS
-    kLaunchGemmSplit = 3,  // gemm_bf16_filter_kernel<RR, MODE, 3>: args RR, MODE, LIMBS
-    kLaunchI8One = 4,      // gemm_i8h_filter_kernel<RR, MODE>
-    kLaunchI8Two = 5,      // gemm_i8_filter_kernel<RR, MODE>
-    kLaunchI8Small = 6,    // gemm_i8s_filter_kernel<12, NK, CT, MODE>: args NK, CT, MODE
-    kLaunchMsScan = 7,     // maxsim_scan_kernel<COS, NQ, MULTI>, once per pass
-    kLaunchMsTile = 8,     // maxsim_mfma_tile_kernel<COS, NB, NQ>, once per pass
-    kLaunchMsGeneric = 9,  // maxsim_mfma_kernel<COS>, once per pass
-    kLaunchMsRerank = 10,  // maxsim_rerank_kernel<COS, NQ, MULTI>, once per pass
-    kLaunchRangeScan = 11, // range_scan_kernel<QB, L2, COS, EMIT>: args QB, metric (INNR_METRIC_*), EMIT; groups = query groups
-};
-struct LaunchRec {
-    uint8_t family;    // LaunchFamily
-    uint8_t lockstep;  // gemm_i8s_filter_kernel: the soft-lockstep `prog` buffer was passed
-    int16_t arg[4];    // the template arguments, in the order of the family's comment above (unused: 0)
-    uint32_t groups;   // query groups (tiles) of the launch; the maxsim families: queries per corpus pass
-};
-constexpr size_t kLaunchLogCap = 64;
-
-struct innr_ctx {
-    innr_tuning tune;
-    // One call at a time per context: the workspace below (grow-by-free DevBufs, the pinned bump allocator, `pending`,
-    // the flags buffer, ev[]) is shared by every entry point, so each one holds this lock for its whole duration
-    // (CtxGuard). Recursive: host-pointer entry points call their _dev counterparts.
-    std::recursive_mutex mu;
-    int depth = 0;  // nesting of CtxGuards on the owning thread
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int num_cus = 256;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [4], [5]: the span of a filtered multi-query call
-    // Pinned staging for SMALL host<->device transfers (queries in, top-k out, flags): a hipMemcpyAsync on pageable
-    // memory costs ~40 us per call on this stack, four of them made a single-query call 190 us; through pinned
-    // memory the same copies are a few us. Inputs are staged by copy_in (bump allocation), outputs land in the
-    // pinned area and are handed to the caller's buffers by ctx_sync, which every host-pointer entry point ends on.
-    char* pin = nullptr;
-    size_t pin_in_off = 0, pin_out_off = 0;
-    struct PendingOut {
-        void* user;
-        const void* staged;
-        size_t bytes;
-    };
-    std::vector<PendingOut> pending;
-    // workspace (a DevBuf added here goes into workspace_bufs() below as well: destroy, innr_ctx_memory and innr_ctx_trim walk that list)
-    DevBuf q_row;     // queries row-major [Q][ldq]
-    DevBuf q_kmajor;  // queries K-major [Dpad][Qpad] for the GEMM engine
-    DevBuf q_norm;    // [Q] exact query norms
-    DevBuf lists;     // candidate lists
-    DevBuf counts;    // list counts
-    DevBuf sel;       // selected composites [Q][KP]
-    DevBuf sel_cnt;   // [Q]
-    DevBuf gthr;           // GEMM engine: global threshold slots + bounds + k-rule margins
-    DevBuf kmargin;        // [Qpad] 2E per query, staged for prep_gthr
-    DevBuf i8s_prog;       // gemm_i8s_filter_kernel with several query groups: [wave slices][groups] positions (soft lockstep)
-    DevBuf sel_tmp[2];     // multi-level select: [parts][Q][KP]
-    DevBuf selcnt_tmp[2];  // [parts][Q]
-    DevBuf scores;    // [QB][ldN] materialised scores
-    DevBuf tmp_norms; // caller-provided norms staged on device
-    DevBuf flags;     // error flag + per-query fallback flags
-    DevBuf out_idx;   // staging for host-pointer entry points
-    DevBuf out_score;
-    DevBuf seed_idx;   // threshold seeding: exact top-KP of a corpus prefix (indices unused, scores -> bounds)
-    DevBuf seed_score;
-    DevBuf misc;
-    DevBuf q_bf16;     // bf16 filter engine: K-packed bf16 queries
-    struct RedoBufs {
-        DevBuf q, idx, sc, map, qn;
-    } redo[2];  // unproven queries, gathered and redone as ONE batch; [1]: the batch's own unproven queries (redo_batch)
-    RedoBufs cmpl;     // the completion pass of unproven queries (knn_complete)
-    DevBuf q_hat;      // int8 filter of an f32 corpus, cosine: the normalised queries
-    DevBuf q_pad;      // exact engine: a ragged tail of 2-3 / 5-7 queries padded with zero rows to a 4- / 8-query pass
-    DevBuf q_one;      // full-sort path (k > INNR_MAX_K): one zero-padded query row
-    DevBuf sort_keys;  // [2][N] composites: unsorted, sorted
-    DevBuf sort_tmp;   // radix sort scratch
-    DevBuf flt_in;     // innr_batch_knn_filtered_multi: the caller's mask bytes staged on the device (host-memory entry point)
-    DevBuf flt_mask;   // ... the mask normalised to 0/1, [ldN]
-    DevBuf flt_scan;   // ... passing vectors per chunk [nchunks], their exclusive scan [nchunks], the total, the mask-differs flag
-    DevBuf rs_cnt;     // innr_batch_range_search: survivors per 256-vector chunk [queries][nchunks + 1], scanned in place
-    DevBuf rs_bits;    // ... the collect path's survivor bitmaps [queries][ldN / 32]
-    DevBuf rs_tot;     // ... [queries] totals, then [queries] flags: the exact scan finishes this query
-    DevBuf rs_thr;     // ... the thresholds and [Q + 1] offsets of the host-memory entry point, staged on the device
-    DevBuf rs_off;
-    int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
-    LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
-    uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
-};
-
 // Every workspace DevBuf of a context (innr_ctx_destroy, innr_ctx_memory, innr_ctx_trim). All but `flags` are sized by the calls
 // that use them (an ensure() in front of every use) and carry nothing from one call to the next; `flags` is allocated and zeroed
 // once, in innr_ctx_create, and the kernels' error words live there between the calls' own memsets: innr_ctx_trim keeps it.
@@ -232,58 +69,21 @@ static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
             &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off};
 }
 
-// ---- choosing a kernel instantiation from run-time values ------------------------------------------------------------
-// One instantiation of a recorded family, as compile-time constants: the family and the template arguments in the order of
-// LaunchFamily's comments (bool parameters as 0 / 1). kernel_of(Inst) is the kernel they name.
-template <int N> using IntC = std::integral_constant<int, N>;
-template <int FAMILY, int... ARGS> struct Inst {};
+// kernel_of(Inst) of the recorded families whose kernels this file owns (api_internal.h: Inst, launch_kernel)
 template <int KIND, int RR, int MODE, int WV> constexpr auto kernel_of(Inst<kLaunchGemmF32, KIND, RR, MODE, WV>) { return &gemm_filter_kernel<KIND, RR, MODE, WV>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmBf16, RR, MODE, 1>) { return &gemm_bf16_filter_kernel<RR, MODE, 1>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmSplit, RR, MODE, 3>) { return &gemm_bf16_filter_kernel<RR, MODE, 3>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8One, RR, MODE>) { return &gemm_i8h_filter_kernel<RR, MODE>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Two, RR, MODE>) { return &gemm_i8_filter_kernel<RR, MODE>; }
 template <int NK, int CT, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Small, NK, CT, MODE>) { return &gemm_i8s_filter_kernel<12, NK, CT, MODE>; }
-template <int COS, int NQ, int MULTI> constexpr auto kernel_of(Inst<kLaunchMsScan, COS, NQ, MULTI>) { return &maxsim_scan_kernel<COS != 0, NQ, MULTI != 0>; }
-template <int COS, int NB, int NQ> constexpr auto kernel_of(Inst<kLaunchMsTile, COS, NB, NQ>) { return &maxsim_mfma_tile_kernel<COS != 0, NB, NQ>; }
-template <int COS> constexpr auto kernel_of(Inst<kLaunchMsGeneric, COS>) { return &maxsim_mfma_kernel<COS != 0>; }
-template <int COS, int NQ, int MULTI> constexpr auto kernel_of(Inst<kLaunchMsRerank, COS, NQ, MULTI>) { return &maxsim_rerank_kernel<COS != 0, NQ, MULTI != 0>; }
 template <int QB, int MET, int EMIT> constexpr auto kernel_of(Inst<kLaunchRangeScan, QB, MET, EMIT>) {
     return &range_scan_kernel<QB, MET == INNR_METRIC_L2SQ, MET == INNR_METRIC_COSINE, EMIT != 0>;
 }
 
-// Record an instantiation (the caller holds the context's lock, as every dispatch site does: a few host stores) and launch it on
-// the context's stream. The record is written from the constants that name the kernel, so it cannot name another one.
-struct LaunchDims {
-    dim3 grid, block;
-    size_t lds = 0;
-    uint32_t groups = 1;    // LaunchRec::groups
-    bool lockstep = false;  // LaunchRec::lockstep
-};
-template <int FAMILY, int... ARGS, class... KernelArgs>
-static void launch_kernel(innr_ctx* c, Inst<FAMILY, ARGS...> inst, const LaunchDims& d, KernelArgs... args) {
-    c->launch_log[c->launch_total++ % kLaunchLogCap] = LaunchRec{(uint8_t)FAMILY, (uint8_t)d.lockstep, {ARGS...}, d.groups};
-    kernel_of(inst)<<<d.grid, d.block, d.lds, c->stream>>>(args...);
-}
-
-// A run-time value that selects one of the constants Vs; any other value selects the LAST of them (a switch's `default:`).
-// dispatch(f, one_of<..>(a), one_of<..>(b), ...) calls f(IntC<A>(), IntC<B>(), ...) with the selected constants and returns what it
-// returns: f is a generic lambda, instantiated once per combination, and excludes the combinations that must not exist by
-// `if constexpr` on its arguments.
-template <int... Vs> struct OneOf { int v; };
-template <int... Vs> static OneOf<Vs...> one_of(long v) { return {(int)v}; }
-template <class F> static auto dispatch(F&& f) { return f(); }
-template <class F, int V, int... Vs, class... Rest>
-static auto dispatch(F&& f, OneOf<V, Vs...> o, Rest... rest) {
-    const auto bound = [&](auto... cs) { return f(IntC<V>(), cs...); };
-    if constexpr (sizeof...(Vs) == 0) return dispatch(bound, rest...);
-    else return o.v == V ? dispatch(bound, rest...) : dispatch(f, OneOf<Vs...>{o.v}, rest...);
-}
-static auto flag(bool on) { return one_of<1, 0>(on); }
 static auto metric_of(int metric) { return one_of<INNR_METRIC_COSINE, INNR_METRIC_L2SQ, INNR_METRIC_DOT>(metric); }
 // RR (R in the kernels) of a list capacity of 64 RR entries: the GEMM-type filters have lists of 32 / 64 / 128 / 256 candidates
 // (cand_cap: 384 / 512 / 768 / 1280 entries), the exact scans of 32 / 128 / 256 (exact_cap)
 static auto rr_gemm(uint32_t cap) { return one_of<6, 8, 12, 20>(cap / 64); }
-static auto rr_scan(uint32_t cap) { return one_of<6, 12, 20>(cap / 64); }
 
 // The score space of a proof: rescore_kernel's MET, seed_thresholds_kernel's and kmargin_kernel's kind.
 enum ScoreSpace : int { kSpaceDot = 0, kSpaceCos = 1, kSpaceL2 = 2, kSpaceEq = 3, kSpaceCode = 4 };
@@ -308,7 +108,7 @@ namespace innr {
 constexpr size_t kPinIn = 512 << 10, kPinOut = 768 << 10, kPinSmall = 256 << 10;
 
 // host -> device; small buffers go through the pinned staging area (valid until the next ctx_sync)
-static hipError_t copy_in(innr_ctx* c, void* dst, const void* src, size_t bytes) {
+hipError_t copy_in(innr_ctx* c, void* dst, const void* src, size_t bytes) {
     if (c->pin && bytes <= kPinSmall && c->pin_in_off + bytes <= kPinIn) {
         char* st = c->pin + c->pin_in_off;
         memcpy(st, src, bytes);
@@ -319,7 +119,7 @@ static hipError_t copy_in(innr_ctx* c, void* dst, const void* src, size_t bytes)
 }
 
 // device -> host; small buffers land in pinned memory and reach `dst` at the next ctx_sync
-static hipError_t copy_out(innr_ctx* c, void* dst, const void* src, size_t bytes) {
+hipError_t copy_out(innr_ctx* c, void* dst, const void* src, size_t bytes) {
     if (c->pin && bytes <= kPinSmall && c->pin_out_off + bytes <= kPinOut) {
         char* st = c->pin + kPinIn + c->pin_out_off;
         c->pin_out_off += (bytes + 255) & ~(size_t)255;
@@ -330,7 +130,7 @@ static hipError_t copy_out(innr_ctx* c, void* dst, const void* src, size_t bytes
 }
 
 // stream synchronise + deliver the staged outputs + recycle the staging area
-static hipError_t ctx_sync(innr_ctx* c) {
+hipError_t ctx_sync(innr_ctx* c) {
     const hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)
         for (const auto& po : c->pending) memcpy(po.user, po.staged, po.bytes);
@@ -338,77 +138,6 @@ static hipError_t ctx_sync(innr_ctx* c) {
     c->pin_in_off = c->pin_out_off = 0;
     return e;
 }
-
-// The derived copies of its corpus a batch can own (innr_batch::copy), and what the batch keeps of each
-enum CopyKind { kCopyRows, kCopyBfDot, kCopyBfCos, kCopyBfL2, kCopyBfDotLo, kCopyBfCosLo, kCopyI8Dot, kCopyI8Cos, kCopyI8L2, kCopyKinds };
-struct CorpusCopy {
-    char* p = nullptr;
-    size_t bytes = 0;
-    uint32_t nk = 0;       // K-steps of this copy (the rows copy: Dr)
-    bool refused = false;  // rows, lo limbs (for the split pair): it did not fit -- do not try again on every call
-    bool weak = false;     // int8 kinds: most proofs failed on this corpus (a range blown up by outliers): AUTO stops picking the filter
-};
-}  // namespace innr
-
-
-struct innr_batch {
-    innr_ctx* ctx = nullptr;
-    size_t N = 0, D = 0, ldN = 0, Dpad = 0;
-    float* V = nullptr;      // [Dpad][ldN]
-    float* norms = nullptr;  // [ldN], lazily computed (exact batch_norms)
-    float* invn = nullptr;   // [ldN], 1/norm (0 for zero-norm vectors): GEMM engine's approximate cosine
-    float* sqn = nullptr;    // [ldN], norm^2: GEMM engine's approximate L2
-    uint32_t* max_norm_bits = nullptr;
-    size_t aux_bytes = 0;  // what norms, max_norm_bits, invn and sqn were allocated with, added up where each is allocated
-    bool norms_ready = false;
-    float max_norm = 0.0f;
-    uint64_t index_base = 0;
-    std::vector<float> dimvar;  // batch_dimension_variance, computed once (batch.rs:572)
-    // scalar-quantised corpus (scalar.rs): codes C8[d*ldN + i] instead of V, with the collection's params
-    uint8_t* C8 = nullptr;
-    float alpha = 1.0f, offset = 0.0f;
-    // innr_batch_prefix_view: V / C8 belong to another batch (never freed here). Rows D..Dpad of a view can hold the
-    // parent's next dimensions instead of zero padding; the GEMM engine (which multiplies all Dpad rows) is then off.
-    bool is_view = false, gemm_ok = true;
-    // The derived copies of the corpus, indexed by innr::CopyKind; each is built on first use and always owned:
-    //  rows: row-major rows[i*Dr + d] (Dr = D rounded up to 4, kept in nk), built on the first call that has MANY candidates per
-    //    query to re-score exactly (the completion pass, k beyond the candidate lists): in the dimension-major store a candidate's D
-    //    values lie in D different cache lines (64 B fetched per 4 B used); here they are contiguous. + N*Dr*4 bytes.
-    //  bf16 filter engine (kernels_gemm_bf16.h): the K-packed bf16 copy (dot), the same with every row scaled by 1/||v|| (cosine,
-    //    built on the first cosine call) and the squared-L2 filter's copy: six more K columns per row (|v|^2 in three limbs, three ones)
-    //  split-bf16 filter of INNR_KNN_MFMA: the lo limbs x - rne_bf16(x) of the dot and the cosine copy's values, in
-    //    the same layout; built on first use when they fit
-    //  int8 filter engine (kernels_gemm_i8.h): of a u8 code batch the K-packed signed copy of the codes (the dot kind); of an F32
-    //    batch (INNR_KNN_MFMA_I8) its values scalar-quantised with one (offset, alpha) for the whole corpus (dot), its normalised
-    //    rows quantised over their own range (cosine), and the squared-L2 copy: the dot copy's quantisation plus R + 1 more
-    //    dimensions that carry |v|^2 in two 8-bit limbs (pack_corpus_f32_i8_kernel); D' = D + R + 1
-    innr::CorpusCopy copy[innr::kCopyKinds];
-    // what the int8 copies of an F32 batch were quantised with: the raw values' range (the dot and squared-L2 copies), the
-    // normalised rows' (the cosine copy), and the squared-L2 copy's extra dimensions
-    struct I8Range {
-        float alpha = 0.0f, offset = 0.0f;
-    } i8_raw, i8_norm;
-    I8Range& i8_range(innr::CopyKind k) { return k == innr::kCopyI8Cos ? i8_norm : i8_raw; }
-    uint32_t i8l2_R = 0;
-    float i8l2_nmax = 0.0f;
-    uint32_t i8_weak_skips = 0;              // AUTO calls that skipped the int8 filter since (every 64th tries it again)
-    uint32_t auto_small_calls = 0;           // AUTO calls with fewer than four queries while no int8 copy existed: the fourth builds it
-    // innr_batch_knn_filtered_multi (kernels_select.h): the selection of the last mask -- its passing vectors compacted into a batch
-    // of their own (npass * Dpad * 4 bytes, plus the filter copies the engines build on it), the normalised mask it was built from
-    // and the map selection index -> column of this batch. At most one; freed with the batch, when a call brings a different mask,
-    // and at the end of every call under filter_keep_selection = 0.
-    innr_batch* fsel = nullptr;
-    uint8_t* fsel_mask = nullptr;  // [ldN] 0/1
-    uint32_t* fsel_map = nullptr;  // [fsel->N]
-    uint32_t fsel_builds = 0;      // selections built for this batch (read by a test hook)
-    size_t fsel_mask_bytes = 0, fsel_map_bytes = 0;  // what fsel_mask / fsel_map were allocated with
-    // memory accounting (innr_batch_memory): what V / C8 was allocated with (0 for a view), and the copy budget -- the most the
-    // derived allocations (copy[] and the selection) may add up to; see budget_admits
-    size_t corpus_bytes = 0;
-    uint64_t copy_budget = UINT64_MAX;
-};
-
-namespace innr {
 
 // which copy a call of a metric filters on: the bf16 kinds (lo: the split filter's lo limbs, dot and cosine only) and the int8 kinds
 static CopyKind bf16_kind(int metric, bool lo = false) {
@@ -496,37 +225,10 @@ static innr_status alloc_copy(innr_batch* b, CopyKind kind, size_t bytes, uint32
     return INNR_OK;
 }
 
-static innr_status bind_device(innr_ctx* ctx) {
+innr_status bind_device(innr_ctx* ctx) {
     INNR_HIP_CHECK(hipSetDevice(ctx->device));
     return INNR_OK;
 }
-
-// Serialises the entry points of one context and, when the outermost entry point leaves with device->host copies still
-// queued (an error return between a copy_out and its ctx_sync), cancels them: their destinations may be stack variables
-// of frames that are gone, and the next successful ctx_sync must not deliver into them.
-struct CtxGuard {
-    innr_ctx* c;
-    explicit CtxGuard(innr_ctx* ctx) : c(ctx) {
-        if (c) {
-            c->mu.lock();
-            ++c->depth;
-        }
-    }
-    ~CtxGuard() {
-        if (!c) return;
-        if (--c->depth == 0 && (!c->pending.empty() || c->pin_in_off || c->pin_out_off)) {
-            (void)hipStreamSynchronize(c->stream);  // the staged copies still target the pinned area: let them land
-            c->pending.clear();
-            c->pin_in_off = c->pin_out_off = 0;
-        }
-        c->mu.unlock();
-    }
-    CtxGuard(const CtxGuard&) = delete;
-    CtxGuard& operator=(const CtxGuard&) = delete;
-};
-#define INNR_ENTER(ctxp)            \
-    ::innr::CtxGuard _guard(ctxp);  \
-    INNR_TRY(::innr::bind_device(ctxp))
 
 // the copy budget a new batch starts with: the context option copy_budget_mib (< 0: unlimited)
 static uint64_t budget_from_option(const innr_ctx* ctx) {
@@ -591,9 +293,9 @@ static innr_status ensure_norms(innr_batch* b) {
     return INNR_OK;
 }
 
-static bool metric_ok(int m) { return m == INNR_METRIC_DOT || m == INNR_METRIC_L2SQ || m == INNR_METRIC_COSINE; }
+bool metric_ok(int m) { return m == INNR_METRIC_DOT || m == INNR_METRIC_L2SQ || m == INNR_METRIC_COSINE; }
 
-static uint32_t pick_kp(size_t k, size_t margin) {
+uint32_t pick_kp(size_t k, size_t margin) {
     uint32_t kp = 32;
     while (kp < k + margin) kp <<= 1;
     return kp;
@@ -601,7 +303,7 @@ static uint32_t pick_kp(size_t k, size_t margin) {
 
 // Cross-producer selection: best KP per query over `nslots` lists (each <= KP entries), tree-reduced in parts of
 // kSelSlots/KP lists until one part remains. Result: c->sel [Q][KP] best-first, c->sel_cnt [Q].
-static innr_status run_select(innr_ctx* c, const uint64_t* lists, const uint32_t* counts, uint32_t nslots,
+innr_status run_select(innr_ctx* c, const uint64_t* lists, const uint32_t* counts, uint32_t nslots,
                               uint32_t qstride, uint32_t cap, uint32_t KP, uint32_t Q) {
     INNR_TRY(c->sel.ensure((size_t)Q * KP * sizeof(uint64_t)));
     INNR_TRY(c->sel_cnt.ensure((size_t)Q * sizeof(uint32_t)));
@@ -630,9 +332,20 @@ static innr_status run_select(innr_ctx* c, const uint64_t* lists, const uint32_t
     }
 }
 
+// The one launch site of emit_results_kernel (kernels_topk.h): the first kout composites of each of Q rows of KP -> index base +
+// index and score, on the context's stream
+innr_status emit_results(innr_ctx* c, const uint64_t* sel, size_t KP, size_t Q, size_t kout, bool smaller_is_better, uint64_t index_base,
+                         uint64_t* out_idx, float* out_score) {
+    const size_t total = Q * kout;
+    emit_results_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(sel, (uint32_t)KP, (uint32_t)Q, (uint32_t)kout,
+                                                                               smaller_is_better, index_base, out_idx, out_score);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
 // ---- exact engine ---------------------------------------------------------------------------------
 // list capacity used by the exact engine for a given KP: 64*R with R in {6, 12, 20}
-static uint32_t exact_cap(uint32_t KP) { return KP <= 32 ? 384u : (KP <= 128 ? 768u : 1280u); }
+uint32_t exact_cap(uint32_t KP) { return KP <= 32 ? 384u : (KP <= 128 ? 768u : 1280u); }
 
 // optional extras of the L2 variants (device pointers; both null for the plain scans)
 struct ScanExt {
@@ -681,11 +394,7 @@ static innr_status select_and_emit(innr_batch* b, uint32_t nslots, uint32_t nql,
                                    bool l2, uint64_t* d_out_idx, float* d_out_score) {
     innr_ctx* c = b->ctx;
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), nslots, nql, cap, KP, nql));
-    const uint32_t total = nreal * (uint32_t)kout;
-    emit_results_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(c->sel.as<uint64_t>(), KP, nreal, (uint32_t)kout, l2, b->index_base,
-                                                                    d_out_idx, d_out_score);
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
+    return emit_results(c, c->sel.as<uint64_t>(), KP, nreal, kout, l2, b->index_base, d_out_idx, d_out_score);
 }
 
 // Exact kNN for queries [q0, q0+nq) (row-major on device, stride ldq): results to d_out_* at row q0.
@@ -1792,7 +1501,7 @@ static constexpr bool i8h_probe_skips_visits() {
     return (kI8hProbe & (1 | 8 | 16 | 32 | 64 | 128)) != 0;  // (8, 16: the K-loop fed from L1 / L2 instead of its real operands)
 }
 
-static innr_status check_errflag(innr_ctx* c) {
+innr_status check_errflag(innr_ctx* c) {
     uint32_t e = 0;
     INNR_HIP_CHECK(copy_out(c, &e, c->flags.p, sizeof(e)));
     INNR_HIP_CHECK(ctx_sync(c));
@@ -2213,10 +1922,7 @@ innr_status innr_batch_rerank_dev(innr_batch* b, int metric, const float* d_quer
         });
         INNR_HIP_CHECK(hipGetLastError());
         INNR_HIP_CHECK(segmented_topk_keys(keys, keys + Q * kc, Q, kc, kout, keys + 2 * Q * kc, c->sort_tmp.p, c->stream));
-        const uint32_t total = (uint32_t)(Q * kout);
-        emit_results_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(keys + Q * kc, (uint32_t)kc, (uint32_t)Q, (uint32_t)kout,
-                                                                        metric == INNR_METRIC_L2SQ, b->index_base, d_out_idx, d_out_score);
-        INNR_HIP_CHECK(hipGetLastError());
+        INNR_TRY(emit_results(c, keys + Q * kc, kc, Q, kout, metric == INNR_METRIC_L2SQ, b->index_base, d_out_idx, d_out_score));
         return finish();
     }
     const uint32_t KP = pick_kp(kc, 0);  // 32..256
@@ -2423,10 +2129,7 @@ static innr_status knn_full_sort(innr_batch* b, int metric, const float* dQ, siz
         }
         INNR_HIP_CHECK(hipGetLastError());
         INNR_HIP_CHECK(full_sort_scores(ds, N, smaller, keys, keys + N, c->sort_tmp.p, tmp_bytes, c->stream, mask, kout));
-        emit_results_kernel<<<(unsigned)((kout + 255) / 256), 256, 0, c->stream>>>(keys + N, 0, 1, (uint32_t)kout, smaller,
-                                                                               b->index_base, d_out_idx + q * kout,
-                                                                               d_out_score + q * kout);
-        INNR_HIP_CHECK(hipGetLastError());
+        INNR_TRY(emit_results(c, keys + N, 0, 1, kout, smaller, b->index_base, d_out_idx + q * kout, d_out_score + q * kout));
     }
     return INNR_OK;
 }
@@ -2452,25 +2155,6 @@ static innr_status finish_knn(innr_ctx* c, int engine, size_t kout, uint32_t nfa
     if (engine == INNR_KNN_MFMA_I8 && i8h_probe_skips_visits()) {
         set_error("this library is a timing build (-DINNR_I8H_PROBE): the int8 filter kernel skipped its visits, the call's results are not valid");
         return INNR_E_UNSUPPORTED;
-    }
-    return INNR_OK;
-}
-
-// A kNN call on host memory: the queries staged on the device, dev(d_queries, d_out_idx, d_out_score) (a *_dev entry point, room
-// for `cap` results per query), then *out_k results per query copied back
-template <class Dev>
-static innr_status knn_from_host(innr_ctx* c, const float* queries, size_t Q, size_t D, size_t cap, uint64_t* out_idx,
-                                 float* out_score, const size_t* out_k, Dev&& dev) {
-    INNR_ENTER(c);
-    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
-    INNR_TRY(c->out_idx.ensure(Q * cap * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(Q * cap * sizeof(float)));
-    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
-    INNR_TRY(dev(c->q_row.as<float>(), c->out_idx.as<uint64_t>(), c->out_score.as<float>()));
-    if (*out_k) {
-        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, Q * *out_k * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * *out_k * sizeof(float)));
-        INNR_HIP_CHECK(ctx_sync(c));
     }
     return INNR_OK;
 }
@@ -3554,706 +3238,6 @@ innr_status innr_batch_knn_u8(innr_batch* b, const float* queries, size_t Q, siz
     });
 }
 
-// ---- maxsim over a document corpus (maxsim.rs) -------------------------------------------------------------
-struct innr_docs {
-    innr_ctx* ctx = nullptr;
-    size_t ndocs = 0, T = 0, dim = 0;
-    float* tok = nullptr;          // [ndocs][T][dim]
-    uint32_t* doc_len = nullptr;   // [ndocs] or null (every document has T tokens)
-    float* tok_inv = nullptr;      // [ndocs*T] 1/|token| (0 for zero-norm tokens), built on first MFMA-engine use
-    size_t tok_bytes = 0, doc_len_bytes = 0, tok_inv_bytes = 0;  // what each was allocated with (innr_docs_memory)
-    float max_norm = 0.0f;         // max |token| over the corpus
-    uint64_t index_base = 0;
-};
-
-static innr_status alloc_docs(innr_ctx* ctx, size_t ndocs, size_t T, size_t dim, innr_docs** out) {
-    if (!ctx || !out) return INNR_E_BAD_ARG;
-    if (ndocs >= 0xFFFFFFFFull || dim > 1024 || T > 65535) {
-        set_error("maxsim corpus limits: docs < 2^32, dim <= 1024, T <= 65535 (got %zu, %zu, %zu)", ndocs, dim, T);
-        return INNR_E_UNSUPPORTED;
-    }
-    INNR_ENTER(ctx);
-    innr_docs* d = new (std::nothrow) innr_docs();
-    if (!d) return INNR_E_OOM;
-    d->ctx = ctx;
-    d->ndocs = ndocs;
-    d->T = T;
-    d->dim = dim;
-    const size_t bytes = std::max<size_t>(ndocs * T * dim, 1) * sizeof(float);
-    hipError_t e = hipMalloc((void**)&d->tok, bytes);
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu bytes) for document tokens failed: %s", bytes, hipGetErrorString(e));
-        delete d;
-        return INNR_E_OOM;
-    }
-    d->tok_bytes = bytes;
-    *out = d;
-    return INNR_OK;
-}
-
-innr_status innr_maxsim_upload(innr_ctx* ctx, const float* tokens, const uint32_t* doc_len, size_t ndocs, size_t T,
-                               size_t dim, innr_docs** out) {
-    if ((!tokens && ndocs * T * dim) || !ctx) return INNR_E_BAD_ARG;
-    INNR_ENTER(ctx);
-    innr_docs* d = nullptr;
-    INNR_TRY(alloc_docs(ctx, ndocs, T, dim, &d));
-    hipError_t e = hipSuccess;
-    if (ndocs * T * dim) e = hipMemcpy(d->tok, tokens, ndocs * T * dim * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && doc_len && ndocs) {
-        e = hipMalloc((void**)&d->doc_len, ndocs * sizeof(uint32_t));
-        if (e == hipSuccess) d->doc_len_bytes = ndocs * sizeof(uint32_t);
-        if (e == hipSuccess) e = hipMemcpy(d->doc_len, doc_len, ndocs * sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        set_error("maxsim upload failed: %s", hipGetErrorString(e));
-        innr_docs_free(d);
-        return INNR_E_HIP;
-    }
-    *out = d;
-    return INNR_OK;
-}
-
-innr_status innr_maxsim_generate(innr_ctx* ctx, size_t ndocs, size_t T, size_t dim, uint64_t seed, uint64_t row0,
-                                 innr_docs** out) {
-    if (!ctx) return INNR_E_BAD_ARG;
-    INNR_ENTER(ctx);
-    innr_docs* d = nullptr;
-    INNR_TRY(alloc_docs(ctx, ndocs, T, dim, &d));
-    const size_t ntok = ndocs * T;
-    if (ntok && dim) {
-        generate_tokens_kernel<<<(unsigned)((ntok + 255) / 256), 256, 0, ctx->stream>>>(d->tok, ntok, (uint32_t)dim, seed, row0);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = ctx_sync(ctx);
-        if (e != hipSuccess) {
-            set_error("maxsim generate failed: %s", hipGetErrorString(e));
-            innr_docs_free(d);
-            return INNR_E_HIP;
-        }
-    }
-    *out = d;
-    return INNR_OK;
-}
-
-void innr_docs_free(innr_docs* d) {
-    if (!d) return;
-    CtxGuard _guard(d->ctx);
-    if (d->ctx) {
-        (void)hipSetDevice(d->ctx->device);
-        (void)ctx_sync(d->ctx);
-    }
-    if (d->tok) (void)hipFree(d->tok);
-    if (d->doc_len) (void)hipFree(d->doc_len);
-    if (d->tok_inv) (void)hipFree(d->tok_inv);
-    delete d;
-}
-
-size_t innr_docs_count(const innr_docs* d) { return d ? d->ndocs : 0; }
-
-innr_status innr_docs_shape(const innr_docs* d, size_t* ndocs, size_t* T, size_t* dim, int* has_doc_len) {
-    if (!d) return INNR_E_BAD_ARG;
-    if (ndocs) *ndocs = d->ndocs;
-    if (T) *T = d->T;
-    if (dim) *dim = d->dim;
-    if (has_doc_len) *has_doc_len = d->doc_len ? 1 : 0;
-    return INNR_OK;
-}
-
-// tokens[docs*T*dim] (the layout innr_maxsim_upload takes) and, when the corpus has them, doc_len[docs]
-innr_status innr_docs_download(innr_docs* d, float* tokens, uint32_t* doc_len) {
-    if (!d || (!tokens && d->ndocs * d->T * d->dim)) return INNR_E_BAD_ARG;
-    INNR_ENTER(d->ctx);
-    const size_t n = d->ndocs * d->T * d->dim;
-    if (n) INNR_HIP_CHECK(hipMemcpyAsync(tokens, d->tok, n * sizeof(float), hipMemcpyDeviceToHost, d->ctx->stream));
-    if (doc_len && d->doc_len && d->ndocs)
-        INNR_HIP_CHECK(hipMemcpyAsync(doc_len, d->doc_len, d->ndocs * sizeof(uint32_t), hipMemcpyDeviceToHost, d->ctx->stream));
-    INNR_HIP_CHECK(ctx_sync(d->ctx));
-    return INNR_OK;
-}
-
-innr_status innr_docs_set_index_base(innr_docs* d, uint64_t base) {
-    if (!d) return INNR_E_BAD_ARG;
-    d->index_base = base;
-    return INNR_OK;
-}
-
-// ---- query staging: tokens zero-padded to a multiple of kMsQ in c->q_row, exact squared norms in c->q_norm (cosine)
-static innr_status maxsim_stage_query(innr_docs* d, int cosine, const float* qtok, size_t Tq) {
-    innr_ctx* c = d->ctx;
-    const size_t dim = d->dim, Tq_pad = round_up(Tq, kMsQ);
-    INNR_TRY(c->q_row.ensure(Tq_pad * dim * sizeof(float)));
-    INNR_TRY(c->q_norm.ensure(2 * Tq_pad * sizeof(float)));  // [Tq_pad] squared norms, [Tq_pad] 1/norm (MFMA engine)
-    INNR_HIP_CHECK(hipMemsetAsync(c->q_row.p, 0, Tq_pad * dim * sizeof(float), c->stream));
-    INNR_HIP_CHECK(copy_in(c, c->q_row.p, qtok, Tq * dim * sizeof(float)));
-    if (cosine) {
-        query_token_sq_kernel<<<(unsigned)((Tq_pad + 63) / 64), 64, 0, c->stream>>>(c->q_row.as<float>(), (uint32_t)Tq_pad,
-                                                                                   (uint32_t)dim, c->q_norm.as<float>());
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    return INNR_OK;
-}
-
-// exact engine over `nslots` documents (all of them, or the ones listed in doc_ids) -> out[slot]; query staged
-static innr_status maxsim_scan_exact(innr_docs* d, int cosine, size_t Tq, const uint32_t* doc_ids, size_t nslots, float* out) {
-    innr_ctx* c = d->ctx;
-    const size_t dim = d->dim;
-    uint32_t Tp = 1;
-    while (Tp < d->T && Tp < 64) Tp <<= 1;
-    const uint32_t docs_per_wave = 64 / Tp;
-    const size_t nwaves_needed = (nslots + docs_per_wave - 1) / docs_per_wave;
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((nwaves_needed + 3) / 4, (size_t)c->num_cus * 2));
-    const size_t qpk_floats = (size_t)kMsQ * std::max<size_t>(dim, 8) * 4;
-    INNR_TRY(c->q_kmajor.ensure((qpk_floats + kMsQ) * sizeof(float)));  // packed query (either engine) + sqrt of the pass' squared norms
-    float* qpk = c->q_kmajor.as<float>();
-    float* saa = qpk + qpk_floats;
-    for (size_t p0 = 0; p0 < Tq; p0 += kMsQ) {
-        const uint32_t nq = (uint32_t)std::min<size_t>(kMsQ, Tq - p0);
-        const float* qp = c->q_row.as<float>() + p0 * dim;
-        const float* aa = c->q_norm.as<float>() + p0;
-        if (cosine) sqrt_kernel<<<1, kMsQ, 0, c->stream>>>(aa, nq, saa);
-        // (every instantiation has a row in tests/test_gpu_kernel_variants.py: MS_SCAN)
-        dispatch([&](auto cosv, auto nqv, auto multi) {
-            const unsigned npk = (unsigned)(dim / 4) * nqv * 4;
-            if (npk) maxsim_pack_query_kernel<<<(npk + 255) / 256, 256, 0, c->stream>>>(qp, (uint32_t)nqv, (uint32_t)dim, qpk);
-            launch_kernel(c, Inst<kLaunchMsScan, cosv, nqv, multi>(), {blocks, kMsThreads}, d->tok, d->doc_len, (uint32_t)nslots,
-                          (uint32_t)d->T, Tp, (uint32_t)dim, qp, qpk, nq, cosine ? aa : nullptr, out, out, p0 == 0, doc_ids,
-                          cosine ? saa : nullptr);
-        }, flag(cosine), one_of<8, 16, 32>(nq <= 8 ? 8 : (nq <= 16 ? 16 : 32)), flag(d->T > 64));
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    return INNR_OK;
-}
-
-// exact scores of every document into c->scores (device); q tokens uploaded from the host
-static innr_status maxsim_scores_dev(innr_docs* d, int cosine, const float* qtok, size_t Tq, size_t dim) {
-    innr_ctx* c = d->ctx;
-    if (dim != d->dim) {  // maxsim.rs:103-110
-        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
-        return INNR_E_DIM_MISMATCH;
-    }
-    INNR_TRY(c->scores.ensure(std::max<size_t>(d->ndocs, 1) * sizeof(float)));
-    float* out = c->scores.as<float>();
-    if (Tq == 0 || d->T == 0 || d->ndocs == 0) {  // maxsim.rs:97-99: empty query or empty documents -> 0.0
-        INNR_HIP_CHECK(hipMemsetAsync(out, 0, std::max<size_t>(d->ndocs, 1) * sizeof(float), c->stream));
-        return INNR_OK;
-    }
-    INNR_TRY(maxsim_stage_query(d, cosine, qtok, Tq));
-    return maxsim_scan_exact(d, cosine, Tq, nullptr, d->ndocs, out);
-}
-
-innr_status innr_maxsim_scores(innr_docs* d, int cosine, const float* qtok, size_t Tq, size_t dim, float* out) {
-    if (!d || (!out && d->ndocs) || (!qtok && Tq * dim)) return INNR_E_BAD_ARG;
-    INNR_ENTER(d->ctx);
-    INNR_TRY(maxsim_scores_dev(d, cosine, qtok, Tq, dim));
-    if (d->ndocs) {
-        INNR_HIP_CHECK(copy_out(d->ctx, out, d->ctx->scores.p, d->ndocs * sizeof(float)));
-        INNR_HIP_CHECK(ctx_sync(d->ctx));
-    }
-    return INNR_OK;
-}
-
-// top-KP of the dense score array c->scores -> c->sel / c->sel_cnt (order: score desc, document index asc -- the
-// caller's stable sort in the reference example, examples/maxsim_colbert.rs:186-187)
-static innr_status maxsim_select(innr_docs* d, uint32_t KP, const float* sc) {
-    innr_ctx* c = d->ctx;
-    const uint32_t cap = exact_cap(KP);
-    const size_t nchunks = (d->ndocs + 255) / 256;
-    size_t nslots = round_up(std::min<size_t>(nchunks, (size_t)c->num_cus * 8), 4);
-    const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
-    INNR_TRY(c->lists.ensure(nslots * cap * sizeof(uint64_t)));
-    INNR_TRY(c->counts.ensure(nslots * sizeof(uint32_t)));
-    const unsigned nb = (unsigned)(nslots / 4);
-    uint64_t* lists = c->lists.as<uint64_t>();
-    uint32_t* counts = c->counts.as<uint32_t>();
-    uint32_t* err = c->flags.as<uint32_t>();
-    switch (cap) {
-        case 384: dense_filter_kernel<6><<<nb, 256, 0, c->stream>>>(sc, (uint32_t)d->ndocs, lists, counts, KP, cps, err); break;
-        case 768: dense_filter_kernel<12><<<nb, 256, 0, c->stream>>>(sc, (uint32_t)d->ndocs, lists, counts, KP, cps, err); break;
-        default: dense_filter_kernel<20><<<nb, 256, 0, c->stream>>>(sc, (uint32_t)d->ndocs, lists, counts, KP, cps, err); break;
-    }
-    INNR_HIP_CHECK(hipGetLastError());
-    return run_select(c, lists, counts, (uint32_t)nslots, 1, cap, KP, 1);
-}
-
-// per-token 1/norm and the corpus-wide maximum token norm, computed once per corpus (MFMA engine)
-static innr_status maxsim_ensure_token_norms(innr_docs* d) {
-    if (d->tok_inv) return INNR_OK;
-    innr_ctx* c = d->ctx;
-    const size_t ntok = d->ndocs * d->T;
-    hipError_t e = hipMalloc((void**)&d->tok_inv, (ntok + 64) * sizeof(float));  // + slack: tiles read 4-float groups past T
-    if (e != hipSuccess) {
-        d->tok_inv = nullptr;
-        set_error("hipMalloc(%zu bytes) for token norms failed: %s", ntok * sizeof(float), hipGetErrorString(e));
-        return INNR_E_OOM;
-    }
-    d->tok_inv_bytes = (ntok + 64) * sizeof(float);
-    INNR_TRY(c->misc.ensure(4096));
-    INNR_HIP_CHECK(hipMemsetAsync(c->misc.p, 0, 4, c->stream));
-    maxsim_token_norms_kernel<<<(unsigned)((ntok + 255) / 256), 256, 0, c->stream>>>(d->tok, ntok, (uint32_t)d->dim, d->tok_inv,
-                                                                                     c->misc.as<uint32_t>());
-    INNR_HIP_CHECK(hipGetLastError());
-    uint32_t bits = 0;
-    INNR_HIP_CHECK(copy_out(c, &bits, c->misc.p, 4));
-    INNR_HIP_CHECK(ctx_sync(c));
-    memcpy(&d->max_norm, &bits, 4);
-    return INNR_OK;
-}
-
-static bool maxsim_mfma_eligible(const innr_docs* d, size_t Tq) {
-    return d->T > 16 && d->dim % 8 == 0 && d->dim >= 8 && d->dim <= 512 && Tq > 0 && d->ndocs > 0;
-}
-
-// MFMA engine: approximate scores of every document (c->scores), top-KP by approximate score, exact re-score of
-// those KP documents, proof. Results in c->out_idx / c->out_score; *proven = false -> the caller redoes it exactly.
-// error bound of the approximate document score: per (token, query token) pair the MFMA fma chain and
-// the reference's mul-then-add 4-way sum differ by <= (2 dim + 8) u |q_j| |d_i|; the max over tokens is 1-Lipschitz; the
-// two Tq-term sums (tree here, sequential there) add <= 2 Tq u sum_j |best_j|. Returns false when no finite bound exists.
-static bool maxsim_error_bound(const innr_docs* d, int cosine, const float* qtok, size_t Tq, float* E) {
-    const size_t dim = d->dim;
-    double qsum = 0.0;
-    for (size_t j = 0; j < Tq; ++j) {
-        double ss = 0.0;
-        for (size_t e = 0; e < dim; ++e) ss += (double)qtok[j * dim + e] * (double)qtok[j * dim + e];
-        qsum += std::sqrt(ss);
-    }
-    const double u = 5.9604644775390625e-08;  // 2^-24
-    const double Ed = cosine ? 1.05 * (2.0 * dim + 32.0 + 2.0 * Tq) * u * (double)Tq
-                             : 1.05 * (2.0 * dim + 8.0 + 2.0 * Tq) * u * (double)d->max_norm * qsum;
-    if (!(Ed - Ed == 0.0) || Ed > 3.0e38) return false;
-    *E = (float)(Ed * 1.0000002);
-    return true;
-}
-
-// Approximate scores of `nqr` queries (1, 2 or 4; more than one only with <= 32 tokens each and a tile-unrolled dim)
-// for every document: c->scores[qi * ndocs + doc]. Query qi = qtoks[qi], Tqs[qi] tokens.
-static innr_status maxsim_approx(innr_docs* d, int cosine, const float* const* qtoks, const size_t* Tqs, int nqr) {
-    innr_ctx* c = d->ctx;
-    const size_t dim = d->dim;
-    size_t Tq_pad = 0;
-    for (int qi = 0; qi < nqr; ++qi) Tq_pad = std::max(Tq_pad, round_up(Tqs[qi], kMsQ));
-    const size_t rows = (size_t)nqr * Tq_pad;  // query qi occupies rows [qi*Tq_pad, (qi+1)*Tq_pad), zero padded
-    INNR_TRY(c->q_row.ensure(rows * dim * sizeof(float)));
-    INNR_TRY(c->q_norm.ensure(2 * rows * sizeof(float)));
-    INNR_HIP_CHECK(hipMemsetAsync(c->q_row.p, 0, rows * dim * sizeof(float), c->stream));
-    for (int qi = 0; qi < nqr; ++qi)
-        INNR_HIP_CHECK(copy_in(c, c->q_row.as<float>() + (size_t)qi * Tq_pad * dim, qtoks[qi], Tqs[qi] * dim * sizeof(float)));
-    float* qscale = c->q_norm.as<float>() + rows;
-    if (cosine) {
-        query_token_sq_kernel<<<(unsigned)((rows + 63) / 64), 64, 0, c->stream>>>(c->q_row.as<float>(), (uint32_t)rows,
-                                                                                 (uint32_t)dim, c->q_norm.as<float>());
-        maxsim_query_scale_kernel<<<(unsigned)((rows + 63) / 64), 64, 0, c->stream>>>(c->q_norm.as<float>(), (uint32_t)rows, qscale);
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    INNR_TRY(c->scores.ensure((size_t)nqr * d->ndocs * sizeof(float)));
-    INNR_TRY(c->q_kmajor.ensure((size_t)nqr * kMsQ * std::max<size_t>(dim, 8) * sizeof(float) * 4));
-    // [0,8K) norm scratch, [8K,16K) candidate ids / exact scores (maxsim_post), [16K,..) per-pass token counts: 16 bytes
-    // per pass of kMsQ query tokens -- sized from the pass count, a long query must not run into its neighbours
-    const size_t npass = Tq_pad / kMsQ;
-    INNR_TRY(c->misc.ensure(16384 + npass * 16 + 64));
-    float* qB = c->q_kmajor.as<float>();
-    float* approx = c->scores.as<float>();
-    const size_t qb_stride = dim * 32;  // floats per packed query: [dim/8][64][4]
-    const size_t lds = (size_t)nqr * qb_stride * sizeof(float);
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((d->ndocs + 3) / 4, (size_t)c->num_cus * 8));
-    const bool tiled = dim % 32 == 0 && dim <= 128 && !d->ctx->tune.maxsim_generic;
-    uint32_t* nq_dev = reinterpret_cast<uint32_t*>(static_cast<char*>(c->misc.p) + 16384);  // token counts, 4 per pass
-    for (size_t p0 = 0; p0 < Tq_pad; p0 += kMsQ) {
-        uint32_t nq_host[4] = {0, 0, 0, 0};
-        for (int qi = 0; qi < nqr; ++qi) {
-            nq_host[qi] = Tqs[qi] > p0 ? (uint32_t)std::min<size_t>(kMsQ, Tqs[qi] - p0) : 0u;
-            maxsim_pack_mfma_kernel<<<(unsigned)((dim * 32 + 255) / 256), 256, 0, c->stream>>>(
-                c->q_row.as<float>() + ((size_t)qi * Tq_pad + p0) * dim, (uint32_t)dim, qB + (size_t)qi * qb_stride);
-        }
-        INNR_HIP_CHECK(copy_in(c, nq_dev + 4 * (p0 / kMsQ), nq_host, sizeof(nq_host)));
-        const uint32_t* nqp = nq_dev + 4 * (p0 / kMsQ);
-        const float* tok_inv = cosine ? d->tok_inv : nullptr;
-        const float* qsc = cosine ? qscale + p0 : nullptr;
-        // (every instantiation has a row in tests/test_gpu_kernel_variants.py: MS_TILE, MS_GENERIC)
-        if (tiled) {  // NB = dim / 32 K-blocks; four, two or one query a pass
-            dispatch([&](auto cosv, auto nb, auto nqv) {
-                launch_kernel(c, Inst<kLaunchMsTile, cosv, nb, nqv>(), {blocks, kMsThreads, lds, (uint32_t)nqr}, d->tok, d->doc_len, tok_inv,
-                              (uint32_t)d->ndocs, (uint32_t)d->T, qB, nqp, qsc, approx, approx, p0 == 0);
-            }, flag(cosine), one_of<1, 2, 3, 4>(dim / 32), one_of<4, 2, 1>(nqr));
-        } else if (nqr != 1) {
-            set_error("internal: multi-query maxsim needs the tile-unrolled kernel");
-            return INNR_E_UNSUPPORTED;
-        } else {
-            dispatch([&](auto cosv) {
-                launch_kernel(c, Inst<kLaunchMsGeneric, cosv>(), {blocks, kMsThreads, lds}, d->tok, d->doc_len, tok_inv, (uint32_t)d->ndocs,
-                              (uint32_t)d->T, (uint32_t)dim, qB, nq_host[0], qsc, approx, approx, p0 == 0);
-            }, flag(cosine));
-        }
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    return INNR_OK;
-}
-
-// Second half of the MFMA engine for ONE query: top-KP of its approximate scores, exact re-score of those documents,
-// final order + proof. Results at c->out_idx / c->out_score + out_off; *proven = false -> the caller redoes it exactly.
-static innr_status maxsim_post(innr_docs* d, int cosine, const float* qtok, size_t Tq, size_t kout, float E,
-                               const float* approx, size_t out_off, bool* proven, uint32_t* kp_out) {
-    innr_ctx* c = d->ctx;
-    const uint32_t KP = pick_kp(kout, 16);
-    *kp_out = KP;
-    INNR_TRY(maxsim_select(d, KP, approx));
-    INNR_TRY(c->misc.ensure(16384));  // KP <= 256: ids + exact scores fit behind the first 8 KiB
-    uint32_t* ids = reinterpret_cast<uint32_t*>(static_cast<char*>(c->misc.p) + 8192);
-    float* exact = reinterpret_cast<float*>(ids + KP);
-    maxsim_cand_ids_kernel<<<(KP + 255) / 256, 256, 0, c->stream>>>(c->sel.as<uint64_t>(), c->sel_cnt.as<uint32_t>(), KP, ids);
-    INNR_HIP_CHECK(hipGetLastError());
-    const size_t ncand = std::min<size_t>(KP, d->ndocs);
-    INNR_TRY(maxsim_stage_query(d, cosine, qtok, Tq));  // the exact engine reads the query from c->q_row / c->q_norm
-    INNR_TRY(maxsim_scan_exact(d, cosine, Tq, ids, ncand, exact));
-    uint32_t* flag = c->flags.as<uint32_t>() + 64;
-    maxsim_finish_kernel<<<1, 256, 0, c->stream>>>(c->sel.as<uint64_t>(), c->sel_cnt.as<uint32_t>(), exact, (uint32_t)kout,
-                                                   (uint32_t)d->ndocs, E, d->index_base, c->out_idx.as<uint64_t>() + out_off,
-                                                   c->out_score.as<float>() + out_off, flag);
-    INNR_HIP_CHECK(hipGetLastError());
-    uint32_t ok = 0;
-    INNR_HIP_CHECK(copy_out(c, &ok, flag, 4));
-    INNR_HIP_CHECK(ctx_sync(c));
-    *proven = ok != 0;
-    return INNR_OK;
-}
-
-// exact engine for one query: all-document scores -> top-k at c->out_idx / c->out_score + out_off
-static innr_status maxsim_topk_exact(innr_docs* d, int cosine, const float* qtok, size_t Tq, size_t kout, size_t out_off,
-                                     uint32_t* kp_out) {
-    innr_ctx* c = d->ctx;
-    INNR_TRY(maxsim_scores_dev(d, cosine, qtok, Tq, d->dim));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-    if (kout > INNR_MAX_K) {  // more results than a candidate list holds: sort all document scores (cf. knn_full_sort)
-        size_t tmp_bytes = 0;
-        INNR_HIP_CHECK(full_sort_scratch_bytes(d->ndocs, &tmp_bytes));
-        INNR_TRY(c->sort_keys.ensure((d->ndocs + full_topk_out_capacity(kout)) * sizeof(uint64_t)));
-        INNR_TRY(c->sort_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
-        uint64_t* keys = c->sort_keys.as<uint64_t>();
-        INNR_HIP_CHECK(full_sort_scores(c->scores.as<float>(), d->ndocs, false, keys, keys + d->ndocs, c->sort_tmp.p, tmp_bytes,
-                                        c->stream, nullptr, kout));
-        emit_results_kernel<<<(unsigned)((kout + 255) / 256), 256, 0, c->stream>>>(keys + d->ndocs, 0, 1, (uint32_t)kout, false,
-                                                                               d->index_base, c->out_idx.as<uint64_t>() + out_off,
-                                                                               c->out_score.as<float>() + out_off);
-        INNR_HIP_CHECK(hipGetLastError());
-        *kp_out = (uint32_t)d->ndocs;
-        return INNR_OK;
-    }
-    const uint32_t KP = pick_kp(kout, 0);
-    *kp_out = KP;
-    INNR_TRY(maxsim_select(d, KP, c->scores.as<float>()));
-    emit_results_kernel<<<(unsigned)((kout + 255) / 256), 256, 0, c->stream>>>(c->sel.as<uint64_t>(), KP, 1, (uint32_t)kout, false,
-                                                                              d->index_base, c->out_idx.as<uint64_t>() + out_off,
-                                                                              c->out_score.as<float>() + out_off);
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
-}
-
-// to_host == false (the sharded call): the result stays on the device, at c->out_idx / c->out_score [*out_k]
-static innr_status maxsim_topk_impl(innr_docs* d, int cosine, const float* qtok, size_t Tq, size_t dim, size_t k, int engine,
-                                    uint64_t* out_doc, float* out_score, size_t* out_k, innr_knn_stats* stats, bool to_host) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!d || !out_k || (!qtok && Tq * dim)) return INNR_E_BAD_ARG;
-    if (engine != INNR_KNN_AUTO && engine != INNR_KNN_EXACT && engine != INNR_KNN_MFMA) return INNR_E_BAD_ARG;
-    *out_k = 0;
-    innr_ctx* c = d->ctx;
-    INNR_ENTER(c);
-    if (dim != d->dim && Tq && d->T) {
-        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
-        return INNR_E_DIM_MISMATCH;
-    }
-    if (d->ndocs == 0 || k == 0) return INNR_OK;
-    const size_t kout = std::min(k, d->ndocs);  // beyond INNR_MAX_K: the exact engine sorts all document scores
-    if (to_host && (!out_doc || !out_score)) return INNR_E_BAD_ARG;
-    const bool eligible = maxsim_mfma_eligible(d, Tq) && kout <= INNR_MAX_K && pick_kp(kout, 16) <= 256;
-    if (engine == INNR_KNN_MFMA && !eligible) {
-        set_error("maxsim MFMA engine needs T > 16, dim %% 8 == 0, 8 <= dim <= 512, a non-empty query and k <= 240");
-        return INNR_E_UNSUPPORTED;
-    }
-    const bool use_mfma = engine == INNR_KNN_MFMA || (engine == INNR_KNN_AUTO && eligible && d->ndocs >= 4096);
-    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-    bool proven = false;
-    uint32_t KP = 0;
-    int used = INNR_KNN_EXACT;
-    float scan_ms = 0.0f;
-    INNR_TRY(c->out_idx.ensure(kout * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(kout * sizeof(float)));
-    if (use_mfma) {
-        float E = 0.0f;
-        INNR_TRY(maxsim_ensure_token_norms(d));
-        // a non-finite token somewhere, or no finite bound: nothing can be proven, go straight to the exact engine
-        if ((d->max_norm - d->max_norm == 0.0f) && maxsim_error_bound(d, cosine, qtok, Tq, &E)) {
-            INNR_TRY(maxsim_approx(d, cosine, &qtok, &Tq, 1));
-            INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-            INNR_TRY(maxsim_post(d, cosine, qtok, Tq, kout, E, c->scores.as<float>(), 0, &proven, &KP));
-        }
-        if (proven) {
-            used = INNR_KNN_MFMA;
-            (void)hipEventElapsedTime(&scan_ms, c->ev[2], c->ev[3]);
-        }
-    }
-    if (!proven) {
-        INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-        INNR_TRY(maxsim_topk_exact(d, cosine, qtok, Tq, kout, 0, &KP));
-    }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
-    INNR_TRY(check_errflag(c));
-    if (to_host) {
-        INNR_HIP_CHECK(copy_out(c, out_doc, c->out_idx.p, kout * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, kout * sizeof(float)));
-    }
-    INNR_HIP_CHECK(ctx_sync(c));
-    *out_k = kout;
-    if (stats) {
-        stats->engine = used;
-        stats->candidates_kept = KP;
-        stats->queries_fallback = (use_mfma && !proven) ? 1u : 0u;
-        float ms = 0.0f;
-        if (used == INNR_KNN_MFMA) stats->gemm_ms = scan_ms;  // the approximate scan kernel(s)
-        else if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) stats->gemm_ms = ms;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
-    }
-    return INNR_OK;
-}
-
-innr_status innr_maxsim_topk(innr_docs* d, int cosine, const float* qtok, size_t Tq, size_t dim, size_t k, int engine,
-                             uint64_t* out_doc, float* out_score, size_t* out_k, innr_knn_stats* stats) {
-    return maxsim_topk_impl(d, cosine, qtok, Tq, dim, k, engine, out_doc, out_score, out_k, stats, true);
-}
-
-// Several queries against the same corpus in one call (an addition: the reference scores one (query, document) pair
-// per call). Queries are taken 4 (then 2, then 1) per corpus pass on the MFMA engine, which turns the scan from
-// HBM-bound into MFMA-bound; every query's result is the same as innr_maxsim_topk's.
-// qtoks: Q queries of Tq_stride*dim floats each, query i using its first tq[i] tokens (tq == NULL: all Tq_stride).
-innr_status innr_maxsim_topk_multi(innr_docs* d, int cosine, const float* qtoks, size_t Q, const uint32_t* tq,
-                                   size_t Tq_stride, size_t dim, size_t k, int engine, uint64_t* out_doc, float* out_score,
-                                   size_t* out_k, innr_knn_stats* stats) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!d || !out_k || (!qtoks && Q * Tq_stride * dim)) return INNR_E_BAD_ARG;
-    if (engine != INNR_KNN_AUTO && engine != INNR_KNN_EXACT && engine != INNR_KNN_MFMA) return INNR_E_BAD_ARG;
-    *out_k = 0;
-    innr_ctx* c = d->ctx;
-    INNR_ENTER(c);
-    if (dim != d->dim && Tq_stride && d->T) {
-        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
-        return INNR_E_DIM_MISMATCH;
-    }
-    if (d->ndocs == 0 || k == 0 || Q == 0) return INNR_OK;
-    const size_t kout = std::min(k, d->ndocs);
-    if (!out_doc || !out_score) return INNR_E_BAD_ARG;
-    std::vector<size_t> Tqs(Q);
-    size_t tq_max = 0, tq_min = Tq_stride;
-    for (size_t i = 0; i < Q; ++i) {
-        Tqs[i] = tq ? std::min<size_t>(tq[i], Tq_stride) : Tq_stride;
-        tq_max = std::max(tq_max, Tqs[i]);
-        tq_min = std::min(tq_min, Tqs[i]);
-    }
-    const bool eligible = tq_min > 0 && maxsim_mfma_eligible(d, tq_min) && kout <= INNR_MAX_K && pick_kp(kout, 16) <= 256;
-    if (engine == INNR_KNN_MFMA && !eligible) {
-        set_error("maxsim MFMA engine needs T > 16, dim %% 8 == 0, 8 <= dim <= 512, non-empty queries and k <= 240");
-        return INNR_E_UNSUPPORTED;
-    }
-    bool use_mfma = engine == INNR_KNN_MFMA || (engine == INNR_KNN_AUTO && eligible && d->ndocs >= 4096);
-    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
-    INNR_TRY(c->out_idx.ensure(Q * kout * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(Q * kout * sizeof(float)));
-    if (use_mfma) {
-        INNR_TRY(maxsim_ensure_token_norms(d));
-        if (!(d->max_norm - d->max_norm == 0.0f)) use_mfma = false;  // a non-finite token: nothing can be proven
-    }
-    // groups of 4 / 2 queries share a corpus pass when the tile-unrolled kernel applies and every query fits one pass
-    const bool groupable = use_mfma && dim % 32 == 0 && dim <= 128 && tq_max <= (size_t)kMsQ && !d->ctx->tune.maxsim_generic;
-    std::vector<uint8_t> done(Q, 0);
-    uint32_t KP = 0, nfallback = 0;
-    float scan_ms = 0.0f;
-    for (size_t i = 0; use_mfma && i < Q;) {
-        const int g = !groupable ? 1 : (Q - i >= 4 ? 4 : (Q - i >= 2 ? 2 : 1));
-        const float* ptrs[4];
-        size_t tqs[4];
-        float E[4];
-        bool bounded = true;
-        for (int j = 0; j < g; ++j) {
-            ptrs[j] = qtoks + (i + j) * Tq_stride * dim;
-            tqs[j] = Tqs[i + j];
-            bounded = bounded && maxsim_error_bound(d, cosine, ptrs[j], tqs[j], &E[j]);
-        }
-        if (bounded) {
-            INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-            INNR_TRY(maxsim_approx(d, cosine, ptrs, tqs, g));
-            INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-            for (int j = 0; j < g; ++j) {
-                bool proven = false;
-                INNR_TRY(maxsim_post(d, cosine, ptrs[j], tqs[j], kout, E[j], c->scores.as<float>() + (size_t)j * d->ndocs,
-                                     (i + j) * kout, &proven, &KP));
-                done[i + j] = proven ? 1 : 0;
-            }
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) scan_ms += ms;
-        }
-        i += g;
-    }
-    for (size_t i = 0; i < Q; ++i) {  // exact engine: unproven queries, or everything when the MFMA engine is off
-        if (done[i]) continue;
-        if (use_mfma) ++nfallback;
-        INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-        INNR_TRY(maxsim_topk_exact(d, cosine, qtoks + i * Tq_stride * dim, Tqs[i], kout, i * kout, &KP));
-        if (!use_mfma) {
-            INNR_HIP_CHECK(ctx_sync(c));
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) scan_ms += ms;
-        }
-    }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
-    INNR_TRY(check_errflag(c));
-    INNR_HIP_CHECK(copy_out(c, out_doc, c->out_idx.p, Q * kout * sizeof(uint64_t)));
-    INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * kout * sizeof(float)));
-    INNR_HIP_CHECK(ctx_sync(c));
-    *out_k = kout;
-    if (stats) {
-        stats->engine = use_mfma ? INNR_KNN_MFMA : INNR_KNN_EXACT;
-        stats->candidates_kept = KP;
-        stats->queries_fallback = nfallback;
-        stats->gemm_ms = scan_ms;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
-    }
-    return INNR_OK;
-}
-
-// slots and document ids are 32-bit in the re-rank kernels; its pack and norms launches have one thread per packed float / token
-static innr_status maxsim_rerank_fits(size_t Q, size_t kc, size_t Tq_stride, size_t dim) {
-    const size_t stride_pad = round_up(std::max<size_t>(Tq_stride, 1), kMsQ);
-    if (kc > 0xFFFFFF00ull / Q || Tq_stride > 0xFFFFFFFFull || stride_pad > ((size_t)0x7fffffff * 256) / (Q * (ms_rerank_blk(dim) / kMsQ))) {
-        set_error("maxsim rerank: %zu queries x %zu candidates (x %zu query tokens) is beyond one launch", Q, kc, Tq_stride);
-        return INNR_E_UNSUPPORTED;
-    }
-    return INNR_OK;
-}
-
-// Second stage for multi-vector corpora (an addition, the document-side twin of innr_batch_rerank): exact maxsim /
-// maxsim_cosine of query j against ITS kc candidate documents, best min(k, kc) per query. Every candidate is scored
-// exactly, once (maxsim_rerank_kernel: the corpus scan's arithmetic over all Q*kc pairs in one launch per 32-token pass);
-// there is no approximate stage and nothing to prove. Queries as in innr_maxsim_topk_multi, candidates as in innr_batch_rerank.
-innr_status innr_maxsim_rerank_dev(innr_docs* d, int cosine, const float* d_qtoks, size_t Q, const uint32_t* tq, size_t Tq_stride,
-                                   size_t dim, const uint64_t* d_cand, size_t kc, size_t k, uint64_t* d_out_doc, float* d_out_score,
-                                   size_t* out_k) {
-    if (!d || !out_k) return INNR_E_BAD_ARG;
-    *out_k = 0;
-    if (dim != d->dim) {  // maxsim.rs:103-110
-        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
-        return INNR_E_DIM_MISMATCH;
-    }
-    if (d->ndocs == 0 || Q == 0 || k == 0 || kc == 0) return INNR_OK;
-    if (!d_cand || !d_out_doc || !d_out_score) return INNR_E_BAD_ARG;
-    INNR_TRY(maxsim_rerank_fits(Q, kc, Tq_stride, dim));
-    std::unique_ptr<uint32_t[]> tqv(new (std::nothrow) uint32_t[Q]);
-    if (!tqv) return INNR_E_OOM;
-    size_t tq_max = 0;
-    for (size_t i = 0; i < Q; ++i) {
-        tqv[i] = (uint32_t)(tq ? std::min<size_t>(tq[i], Tq_stride) : Tq_stride);
-        tq_max = std::max<size_t>(tq_max, tqv[i]);
-    }
-    if (!d_qtoks && tq_max * dim) return INNR_E_BAD_ARG;
-    const size_t npass = std::max<size_t>((tq_max + kMsQ - 1) / kMsQ, 1), blk = ms_rerank_blk(dim);
-    const size_t kout = std::min(k, kc);
-    innr_ctx* c = d->ctx;
-    INNR_ENTER(c);
-    size_t tmp_bytes = 0;
-    INNR_HIP_CHECK(segmented_sort_scratch_bytes(Q, kc, &tmp_bytes));
-    INNR_TRY(c->sort_keys.ensure((2 * Q * kc + full_topk_out_capacity(kout)) * sizeof(uint64_t)));
-    INNR_TRY(c->sort_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
-    INNR_TRY(c->misc.ensure(Q * sizeof(uint32_t) + 64));
-    INNR_TRY(c->q_kmajor.ensure(Q * npass * blk * sizeof(float)));
-    if (cosine) INNR_TRY(c->q_norm.ensure(std::max<size_t>(2 * Q * Tq_stride, 1) * sizeof(float)));
-    if (npass > 1) INNR_TRY(c->scores.ensure(Q * kc * sizeof(float)));
-    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
-    uint32_t* bad = c->flags.as<uint32_t>() + 65;  // set by the kernel for a candidate outside the corpus
-    uint32_t* d_tq = c->misc.as<uint32_t>();
-    INNR_HIP_CHECK(copy_in(c, d_tq, tqv.get(), Q * sizeof(uint32_t)));
-    float* qpk = c->q_kmajor.as<float>();
-    float* aa = cosine ? c->q_norm.as<float>() : nullptr;
-    float* saa = cosine ? aa + Q * Tq_stride : nullptr;
-    if (tq_max && d->T) {
-        maxsim_rerank_pack_kernel<<<(unsigned)((Q * npass * blk + 255) / 256), 256, 0, c->stream>>>(
-            d_qtoks, d_tq, (uint32_t)Q, (uint32_t)Tq_stride, (uint32_t)dim, (uint32_t)npass, (uint32_t)tq_max, qpk);
-        if (cosine)
-            maxsim_rerank_norms_kernel<<<(unsigned)((Q * Tq_stride + 255) / 256), 256, 0, c->stream>>>(
-                d_qtoks, d_tq, (uint32_t)Q, (uint32_t)Tq_stride, (uint32_t)dim, aa, saa);
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    uint32_t Tp = 1;
-    while (Tp < d->T && Tp < 64) Tp <<= 1;
-    const uint32_t docs_per_wave = 64 / Tp;
-    const size_t units = Q * ((kc + docs_per_wave - 1) / docs_per_wave);
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((units + 3) / 4, (size_t)c->num_cus * 2));
-    uint64_t* keys = c->sort_keys.as<uint64_t>();
-    float* partial = c->scores.as<float>();
-    INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-    for (size_t pass = 0; pass < npass; ++pass) {
-        // (every instantiation has a row in tests/test_gpu_kernel_variants.py: MS_RERANK)
-        dispatch([&](auto cosv, auto nqv, auto multi) {
-            launch_kernel(c, Inst<kLaunchMsRerank, cosv, nqv, multi>(), {blocks, kMsThreads, 0, (uint32_t)Q}, d->tok, d->doc_len,
-                          (uint32_t)d->ndocs, (uint32_t)d->T, Tp, (uint32_t)dim, d_qtoks, (uint32_t)Tq_stride, d_tq, qpk, (uint32_t)npass,
-                          (uint32_t)pass, aa, saa, d_cand, (uint32_t)Q, (uint32_t)kc, d->index_base, partial, keys, bad);
-        }, flag(cosine), one_of<8, 16, 32>(ms_pass_nq((uint32_t)tq_max, (uint32_t)pass)), flag(d->T > 64));
-        INNR_HIP_CHECK(hipGetLastError());
-    }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-    INNR_HIP_CHECK(segmented_topk_keys(keys, keys + Q * kc, Q, kc, kout, keys + 2 * Q * kc, c->sort_tmp.p, c->stream));
-    const size_t total = Q * kout;
-    emit_results_kernel<<<(unsigned)((total + 255) / 256), 256, 0, c->stream>>>(keys + Q * kc, (uint32_t)kc, (uint32_t)Q, (uint32_t)kout,
-                                                                               false, d->index_base, d_out_doc, d_out_score);
-    INNR_HIP_CHECK(hipGetLastError());
-    uint32_t hbad = 0;  // the call's one host read
-    INNR_HIP_CHECK(copy_out(c, &hbad, bad, 4));
-    INNR_HIP_CHECK(ctx_sync(c));
-    if (c->tune.trace) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess)
-            fprintf(stderr, "innr: maxsim_rerank Q=%zu kc=%zu passes=%zu: scan kernels %.4f ms\n", Q, kc, npass, ms);
-    }
-    if (hbad) {
-        set_error("maxsim rerank: a candidate index lies outside this corpus' range [%llu, %llu)", (unsigned long long)d->index_base,
-                  (unsigned long long)(d->index_base + d->ndocs));
-        return INNR_E_BAD_ARG;
-    }
-    *out_k = kout;
-    return INNR_OK;
-}
-
-innr_status innr_maxsim_rerank(innr_docs* d, int cosine, const float* qtoks, size_t Q, const uint32_t* tq, size_t Tq_stride, size_t dim,
-                               const uint64_t* cand, size_t kc, size_t k, uint64_t* out_doc, float* out_score, size_t* out_k) {
-    if (!d || !out_k) return INNR_E_BAD_ARG;
-    *out_k = 0;
-    if (dim != d->dim) {
-        set_error("dimension mismatch (doc): query dim %zu, document dim %zu", dim, d->dim);
-        return INNR_E_DIM_MISMATCH;
-    }
-    if (d->ndocs == 0 || Q == 0 || k == 0 || kc == 0) return INNR_OK;
-    if (!cand || !out_doc || !out_score) return INNR_E_BAD_ARG;
-    INNR_TRY(maxsim_rerank_fits(Q, kc, Tq_stride, dim));  // before anything of the caller's is read
-    const size_t qfloats = Q * Tq_stride * dim;
-    if (!qtoks && qfloats) {
-        bool needed = !tq;
-        for (size_t i = 0; tq && i < Q; ++i) needed = needed || tq[i] != 0;
-        if (needed) return INNR_E_BAD_ARG;
-    }
-    innr_ctx* c = d->ctx;
-    INNR_ENTER(c);
-    const size_t kout = std::min(k, kc);
-    INNR_TRY(c->q_row.ensure(std::max<size_t>(qfloats, 1) * sizeof(float)));
-    INNR_TRY(c->out_idx.ensure(Q * (kout + kc) * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(Q * kout * sizeof(float)));
-    uint64_t* d_cand = c->out_idx.as<uint64_t>() + Q * kout;
-    if (qtoks && qfloats) INNR_HIP_CHECK(copy_in(c, c->q_row.p, qtoks, qfloats * sizeof(float)));
-    INNR_HIP_CHECK(copy_in(c, d_cand, cand, Q * kc * sizeof(uint64_t)));
-    INNR_TRY(innr_maxsim_rerank_dev(d, cosine, c->q_row.as<float>(), Q, tq, Tq_stride, dim, d_cand, kc, k, c->out_idx.as<uint64_t>(), c->out_score.as<float>(), out_k));
-    INNR_HIP_CHECK(copy_out(c, out_doc, c->out_idx.p, Q * kout * sizeof(uint64_t)));
-    INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, Q * kout * sizeof(float)));
-    INNR_HIP_CHECK(ctx_sync(c));
-    return INNR_OK;
-}
-
 extern "C" {
 
 // ---- L2 variants (exact engine) ------------------------------------------------------------------------
@@ -4338,9 +3322,7 @@ static innr_status knn_l2_ext(innr_batch* b, const float* q, size_t D, size_t k,
         if (n) {
             INNR_TRY(c->out_idx.ensure(n * sizeof(uint64_t)));
             INNR_TRY(c->out_score.ensure(n * sizeof(float)));
-            emit_results_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(keys + N, 0, 1, (uint32_t)n, true, b->index_base,
-                                                                                c->out_idx.as<uint64_t>(), c->out_score.as<float>());
-            INNR_HIP_CHECK(hipGetLastError());
+            INNR_TRY(emit_results(c, keys + N, 0, 1, n, true, b->index_base, c->out_idx.as<uint64_t>(), c->out_score.as<float>()));
             INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, n * sizeof(uint64_t)));
             INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, n * sizeof(float)));
         }
@@ -4720,17 +3702,6 @@ innr_status innr_batch_build_copies(innr_batch* b, uint32_t mask, uint32_t* buil
     return INNR_OK;
 }
 
-innr_status innr_docs_memory(const innr_docs* d, uint64_t* corpus_bytes, uint64_t* derived) {
-    if (!d) {
-        set_error("corpus is null");
-        return INNR_E_BAD_ARG;
-    }
-    CtxGuard _guard(d->ctx);
-    if (corpus_bytes) *corpus_bytes = d->tok_bytes + d->doc_len_bytes;
-    if (derived) *derived = d->tok_inv_bytes;
-    return INNR_OK;
-}
-
 innr_status innr_ctx_memory(innr_ctx* c, uint64_t* workspace_bytes) {
     if (!c) {
         set_error("ctx is null");
@@ -5075,516 +4046,6 @@ innr_status innr_batch_range_search(innr_batch* b, int metric, const float* quer
         INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, m * sizeof(float)));
     }
     INNR_HIP_CHECK(ctx_sync(c));
-    return INNR_OK;
-}
-
-}  // extern "C"
-
-// =====================================================================================================================
-// The exchange step of the sharded path: RCCL behind the boundary
-// =====================================================================================================================
-namespace innr {
-
-// librccl bound at run time: a process that never shards needs no RCCL, and a host that already carries one (PyTorch
-// bundles its own copy) must not get a second one mapped -- the copy already in the process is preferred.
-struct RcclApi {
-    void* handle = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*CommAbort)(ncclComm_t) = nullptr;  // optional: used to tear down a communicator whose collective failed
-    ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool ok = false;
-};
-
-static RcclApi* load_rccl() {
-    static RcclApi api;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-        if (const char* e = getenv("INNR_RCCL_LIB")) api.handle = dlopen(e, RTLD_NOW | RTLD_GLOBAL);
-        for (int pass = 0; pass < 2 && !api.handle; ++pass)
-            for (const char* n : names) {
-                api.handle = dlopen(n, pass == 0 ? (RTLD_NOW | RTLD_NOLOAD) : (RTLD_NOW | RTLD_GLOBAL));
-                if (api.handle) break;
-            }
-        if (!api.handle) return;
-        api.GetUniqueId = reinterpret_cast<decltype(api.GetUniqueId)>(dlsym(api.handle, "ncclGetUniqueId"));
-        api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(dlsym(api.handle, "ncclCommInitRank"));
-        api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(dlsym(api.handle, "ncclCommDestroy"));
-        api.CommAbort = reinterpret_cast<decltype(api.CommAbort)>(dlsym(api.handle, "ncclCommAbort"));
-        api.AllGather = reinterpret_cast<decltype(api.AllGather)>(dlsym(api.handle, "ncclAllGather"));
-        api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(dlsym(api.handle, "ncclGetErrorString"));
-        api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.AllGather && api.GetErrorString;
-    });
-    if (!api.ok) {
-        set_error("RCCL is not available: %s", api.handle ? "librccl lacks a required symbol" : "librccl.so[.1] could not be loaded");
-        return nullptr;
-    }
-    return &api;
-}
-
-#define INNR_RCCL_CHECK(api, expr)                                                                 \
-    do {                                                                                           \
-        ncclResult_t _r = (expr);                                                                  \
-        if (_r != ncclSuccess) {                                                                   \
-            ::innr::set_error("%s failed: %s (%s:%d)", #expr, (api)->GetErrorString(_r), __FILE__, __LINE__); \
-            return INNR_E_RCCL;                                                                    \
-        }                                                                                          \
-    } while (0)
-
-// a shard's kNN result -> its exchange block (include/innr_hip.h): one thread per (query, slot)
-__global__ void pack_topk_kernel(const uint64_t* __restrict__ idx, const float* __restrict__ score, uint64_t index_base,
-                                 uint64_t shard_vectors, uint32_t Q, uint32_t kin, uint32_t k, uint64_t* __restrict__ block) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t == 0) {
-        block[0] = index_base;
-        block[1] = shard_vectors;
-    }
-    if (t >= (size_t)Q * k) return;
-    const uint32_t q = (uint32_t)(t / k), r = (uint32_t)(t % k);
-    uint64_t e = 0xFFFFFFFFull;  // no candidate
-    if (r < kin) {
-        const uint64_t g = idx[(size_t)q * kin + r];
-        const uint64_t local = g - index_base;
-        if (g >= index_base && local < 0xFFFFFFFFull)
-            e = ((uint64_t)__float_as_uint(score[(size_t)q * kin + r]) << 32) | local;
-    }
-    block[2 + t] = e;
-}
-
-// A rank whose local search FAILED still takes part in the all-gather -- with this block: header word 1 = all ones (no shard holds
-// 2^64 - 1 vectors), word 0 = the negated status, no candidates. Every rank then sees the flag in the gathered headers and returns
-// an error instead of waiting in a collective its peer never enters.
-constexpr uint64_t kBlockFailed = ~0ull;
-__global__ void pack_error_kernel(uint64_t code, uint32_t Q, uint32_t k, uint64_t* __restrict__ block) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t == 0) {
-        block[0] = code;
-        block[1] = kBlockFailed;
-    }
-    if (t < (size_t)Q * k) block[2 + t] = 0xFFFFFFFFull;
-}
-
-// G gathered blocks -> best kout per query; one wave per query, rank counting on (preference, global index) like
-// merge_topk_kernel (kernels_topk.h). The query's G*k candidates are staged in LDS once (dynamic shared memory: total x
-// {u32 preference, u64 global index}); beyond `lds_entries` they are re-read from global memory per comparison (L2-resident).
-// err (nullable): bit 0 set when a block's header carries the failure flag (err[1 + g] = its code), bit 1 when the headers'
-// vector counts do not add up to `expect_total` (the caller's cached figure is stale).
-__global__ __launch_bounds__(64) void merge_blocks_kernel(const uint64_t* __restrict__ blocks, uint32_t G, uint32_t Q, uint32_t k,
-                                                          uint32_t kout, bool smaller_is_better, uint64_t* __restrict__ out_idx,
-                                                          float* __restrict__ out_score, uint32_t lds_entries, uint64_t expect_total,
-                                                          uint32_t* __restrict__ err) {
-    extern __shared__ uint64_t merge_lds[];
-    const uint32_t q = blockIdx.x;
-    const uint32_t total = G * k;
-    const size_t words = 2 + (size_t)Q * k;
-    const int lane = threadIdx.x;
-    if (err && q == 0) {
-        uint64_t sum = 0;
-        bool failed = false;
-        for (uint32_t g = lane; g < G; g += 64) {
-            const uint64_t n = blocks[(size_t)g * words + 1];
-            if (n == kBlockFailed) {
-                failed = true;
-                err[1 + (g < 62 ? g : 62)] = (uint32_t)blocks[(size_t)g * words];
-            } else {
-                sum += n;
-            }
-        }
-        for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor((unsigned long long)sum, off, 64);
-        if (__any(failed)) { if (lane == 0) atomicOr(err, 1u); }
-        else if (expect_total != sum && lane == 0) atomicOr(err, 2u);
-    }
-    const bool staged = total <= lds_entries;
-    uint64_t* s_idx = merge_lds;                                            // [total]
-    uint32_t* s_pref = reinterpret_cast<uint32_t*>(merge_lds + (staged ? total : 0));  // [total]
-    auto fetch = [&](uint32_t c, uint64_t* gi, uint32_t* pf, float* sf) {
-        const uint32_t g = c / k, r = c % k;
-        const uint64_t* blk = blocks + (size_t)g * words;
-        const uint64_t e = blk[2 + (size_t)q * k + r];
-        const bool valid = (uint32_t)e != 0xFFFFFFFFu && blk[1] != kBlockFailed;
-        *gi = valid ? blk[0] + (uint32_t)e : ~0ull;
-        *sf = __uint_as_float((uint32_t)(e >> 32));
-        *pf = !valid ? 0u : (smaller_is_better ? ~f32_ord(*sf) : f32_ord(*sf));
-    };
-    if (staged) {
-        for (uint32_t c = lane; c < total; c += 64) {
-            float sf;
-            fetch(c, &s_idx[c], &s_pref[c], &sf);
-        }
-        __syncthreads();
-    }
-    for (uint32_t c = lane; c < total; c += 64) {
-        uint64_t my_i;
-        uint32_t my_p;
-        float my_sf;
-        fetch(c, &my_i, &my_p, &my_sf);
-        uint32_t rank = 0;
-        if (staged) {
-            for (uint32_t o = 0; o < total; ++o) {
-                const uint32_t p = s_pref[o];
-                const uint64_t i2 = s_idx[o];
-                rank += (p > my_p || (p == my_p && (i2 < my_i || (i2 == my_i && o < c)))) ? 1u : 0u;
-            }
-        } else {
-            for (uint32_t o = 0; o < total; ++o) {
-                uint64_t i2;
-                uint32_t p;
-                float sf;
-                fetch(o, &i2, &p, &sf);
-                rank += (p > my_p || (p == my_p && (i2 < my_i || (i2 == my_i && o < c)))) ? 1u : 0u;
-            }
-        }
-        if (rank < kout) {
-            out_idx[(size_t)q * kout + rank] = my_i;
-            out_score[(size_t)q * kout + rank] = my_sf;
-        }
-    }
-}
-
-}  // namespace innr
-
-struct innr_comm {
-    innr_ctx* ctx = nullptr;
-    ncclComm_t comm = nullptr;
-    bool owned = false;
-    int rank = 0, world = 1;
-    DevBuf block, all, loc_idx, loc_sc, hdr;  // this rank's block, the gathered blocks, the local top-k
-    // Vectors in all shards, learnt from the first exchange's headers: shard sizes are fixed once the shards are attached, so
-    // later calls launch the merge without a host round trip; the merge kernel re-checks the sum and flags a stale figure.
-    // A stale figure LARGER than the truth would let that first merge write min(k, total) entries per query into buffers the
-    // caller sized for the true total: the figure is dropped here, on the host, whenever this rank's own shard is not the one
-    // it was learnt with (total_shard_n) -- e.g. one communicator serving a large and then a small shard.
-    bool have_total = false;
-    uint64_t total = 0, total_shard_n = 0;
-    bool broken = false;  // a collective failed: the communicator is aborted, not destroyed
-};
-
-extern "C" {
-
-innr_status innr_comm_unique_id(void* id_out) {
-    if (!id_out) return INNR_E_BAD_ARG;
-    RcclApi* api = load_rccl();
-    if (!api) return INNR_E_RCCL;
-    static_assert(sizeof(ncclUniqueId) == INNR_COMM_ID_BYTES, "INNR_COMM_ID_BYTES must equal NCCL_UNIQUE_ID_BYTES");
-    ncclUniqueId id;
-    INNR_RCCL_CHECK(api, api->GetUniqueId(&id));
-    memcpy(id_out, &id, sizeof(id));
-    return INNR_OK;
-}
-
-innr_status innr_comm_create(innr_ctx* ctx, const void* id, int rank, int world, innr_comm** out) {
-    if (!ctx || !id || !out || world < 1 || rank < 0 || rank >= world) {
-        set_error("innr_comm_create: bad ctx / id / rank %d of %d", rank, world);
-        return INNR_E_BAD_ARG;
-    }
-    RcclApi* api = load_rccl();
-    if (!api) return INNR_E_RCCL;
-    INNR_ENTER(ctx);
-    innr_comm* cm = new (std::nothrow) innr_comm();
-    if (!cm) return INNR_E_OOM;
-    cm->ctx = ctx;
-    cm->rank = rank;
-    cm->world = world;
-    ncclUniqueId uid;
-    memcpy(&uid, id, sizeof(uid));
-    const ncclResult_t r = api->CommInitRank(&cm->comm, world, uid, rank);  // collective: returns once every rank has joined
-    if (r != ncclSuccess) {
-        set_error("ncclCommInitRank(rank %d of %d) failed: %s", rank, world, api->GetErrorString(r));
-        delete cm;
-        return INNR_E_RCCL;
-    }
-    cm->owned = true;
-    *out = cm;
-    return INNR_OK;
-}
-
-innr_status innr_comm_attach(innr_ctx* ctx, void* nccl_comm, int rank, int world, innr_comm** out) {
-    if (!ctx || !nccl_comm || !out || world < 1 || rank < 0 || rank >= world) return INNR_E_BAD_ARG;
-    if (!load_rccl()) return INNR_E_RCCL;
-    innr_comm* cm = new (std::nothrow) innr_comm();
-    if (!cm) return INNR_E_OOM;
-    cm->ctx = ctx;
-    cm->comm = static_cast<ncclComm_t>(nccl_comm);
-    cm->rank = rank;
-    cm->world = world;
-    *out = cm;
-    return INNR_OK;
-}
-
-void innr_comm_destroy(innr_comm* cm) {
-    if (!cm) return;
-    {
-        CtxGuard guard(cm->ctx);
-        if (cm->ctx) {
-            (void)hipSetDevice(cm->ctx->device);
-            (void)ctx_sync(cm->ctx);
-        }
-        if (cm->owned && cm->comm) {
-            RcclApi* api = load_rccl();
-            if (api && cm->broken && api->CommAbort) (void)api->CommAbort(cm->comm);  // peers may never enter a matching destroy
-            else if (api) (void)api->CommDestroy(cm->comm);
-        }
-        DevBuf* bufs[] = {&cm->block, &cm->all, &cm->loc_idx, &cm->loc_sc, &cm->hdr};
-        for (DevBuf* b : bufs) b->release();
-    }
-    delete cm;
-}
-
-int innr_comm_rank(const innr_comm* cm) { return cm ? cm->rank : -1; }
-int innr_comm_world(const innr_comm* cm) { return cm ? cm->world : 0; }
-
-size_t innr_topk_block_words(size_t Q, size_t k) { return 2 + Q * k; }
-
-innr_status innr_topk_pack_dev(innr_ctx* ctx, const uint64_t* d_idx, const float* d_score, uint64_t index_base,
-                               uint64_t shard_vectors, size_t Q, size_t kin, size_t k, uint64_t* d_block) {
-    if (!ctx || !d_block || kin > k || (Q * kin && (!d_idx || !d_score)) || Q * k >= 0xFFFFFFFFull) return INNR_E_BAD_ARG;
-    INNR_ENTER(ctx);
-    const size_t n = std::max<size_t>(Q * k, 1);
-    pack_topk_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_idx, d_score, index_base, shard_vectors, (uint32_t)Q,
-                                                                         (uint32_t)kin, (uint32_t)k, d_block);
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
-}
-
-innr_status innr_allgather_topk_dev(innr_comm* cm, const uint64_t* d_block, size_t Q, size_t k, uint64_t* d_all_blocks) {
-    if (!cm || !cm->comm || !d_block || !d_all_blocks) return INNR_E_BAD_ARG;
-    RcclApi* api = load_rccl();
-    if (!api) return INNR_E_RCCL;
-    INNR_ENTER(cm->ctx);
-    const size_t bytes = innr_topk_block_words(Q, k) * sizeof(uint64_t);
-    const ncclResult_t r = api->AllGather(d_block, d_all_blocks, bytes, ncclUint8, cm->comm, cm->ctx->stream);
-    if (r != ncclSuccess) {
-        cm->broken = true;
-        set_error("ncclAllGather failed: %s", api->GetErrorString(r));
-        return INNR_E_RCCL;
-    }
-    return INNR_OK;
-}
-
-}  // extern "C"
-
-namespace innr {
-constexpr uint32_t kMergeErrWord = 96;  // c->flags words [96, 160): the merge kernel's report (flag, then one code per rank)
-// launch the merge; LDS staging for up to 3072 candidates per query (36 KiB)
-static innr_status launch_merge_blocks(innr_ctx* c, int metric, const uint64_t* d_all, size_t G, size_t Q, size_t k, size_t kout,
-                                       uint64_t* d_out_idx, float* d_out_score, uint64_t expect_total, bool report) {
-    const uint32_t lds_entries = 3072;
-    const size_t total = G * k;
-    const size_t shmem = total <= lds_entries ? total * 12 + 8 : 0;
-    uint32_t* err = report ? c->flags.as<uint32_t>() + kMergeErrWord : nullptr;
-    if (report) INNR_HIP_CHECK(hipMemsetAsync(err, 0, 64 * sizeof(uint32_t), c->stream));
-    merge_blocks_kernel<<<(unsigned)Q, 64, shmem, c->stream>>>(d_all, (uint32_t)G, (uint32_t)Q, (uint32_t)k, (uint32_t)kout,
-                                                             metric == INNR_METRIC_L2SQ, d_out_idx, d_out_score, lds_entries,
-                                                             expect_total, err);
-    INNR_HIP_CHECK(hipGetLastError());
-    return INNR_OK;
-}
-static innr_status failed_rank_error(const uint64_t* hdr, size_t G) {
-    for (size_t g = 0; g < G; ++g)
-        if (hdr[2 * g + 1] == kBlockFailed) {
-            set_error("rank %zu of the sharded call failed its local search (status %d): no rank has a result", g, -(int)(int64_t)hdr[2 * g]);
-            return INNR_E_RCCL;
-        }
-    return INNR_OK;
-}
-}  // namespace innr
-
-extern "C" {
-
-innr_status innr_merge_blocks_dev(innr_ctx* ctx, int metric, const uint64_t* d_all_blocks, size_t G, size_t Q, size_t k,
-                                  uint64_t* d_out_idx, float* d_out_score, size_t* out_k) {
-    if (!ctx || !out_k || !metric_ok(metric) || G == 0 || !d_all_blocks) return INNR_E_BAD_ARG;
-    *out_k = 0;
-    if (Q == 0 || k == 0) return INNR_OK;
-    if (G * k >= 0xFFFFFFFFull || Q >= 0xFFFFFFFFull) return INNR_E_UNSUPPORTED;
-    INNR_ENTER(ctx);
-    // k' = min(k, vectors in all shards): the shard sizes travel in the blocks' headers (a caller without an innr_comm has
-    // nowhere to cache them: one host round trip; innr_sharded_* caches them in its communicator)
-    const size_t words = innr_topk_block_words(Q, k);
-    std::vector<uint64_t> hdr(2 * G);
-    INNR_HIP_CHECK(hipMemcpy2DAsync(hdr.data(), 16, d_all_blocks, words * sizeof(uint64_t), 16, G, hipMemcpyDeviceToHost, ctx->stream));
-    INNR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    INNR_TRY(failed_rank_error(hdr.data(), G));  // a rank that failed locally says so in its header: every rank returns an error
-    uint64_t total = 0;
-    for (size_t g = 0; g < G; ++g) total += hdr[2 * g + 1];
-    const size_t kout = (size_t)std::min<uint64_t>(k, total);
-    if (kout == 0) return INNR_OK;
-    if (!d_out_idx || !d_out_score) return INNR_E_BAD_ARG;
-    INNR_TRY(launch_merge_blocks(ctx, metric, d_all_blocks, G, Q, k, kout, d_out_idx, d_out_score, total, false));
-    INNR_HIP_CHECK(ctx_sync(ctx));
-    *out_k = kout;
-    return INNR_OK;
-}
-
-}  // extern "C"
-
-namespace innr {
-// Exchange + merge of the sharded calls. local_status: what this rank's local search returned (its results, if any, are at
-// cm->loc_idx / cm->loc_sc with `kin` entries per query). The collective is SYMMETRIC: a failing rank gathers an error block.
-static innr_status sharded_exchange(innr_comm* cm, innr_status local_status, int metric, uint64_t index_base, uint64_t shard_n,
-                                    size_t Q, size_t kin, size_t k, uint64_t* d_out_idx, float* d_out_score, size_t* out_k) {
-    innr_ctx* c = cm->ctx;
-    const size_t words = innr_topk_block_words(Q, k);
-    char local_msg[512];
-    if (local_status != INNR_OK) {
-        snprintf(local_msg, sizeof(local_msg), "%s", innr_last_error());
-        const size_t n = std::max<size_t>(Q * k, 1);
-        pack_error_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>((uint64_t)(int64_t)(-local_status), (uint32_t)Q, (uint32_t)k,
-                                                                            cm->block.as<uint64_t>());
-        INNR_HIP_CHECK(hipGetLastError());
-    } else {
-        INNR_TRY(innr_topk_pack_dev(c, cm->loc_idx.as<uint64_t>(), cm->loc_sc.as<float>(), index_base, shard_n, Q, kin, k,
-                                    cm->block.as<uint64_t>()));
-    }
-    INNR_TRY(innr_allgather_topk_dev(cm, cm->block.as<uint64_t>(), Q, k, cm->all.as<uint64_t>()));
-    const size_t G = (size_t)cm->world;
-    if (cm->have_total && cm->total_shard_n != shard_n) cm->have_total = false;  // another shard than the cached total was learnt with
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (!cm->have_total) {  // first exchange (or the cached figure went stale): learn the shard sizes from the headers
-            std::vector<uint64_t> hdr(2 * G);
-            INNR_HIP_CHECK(hipMemcpy2DAsync(hdr.data(), 16, cm->all.p, words * sizeof(uint64_t), 16, G, hipMemcpyDeviceToHost, c->stream));
-            INNR_HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (local_status != INNR_OK) {
-                set_error("%s", local_msg);
-                return local_status;
-            }
-            INNR_TRY(failed_rank_error(hdr.data(), G));
-            cm->total = 0;
-            for (size_t g = 0; g < G; ++g) cm->total += hdr[2 * g + 1];
-            cm->total_shard_n = shard_n;
-            cm->have_total = true;
-        }
-        const size_t kout = (size_t)std::min<uint64_t>(k, cm->total);
-        if (kout && (!d_out_idx || !d_out_score)) return INNR_E_BAD_ARG;
-        if (kout) INNR_TRY(launch_merge_blocks(c, metric, cm->all.as<uint64_t>(), G, Q, k, kout, d_out_idx, d_out_score, cm->total, true));
-        uint32_t rep[64] = {0};
-        if (kout) INNR_HIP_CHECK(copy_out(c, rep, c->flags.as<uint32_t>() + kMergeErrWord, sizeof(rep)));
-        INNR_HIP_CHECK(ctx_sync(c));  // the one synchronisation of the call: results complete, the merge's report on the host
-        if (local_status != INNR_OK) {
-            set_error("%s", local_msg);
-            return local_status;
-        }
-        if (rep[0] & 1u) {
-            for (size_t g = 0; g < G && g < 63; ++g)
-                if (rep[1 + g]) {
-                    set_error("rank %zu of the sharded call failed its local search (status %d): no rank has a result", g, -(int)rep[1 + g]);
-                    return INNR_E_RCCL;
-                }
-            set_error("a rank of the sharded call failed its local search: no rank has a result");
-            return INNR_E_RCCL;
-        }
-        if (rep[0] & 2u) {  // shard sizes changed since they were cached: read them again and merge once more
-            cm->have_total = false;
-            continue;
-        }
-        *out_k = kout;
-        return INNR_OK;
-    }
-    set_error("internal: shard sizes changed during a sharded call");
-    return INNR_E_HIP;
-}
-}  // namespace innr
-
-extern "C" {
-
-innr_status innr_sharded_knn_dev(innr_comm* cm, innr_batch* shard, int metric, const float* d_queries, size_t Q, size_t D,
-                                 size_t k, int engine, uint64_t* d_out_idx, float* d_out_score, size_t* out_k,
-                                 innr_knn_stats* stats) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!cm || !shard || !out_k || shard->ctx != cm->ctx) {
-        set_error("innr_sharded_knn_dev: null comm / shard, or the shard lives on another context");
-        return INNR_E_BAD_ARG;
-    }
-    *out_k = 0;
-    if (Q == 0 || k == 0) return INNR_OK;  // nothing to exchange (every rank takes this branch: same arguments)
-    if (k > ((size_t)1 << 20) || Q * k >= 0xFFFFFFFFull) {
-        set_error("innr_sharded_knn_dev: k=%zu: at most 2^20 candidates per shard and query (and 2^32 per call) are exchanged", k);
-        return INNR_E_UNSUPPORTED;  // (the same on every rank: same arguments)
-    }
-    innr_ctx* c = cm->ctx;
-    INNR_ENTER(c);
-    const size_t words = innr_topk_block_words(Q, k);
-    // Workspace failures are rank-local too, but without the block there is nothing to gather: they are returned at once
-    // (a few MB against a shard of tens of GB; the peers' collective then times out in RCCL, INNR_E_RCCL there).
-    INNR_TRY(cm->loc_idx.ensure(Q * k * sizeof(uint64_t)));
-    INNR_TRY(cm->loc_sc.ensure(Q * k * sizeof(float)));
-    INNR_TRY(cm->block.ensure(words * sizeof(uint64_t)));
-    INNR_TRY(cm->all.ensure((size_t)cm->world * words * sizeof(uint64_t)));
-    size_t kin = 0;
-    const bool u8 = shard->C8 != nullptr && shard->V == nullptr;
-    // The local search. Its failure -- a filter copy that does not fit on THIS rank, a broken list invariant, a dimension
-    // mismatch -- does not end the call here: the rank gathers an error block, and every rank returns an error.
-    innr_status ls;
-    if (u8) ls = innr_batch_knn_u8_dev(shard, d_queries, Q, D, k, engine, cm->loc_idx.as<uint64_t>(), cm->loc_sc.as<float>(), &kin, stats);
-    else ls = innr_batch_knn_dev(shard, metric, d_queries, Q, D, k, engine, cm->loc_idx.as<uint64_t>(), cm->loc_sc.as<float>(), &kin, stats);
-    if (ls == INNR_OK && c->tune.fail_local_search) {  // test switch: this rank pretends its local search failed
-        set_error("local search failed on request (option fail_local_search)");
-        ls = INNR_E_HIP;
-    }
-    return sharded_exchange(cm, ls, u8 ? INNR_METRIC_DOT : metric, shard->index_base, shard->N, Q, kin, k, d_out_idx, d_out_score, out_k);
-}
-
-innr_status innr_sharded_knn(innr_comm* cm, innr_batch* shard, int metric, const float* queries, size_t Q, size_t D, size_t k,
-                             int engine, uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!cm || !shard || !out_k || shard->ctx != cm->ctx) return INNR_E_BAD_ARG;
-    *out_k = 0;
-    if (Q == 0 || k == 0) return INNR_OK;
-    if ((!queries && D) || !out_idx || !out_score) return INNR_E_BAD_ARG;
-    return knn_from_host(cm->ctx, queries, Q, D, k, out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
-        return innr_sharded_knn_dev(cm, shard, metric, dQ, Q, D, k, engine, di, ds, out_k, stats);
-    });
-}
-
-// maxsim over a document corpus range-partitioned across the ranks (maxsim.rs:96-137 per document; SURVEY.md 8e "same scheme
-// for maxsim"): this rank's innr_maxsim_topk on its shard, then the SAME exchange -- one block of 2 + k words, one ncclAllGather,
-// one merge by (score, global document index). The query (host, [Tq*dim], identical on every rank) and the outputs (host, [k'])
-// follow innr_maxsim_topk.
-innr_status innr_sharded_maxsim(innr_comm* cm, innr_docs* shard, int cosine, const float* qtok, size_t Tq, size_t dim, size_t k,
-                                int engine, uint64_t* out_doc, float* out_score, size_t* out_k, innr_knn_stats* stats) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!cm || !shard || !out_k || shard->ctx != cm->ctx) {
-        set_error("innr_sharded_maxsim: null comm / shard, or the shard lives on another context");
-        return INNR_E_BAD_ARG;
-    }
-    *out_k = 0;
-    if (k == 0) return INNR_OK;
-    if (k > ((size_t)1 << 20)) {
-        set_error("innr_sharded_maxsim: k=%zu: at most 2^20 candidates per shard are exchanged", k);
-        return INNR_E_UNSUPPORTED;
-    }
-    if (!out_doc || !out_score) return INNR_E_BAD_ARG;
-    innr_ctx* c = cm->ctx;
-    INNR_ENTER(c);
-    const size_t words = innr_topk_block_words(1, k);
-    INNR_TRY(cm->loc_idx.ensure(k * sizeof(uint64_t)));
-    INNR_TRY(cm->loc_sc.ensure(k * sizeof(float)));
-    INNR_TRY(cm->block.ensure(words * sizeof(uint64_t)));
-    INNR_TRY(cm->all.ensure((size_t)cm->world * words * sizeof(uint64_t)));
-    INNR_TRY(c->out_idx.ensure(k * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(k * sizeof(float)));
-    size_t kin = 0;
-    innr_status ls = maxsim_topk_impl(shard, cosine, qtok, Tq, dim, k, engine, nullptr, nullptr, &kin, stats, false);
-    if (ls == INNR_OK && c->tune.fail_local_search) {
-        set_error("local search failed on request (option fail_local_search)");
-        ls = INNR_E_HIP;
-    }
-    if (ls == INNR_OK && kin) {  // an empty shard (ndocs == 0) returns kin = 0 and gathers a block without candidates
-        INNR_HIP_CHECK(hipMemcpyAsync(cm->loc_idx.p, c->out_idx.p, kin * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-        INNR_HIP_CHECK(hipMemcpyAsync(cm->loc_sc.p, c->out_score.p, kin * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    }
-    size_t kout = 0;
-    INNR_TRY(sharded_exchange(cm, ls, INNR_METRIC_DOT, shard->index_base, shard->ndocs, 1, kin, k, c->out_idx.as<uint64_t>(),
-                              c->out_score.as<float>(), &kout));
-    if (kout) {
-        INNR_HIP_CHECK(copy_out(c, out_doc, c->out_idx.p, kout * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, kout * sizeof(float)));
-        INNR_HIP_CHECK(ctx_sync(c));
-    }
-    *out_k = kout;
     return INNR_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "common.h"
+#include "topk_dev.h"
 
 namespace innr {
 

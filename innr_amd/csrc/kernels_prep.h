@@ -10,25 +10,6 @@
 
 namespace innr {
 
-// examples/batch_demo.rs:233-242 generate_embedding(dim, seed)[d], bit-exact:
-//   x = seed*6364136223846793005 + d*1442695040888963407 (wrapping u64)
-//   v = ((x >> 33) as f32 / 2^31) * 2.0 - 1.0
-__device__ __forceinline__ float lcg_embedding(uint64_t seed, uint32_t d) {
-    const uint64_t x = seed * 6364136223846793005ull + (uint64_t)d * 1442695040888963407ull;
-    const float f = __uint2float_rn((uint32_t)(x >> 33));  // < 2^31, round-to-nearest-even like `as f32`
-    return ex::sub(ex::mul(ex::mul(f, 4.656612873077393e-10f /* 2^-31: exact divide */), 2.0f), 1.0f);
-}
-
-// i.i.d. uniform[-1,1): splitmix64 finaliser of the element index, top 24 bits -> k*2^-23 - 1 (exact in f32).
-// Same stream as the CPU checker's orc_uniform_elem (distribution of benches/batch.rs:11-21).
-__device__ __forceinline__ float uniform_embedding(uint64_t seed, uint64_t row, uint32_t D, uint32_t d) {
-    uint64_t z = seed * 0xD1342543DE82EF95ull + (row * (uint64_t)D + d) + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return ex::sub(ex::mul(__uint2float_rn((uint32_t)(z >> 40)), 1.1920928955078125e-07f /* 2^-23 */), 1.0f);
-}
-
 // one thread = 4 consecutive vectors of one dimension row.
 // GEN 0: row i = generate_embedding(D, seed + i) (the reference example's generator);
 // GEN 1: row i = uniform stream `seed`, row index row0 + i.

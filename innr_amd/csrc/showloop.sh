@@ -1,6 +1,7 @@
 #!/bin/bash
-# usage: showloop.sh <mangled-prefix>   -- condensed view of the first depth-1 loop of a kernel in ../lib/asm/api.s
-S=../lib/asm/api.s
+# usage: showloop.sh <mangled-prefix> [lines] [listing]   -- condensed view of the first depth-1 loop of a kernel in a listing of
+# `make asm` (default ../lib/asm/api.s; the maxsim kernels are in maxsim.s, the exchange kernels in comm.s)
+S=${3:-../lib/asm/api.s}
 N=$(grep -n "^$1.*:" $S | head -1 | cut -d: -f1)
 [ -z "$N" ] && { echo "kernel not found"; exit 1; }
 tail -n +$N $S | awk '/s_endpgm/{print; exit} {print}' > /tmp/kern.s

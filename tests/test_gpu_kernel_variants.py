@@ -1,7 +1,7 @@
 """GPU tests of the kernel INSTANTIATIONS behind the f32 / bf16 / split-bf16 GEMM filters, the int8 filter and the maxsim entry
 points: one case per instantiation a public call (or, for the dense-score dump mode, a hook of the test-hooks library) can reach.
 Every case (1) compares the call's answer with the CPU oracle bit for bit and (2) asserts, through the context's
-launch record (api.hip: innr_ctx::launch_log, written at every templated dispatch, read by the hook innrdbg_launch_log of the
+launch record (api_internal.h: innr_ctx::launch_log, written at every templated dispatch, read by the hook innrdbg_launch_log of the
 test-hooks library), that the instantiation it is named after really served the call -- a dispatch that silently declines (an
 unseeded corpus, a K-step count without an instantiation, ...) fails the case instead of passing on another kernel's answer.
 
@@ -38,15 +38,15 @@ def _oracle_knn_u8(q, codes, alpha, offset, k):
 
 # ------------------------------------------------------------------------------- the launch record
 FAMILIES = {1: "gemm_f32", 2: "gemm_bf16", 3: "gemm_split", 4: "i8_one", 5: "i8_two", 6: "i8_small", 7: "ms_scan", 8: "ms_tile",
-            9: "ms_generic", 10: "ms_rerank", 11: "range_scan"}  # api.hip LaunchFamily
+            9: "ms_generic", 10: "ms_rerank", 11: "range_scan"}  # api_internal.h LaunchFamily
 _REC = np.dtype({"names": ["family", "lockstep", "arg", "groups"], "formats": ["u1", "u1", ("<i2", (4,)), "<u4"],
-                 "offsets": [0, 1, 2, 12], "itemsize": 16})  # api.hip LaunchRec (the C layout: groups aligned to 4 bytes)
-LOG_CAP = 64  # api.hip kLaunchLogCap
+                 "offsets": [0, 1, 2, 12], "itemsize": 16})  # api_internal.h LaunchRec (the C layout: groups aligned to 4 bytes)
+LOG_CAP = 64  # api_internal.h kLaunchLogCap
 
 
 class Launch(NamedTuple):
     family: str     # FAMILIES
-    args: tuple     # the template arguments in the order api.hip's LaunchFamily comments give, without trailing unused ones
+    args: tuple     # the template arguments in the order api_internal.h's LaunchFamily comments give, without trailing unused ones
     groups: int     # query groups of the launch (maxsim: queries per corpus pass)
     lockstep: bool  # gemm_i8s_filter_kernel: the soft-lockstep buffer was passed
 

@@ -383,8 +383,8 @@ def test_device_entry_equals_host_entry(B, engine):
 
 # ------------------------------------------------------------------------------------------------ 8. which kernel ran
 _REC = np.dtype({"names": ["family", "lockstep", "arg", "groups"], "formats": ["u1", "u1", ("<i2", (4,)), "<u4"],
-                 "offsets": [0, 1, 2, 12], "itemsize": 16})  # api.hip LaunchRec
-GEMM_F32, RANGE_SCAN = 1, 11                                 # api.hip LaunchFamily
+                 "offsets": [0, 1, 2, 12], "itemsize": 16})  # api_internal.h LaunchRec
+GEMM_F32, RANGE_SCAN = 1, 11                                 # api_internal.h LaunchFamily
 
 
 def _logged(call):
