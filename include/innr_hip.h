@@ -337,6 +337,33 @@ innr_status innr_batch_range_search(innr_batch* b, int metric, const float* quer
 innr_status innr_batch_range_search_dev(innr_batch* b, int metric, const float* d_queries, size_t Q, size_t D,
                                         const float* d_thresholds, int engine, uint64_t* d_out_offsets, uint64_t* d_out_idx,
                                         float* d_out_score, size_t cap, size_t* out_total, innr_knn_stats* stats);
+/* batch_knn_adaptive (batch.rs:441-564) for each of Q queries (row-major [Q*D]; Q = 1 is the reference call): squared L2 with a
+ * warm-up over the first min(warmup_dims, D) dimensions, a prune against the extrapolated k-th warm-up distance, then the
+ * remaining dimensions for the survivors only, pruned against a threshold that is renewed after every dimension d with
+ * d % 32 == 0 and never below k live vectors. The function is the reference's HEURISTIC, not an exact k-NN: its survivors depend
+ * on the corpus order, and on data whose early dimensions do not carry the variance its recall against innr_batch_knn is poor.
+ * The contract is the reference's answer for each query alone, bit for bit: the same indices in the same order (distance by
+ * f32::total_cmp, ties to the lower index), the same score bits (every distance includes all D dimensions, accumulated as
+ * innr_batch_scores(INNR_METRIC_L2SQ) does). DESIGN.md 4.5d restates the sequential loop as the phases the device runs.
+ * Writes k' = min(k, N) results per query to out_idx[q*k' + r], out_score[q*k' + r]; *out_k = k'; indices = index base + local
+ * index. Any k is accepted. On a prefix view D and the extrapolation factor D / warmup_dims are the view's.
+ * Order of the checks (batch.rs:447-463): a null batch or out_k, a u8 code batch: INNR_E_BAD_ARG; D != the batch's:
+ * INNR_E_DIM_MISMATCH; warmup_dims == 0: INNR_E_DIM_MISMATCH, "warmup_dims must be > 0" (the reference's assert!, mapped as
+ * innr_batch_quantile_range maps its panic); N == 0, k == 0 or Q == 0: *out_k = 0; null queries / outputs with work to do:
+ * INNR_E_BAD_ARG; D == 0: indices 0 .. k'-1 with scores 0.0.
+ * stats: engine = INNR_KNN_EXACT, queries_fallback = 0, candidates_kept = the largest number of vectors alive after the
+ * warm-up prune over the queries, gemm_ms = device time of the warm-up scans, total_ms = the whole call.
+ * Queries run one after another; each synchronises with the host once after its warm-up prune and once per later segment that
+ * still prunes (usually one or two). Memory, from the context's grow-only workspace (innr_ctx_memory reports it, innr_ctx_trim
+ * returns it): of the order of 8*N bytes, for the one query in flight -- 4*N of warm-up distances, 8*N of sort keys, N/16 of counts,
+ * and 17 bytes per vector alive after the warm-up prune.
+ * Out of scope: sharing the warm-up pass between queries, a sharded variant, u8 code batches, other metrics (the reference's
+ * function is squared L2 only), and any change to the heuristic. */
+innr_status innr_batch_knn_adaptive(innr_batch* b, const float* queries, size_t Q, size_t D, size_t k, size_t warmup_dims,
+                                    uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats);
+/* same, queries and outputs resident on the device (innr_batch_knn_dev's conventions) */
+innr_status innr_batch_knn_adaptive_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, size_t k, size_t warmup_dims,
+                                        uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats);
 
 /* ---- pairwise surface kept on the host: called per PAIR by graph indexes, so a kernel
  * launch cannot pay for itself. Plain host functions in the reference's portable arithmetic order. ------------ */

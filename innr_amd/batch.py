@@ -8,7 +8,7 @@ A reference panic (assert_eq! on a dimension mismatch) is raised as InnrPanic (a
 Vec<f32> <-> numpy float32 arrays; `_into` variants refill a caller-owned Python list in place.
 
 Additions (the reference has no multi-query API; parity = "the reference called in a loop"):
-  batch_knn_dot_multi / batch_knn_cosine_multi / batch_knn_multi.
+  batch_knn_dot_multi / batch_knn_cosine_multi / batch_knn_multi / batch_knn_adaptive_multi.
 
 Every computation runs on the GPU through include/innr_hip.h; nothing here computes scores on the CPU.
 """
@@ -539,3 +539,58 @@ def batch_range_search(queries, batch: VerticalBatch, thresholds, metric: int = 
         idx, sc = call(room)
     r = min(int(total.value), room)
     return off, idx[:r], sc[:r]
+
+
+def batch_knn_adaptive_multi(queries, batch: VerticalBatch, k: int, warmup_dims: int, stats: Optional[KnnStats] = None):
+    """batch_knn_adaptive (batch.rs:441-564) for each of Q queries (innr_batch_knn_adaptive): every query's result is the
+    reference's for that query alone, bit for bit -- the heuristic included. Returns (indices uint64 [Q, k'], scores float32
+    [Q, k']) with k' = min(k, N). Torch device tensors (queries on the batch's GPU) take the device entry point: the results
+    stay there (int64 / float32 tensors). stats.candidates_kept: the most vectors alive after any query's warm-up prune."""
+    n = batch.num_vectors()
+    if int(warmup_dims) < 0:
+        raise OverflowError("warmup_dims is a usize")
+    st = stats if stats is not None else KnnStats()
+    out_k = C.c_size_t(0)
+    kk = min(int(k), n)
+    if hasattr(queries, "is_cuda") and queries.is_cuda:
+        import torch
+        q = queries.to(torch.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        q = q.contiguous()
+        nq, d = q.shape
+        if d != batch.dimension():
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {d}\n right: {batch.dimension()}")
+        if int(warmup_dims) == 0:
+            raise InnrPanic("warmup_dims must be > 0")
+        batch._ctx.bind_torch_stream()  # the queries were produced on torch's stream, the results are consumed there
+        idx = torch.empty((max(nq * kk, 1),), dtype=torch.int64, device=q.device)
+        sc = torch.empty((max(nq * kk, 1),), dtype=torch.float32, device=q.device)
+        check(load().innr_batch_knn_adaptive_dev(batch._h, C.c_void_p(q.data_ptr()) if q.numel() else None, nq, d, int(k),
+                                                 int(warmup_dims), C.c_void_p(idx.data_ptr()), C.c_void_p(sc.data_ptr()),
+                                                 C.byref(out_k), C.byref(st)))
+        r = int(out_k.value)
+        return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+    q = _f32(queries)
+    if q.ndim == 1:
+        q = q.reshape(1, -1)
+    nq, d = q.shape
+    if d != batch.dimension():  # assert_eq!(query.len(), batch.dimension), batch.rs:447
+        raise InnrPanic(f"assertion `left == right` failed\n  left: {d}\n right: {batch.dimension()}")
+    if int(warmup_dims) == 0:  # assert!(warmup_dims > 0, ..), batch.rs:448
+        raise InnrPanic("warmup_dims must be > 0")
+    idx = np.empty(max(nq * kk, 1), dtype=np.uint64)
+    sc = np.empty(max(nq * kk, 1), dtype=np.float32)
+    check(load().innr_batch_knn_adaptive(batch._h, _vp(q) if q.size else None, nq, d, int(k), int(warmup_dims), _vp(idx), _vp(sc),
+                                         C.byref(out_k), C.byref(st)))
+    r = int(out_k.value)
+    return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+
+
+def batch_knn_adaptive(query, batch: VerticalBatch, k: int, warmup_dims: int) -> BatchKnnResult:
+    """batch.rs:441-564: approximate kNN (squared L2) that prunes on partial distances after `warmup_dims` dimensions. The
+    reference's heuristic, reproduced bit for bit (indices, order, scores); for exact selection use batch_knn."""
+    q = _f32(query).reshape(-1)
+    _assert_dim(q, batch)
+    idx, sc = batch_knn_adaptive_multi(q.reshape(1, -1), batch, k, warmup_dims)
+    return BatchKnnResult(indices=[int(i) for i in idx[0]], scores=[float(s) for s in sc[0]])

@@ -1,5 +1,5 @@
 // api.hip -- the extern "C" boundary (include/innr_hip.h) over the gfx950 kernels: contexts, batches, the kNN engines, the u8 and
-// int8 paths, range search, memory. maxsim lives in maxsim.hip, the multi-GPU layer in comm.hip, the full sort in sort_full.hip;
+// int8 paths, range search, memory. maxsim lives in maxsim.hip, batch_knn_adaptive in adaptive.hip, the multi-GPU layer in comm.hip, the full sort in sort_full.hip;
 // what they share with this file is api_internal.h.
 #include <ctype.h>
 #include <stdarg.h>
@@ -66,7 +66,7 @@ static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
             &c->redo[0].q, &c->redo[0].idx, &c->redo[0].sc, &c->redo[0].map, &c->redo[0].qn,
             &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
             &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan,
-            &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off};
+            &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off, &c->adp_scan, &c->adp_list};
 }
 
 // kernel_of(Inst) of the recorded families whose kernels this file owns (api_internal.h: Inst, launch_kernel)
@@ -2133,6 +2133,23 @@ static innr_status knn_full_sort(innr_batch* b, int metric, const float* dQ, siz
     }
     return INNR_OK;
 }
+
+namespace innr {
+innr_status l2_prefix_scores(innr_batch* b, const float* d_query, size_t W, float* out) {
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kScanChunk;
+    const unsigned blocks = (unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * 8);
+    scan_scores_kernel<1, true, false><<<blocks, kScanThreads, 0, c->stream>>>(b->V, b->ldN, (uint32_t)W, d_query, W, nullptr, nullptr,
+                                                                              out, b->ldN);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+innr_status exclusive_scan_u32(innr_ctx* c, const uint32_t* counts, uint32_t n, uint32_t* offsets, uint32_t* total) {
+    exclusive_scan_kernel<<<1, 1024, 0, c->stream>>>(counts, n, offsets, total);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+}  // namespace innr
 
 // the int8 filter in front of an f32 corpus (defined with the int8 engine further down)
 static bool f32_i8_eligible(const innr_batch* b, int metric, size_t Q, size_t kout);

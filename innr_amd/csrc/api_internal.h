@@ -1,8 +1,9 @@
 // api_internal.h -- what more than one translation unit of the library shares: the context and its workspace, the launch record
 // and dispatch, the corpus handles, the entry guard, and the host functions that cross a unit boundary. The units: api.hip (the C
-// ABI, the kNN engines, range search, memory), maxsim.hip, comm.hip (the multi-GPU layer), sort_full.hip.
-// Nothing here may depend on INNR_TEST_HOOKS: maxsim.o, comm.o and sort_full.o are linked into the product library and the hook
-// library alike, so the struct layouts must be the same in every object.
+// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), comm.hip (the multi-GPU layer),
+// sort_full.hip.
+// Nothing here may depend on INNR_TEST_HOOKS: every object but api.o is linked into the product library and the hook library
+// alike, so the struct layouts must be the same in every object.
 #pragma once
 
 #include <string.h>
@@ -161,6 +162,8 @@ struct innr_ctx {
     DevBuf rs_tot;     // ... [queries] totals, then [queries] flags: the exact scan finishes this query
     DevBuf rs_thr;     // ... the thresholds and [Q + 1] offsets of the host-memory entry point, staged on the device
     DevBuf rs_off;
+    DevBuf adp_scan;   // innr_batch_knn_adaptive: the AdaptiveState, then per-chunk counts and their scans [4][chunks of the corpus]
+    DevBuf adp_list;   // ... the live list twice (indices, distances: a compaction writes the other copy) and its death dimensions
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
@@ -300,6 +303,10 @@ bool metric_ok(int m);
 innr_status check_errflag(innr_ctx* c);
 innr_status emit_results(innr_ctx* c, const uint64_t* sel, size_t KP, size_t Q, size_t kout, bool smaller_is_better, uint64_t index_base,
                          uint64_t* out_idx, float* out_score);
+// api.hip, for the units that need a kernel it owns: the exact engine's squared-L2 scan of one query over the first W dimension
+// rows (out[0, ldN): the bits innr_batch_scores gives on a prefix view of W dimensions), and the single-workgroup exclusive scan
+innr_status l2_prefix_scores(innr_batch* b, const float* d_query, size_t W, float* out);
+innr_status exclusive_scan_u32(innr_ctx* c, const uint32_t* counts, uint32_t n, uint32_t* offsets, uint32_t* total);
 // sort_full.hip
 hipError_t full_sort_scratch_bytes(size_t n, size_t* bytes);
 size_t full_topk_out_capacity(size_t k);  // keys the `sorted` buffer must hold for the best k (the next power of two)

@@ -108,6 +108,8 @@ pub mod ffi {
         pub fn innr_batch_l2_squared_pruning(b: *mut InnrBatch, q: *const f32, d: usize, threshold: f32, out_idx: *mut u64, out_dist: *mut f32, cap: usize, out_n: *mut usize) -> c_int;
         pub fn innr_batch_range_search(b: *mut InnrBatch, metric: c_int, queries: *const f32, q: usize, d: usize, thresholds: *const f32, engine: c_int, out_offsets: *mut u64, out_idx: *mut u64, out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_range_search_dev(b: *mut InnrBatch, metric: c_int, d_queries: *const f32, q: usize, d: usize, d_thresholds: *const f32, engine: c_int, d_out_offsets: *mut u64, d_out_idx: *mut u64, d_out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_knn_adaptive(b: *mut InnrBatch, queries: *const f32, q: usize, d: usize, k: usize, warmup_dims: usize, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_knn_adaptive_dev(b: *mut InnrBatch, d_queries: *const f32, q: usize, d: usize, k: usize, warmup_dims: usize, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_dot_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_cosine_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_l2sq_f32(a: *const f32, b: *const f32, n: usize) -> f32;
@@ -453,6 +455,19 @@ pub mod batch {
         let kk = k.min(batch.num_vectors);
         let (mut idx, mut sc, mut n) = (vec![0u64; kk], vec![0f32; kk], 0usize);
         check(unsafe { ffi::innr_batch_knn_reordered(batch.handle(), query.as_ptr(), query.len(), k, idx.as_mut_ptr(), sc.as_mut_ptr(), &mut n) });
+        collect(idx, sc, n)
+    }
+
+    /// batch.rs:441-564: approximate kNN (squared L2) that prunes on partial distances after `warmup_dims` dimensions -- the
+    /// reference's heuristic reproduced bit for bit (indices, order, scores). For exact selection use `batch_knn`.
+    #[must_use] pub fn batch_knn_adaptive(query: &[f32], batch: &VerticalBatch, k: usize, warmup_dims: usize) -> BatchKnnResult {
+        assert_eq!(query.len(), batch.dimension);
+        assert!(warmup_dims > 0, "warmup_dims must be > 0");
+        if batch.num_vectors == 0 || k == 0 { return BatchKnnResult { indices: Vec::new(), scores: Vec::new() }; }
+        let kk = k.min(batch.num_vectors);
+        let (mut idx, mut sc, mut n) = (vec![0u64; kk], vec![0f32; kk], 0usize);
+        check(unsafe { ffi::innr_batch_knn_adaptive(batch.handle(), query.as_ptr(), 1, query.len(), k, warmup_dims, idx.as_mut_ptr(),
+                                                    sc.as_mut_ptr(), &mut n, std::ptr::null_mut()) });
         collect(idx, sc, n)
     }
 
