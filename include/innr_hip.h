@@ -108,8 +108,8 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * the environment ONCE, in innr_ctx_create (INNR_<NAME IN CAPITALS>); no call reads the environment afterwards. Names:
  * gemm_waves, gemm_blocks_per_cu, gemm_qt_group, gemm_seed_n, gemm_no_seed, gemm_no_kp_retry, i8_two_limb, no_auto_bf16,
  * no_auto_i8, u8_no_i8, rescore_all, maxsim_generic, no_k_rule, no_completion, no_rows_copy, i8_slices_per_cu, i8_no_small, i8_no_small4, i8_small_max_q, i8_small_free, trace, fail_local_search (a test
- * switch of the sharded calls), filter_keep_selection (default 1; 0: innr_batch_knn_filtered_multi frees its selection at the end
- * of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
+ * switch of the sharded calls), filter_keep_selection (default 1; 0: innr_batch_knn_filtered_multi and innr_batch_knn_u8_filtered
+ * free their selection at the end of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
  * innr_batch_set_copy_budget) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
@@ -188,6 +188,53 @@ innr_status innr_batch_knn_u8(innr_batch* b, const float* queries, size_t Q, siz
                               uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats);
 innr_status innr_batch_knn_u8_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, size_t k, int engine,
                                   uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats);
+/* batch_knn_u8 (scalar.rs:370-393) over the vectors that pass a mask, for each of Q queries (an addition: the code-batch twin of
+ * innr_batch_knn_filtered_multi). mask: N bytes, mask[i] != 0 <=> the vector takes part, one mask for every query. Writes
+ * k' = min(k, number passing) results per query to out_idx[q*k' + r], out_score[q*k' + r] (arrays sized Q*min(k,N)): top k' by
+ * asymmetric dot, descending by total_cmp, ties to the lower index, indices into this batch plus its index base, scores with the
+ * bits of innr_batch_scores_u8; *out_k = k'. Any k is accepted (beyond INNR_MAX_K: the masked full sort).
+ * Order of the checks: a null batch, an f32 batch or a null out_k: INNR_E_BAD_ARG; N == 0 or k == 0: *out_k = 0 (before the
+ * dimension check, as in innr_batch_knn_u8, scalar.rs:376-378); D != the batch's: INNR_E_DIM_MISMATCH; Q == 0: *out_k = 0; a null
+ * mask: INNR_E_BAD_ARG; null queries / outputs with work to do: INNR_E_BAD_ARG; no passing vector: *out_k = 0.
+ * Engines: INNR_KNN_EXACT scans this batch's codes with the mask applied. Every other engine, INNR_KNN_AUTO included, runs on a
+ * SELECTION: the passing vectors' codes gathered on the device, in index order, into a code batch of their own with this batch's
+ * alpha and offset, searched by innr_batch_knn_u8_dev with the caller's engine (innr_knn_stats.engine tells which engine ran
+ * there; the selection builds its own int8 copy when that engine wants one), the indices then mapped back; results are
+ * bit-identical either way. A mask that passes every vector searches this batch itself. On a prefix view only the view's rows
+ * are gathered. Memory: the batch keeps the selection of its last mask -- round_up(npass, 1024) * round_up(D, 32) bytes of codes,
+ * round_up(N, 1024) + 4*npass bytes of mask and map, plus the selection's own copies -- counted as INNR_COPY_SELECTION and against
+ * the copy budget; a call with the same mask (compared on the device after folding to 0/1) reuses it, a different mask replaces
+ * it, innr_batch_free and innr_batch_release_copies(INNR_COPY_SELECTION) free it, the option filter_keep_selection = 0 frees it
+ * at the end of every call. A selection that does not fit, or that the budget does not admit, leaves the call to the masked exact
+ * scan. stats->total_ms covers the whole call (mask, selection build, search).
+ * Out of scope: a mask per query, the adaptive k-NN on codes (the reference's is squared L2 on f32), a sharded variant. */
+innr_status innr_batch_knn_u8_filtered(innr_batch* b, const float* queries, size_t Q, size_t D, size_t k, const uint8_t* mask,
+                                       int engine, uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats);
+/* same, queries, mask and outputs resident on the device (innr_batch_knn_dev's conventions) */
+innr_status innr_batch_knn_u8_filtered_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, size_t k, const uint8_t* d_mask,
+                                           int engine, uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats);
+/* Range search on codes: innr_batch_range_search's contract with the one metric of a code batch (an addition). A vector survives
+ * for query j iff !(score < thresholds[j]), score with the bits of innr_batch_scores_u8: a NaN score or threshold survives. The
+ * result layout is innr_batch_range_search's: out_offsets of Q + 1 64-bit entries, each query's entries in ascending index order,
+ * indices = index base + local index, only global positions < cap written, cap == 0 a count-only call (out_idx / out_score may
+ * then be null), *out_total > cap still INNR_OK.
+ * Order of the checks: a null or f32 batch: INNR_E_BAD_ARG; D != the batch's: INNR_E_DIM_MISMATCH; a null out_offsets or
+ * out_total: INNR_E_BAD_ARG; N == 0 or Q == 0: all-zero offsets; null thresholds, queries or outputs with work to do:
+ * INNR_E_BAD_ARG.
+ * Engine: the exact scan in the reference's arithmetic serves every `engine` value, up to eight queries per pass: one pass counts
+ * the survivors per 1024-vector chunk, a second one -- which skips every chunk without survivors -- writes them. stats->engine =
+ * INNR_KNN_EXACT, queries_fallback = 0, candidates_kept = 0, gemm_ms = device time of the scans, total_ms of the whole call. The
+ * host-memory entry point stages results as innr_batch_range_search does (a count pass first where min(cap, Q*N) results would
+ * need more than 256 MiB); the call works in rounds of at most 4096 queries whose workspace stays within 2 GiB (per query N/256
+ * bytes of counts).
+ * Out of scope: a collect mode on the integer matrix pipe (`engine` is kept so that it needs no new symbol), a sharded variant. */
+innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
+                                       uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
+                                       innr_knn_stats* stats);
+/* same, queries, thresholds, out_offsets, out_idx and out_score resident on the device; the call synchronises with the host */
+innr_status innr_batch_range_search_u8_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, const float* d_thresholds,
+                                           int engine, uint64_t* d_out_offsets, uint64_t* d_out_idx, float* d_out_score, size_t cap,
+                                           size_t* out_total, innr_knn_stats* stats);
 /* quantize_u8 (scalar.rs:212-225) on the host (one-time ingest step): out[i] =
  * clamp(round((v[i]-offset)*255/alpha), 0, 255), round = half away from zero */
 void innr_quantize_u8(const float* values, size_t n, float alpha, float offset, uint8_t* out);
@@ -277,7 +324,7 @@ innr_status innr_batch_knn_filtered(innr_batch* b, const float* q, size_t D, siz
  * Writes k' = min(k, number passing) results per query to out_idx[q*k' + r], out_score[q*k' + r] (arrays sized Q*min(k,N)),
  * indices into this batch plus its index base, in innr_batch_knn's order for the metric; *out_k = k'. The dimension check comes
  * first (batch.rs:829); then N == 0, k == 0, Q == 0 or no passing vector give *out_k = 0 (batch.rs:831-847). A null mask with
- * N > 0 or a u8 code batch: INNR_E_BAD_ARG.
+ * N > 0 or a u8 code batch (that is innr_batch_knn_u8_filtered): INNR_E_BAD_ARG.
  * Engines: INNR_KNN_EXACT scans this batch with the mask applied. Every other engine, INNR_KNN_AUTO included, runs on a SELECTION:
  * the passing vectors gathered on the device, in index order, into a compact batch of their own, searched like any batch of that
  * size (innr_knn_stats.engine tells which engine ran there), the indices then mapped back; results are bit-identical either way.
@@ -329,7 +376,7 @@ innr_status innr_batch_l2_squared_pruning(innr_batch* b, const float* q, size_t 
  * more search) and stages what the result needs, so a generous cap costs time, not memory; its stats describe the last search.
  * Memory: the call works in rounds of at most 4096 queries whose workspace stays within 2 GiB (per query N/64 bytes of counts;
  * on the collect path N/8 bytes of bitmap and 768 KiB of lists more).
- * Out of scope: the int8 / bf16 collect modes, u8 code batches, a sharded variant. */
+ * Out of scope: the int8 / bf16 collect modes, a sharded variant. (u8 code batches: innr_batch_range_search_u8.) */
 innr_status innr_batch_range_search(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const float* thresholds,
                                     int engine, uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap,
                                     size_t* out_total, innr_knn_stats* stats);
@@ -405,7 +452,7 @@ innr_status innr_batch_prefix_view(innr_batch* parent, size_t prefix_dims, innr_
  *   INNR_COPY_BF16_*        the K-packed bf16 filter copies of INNR_KNN_MFMA_BF16, one per metric
  *   INNR_COPY_BF16LO_*      the lo limbs of the dot / cosine copy: with the BF16 copy of that metric, INNR_KNN_MFMA's split filter
  *   INNR_COPY_I8_*          the K-packed int8 filter copies of INNR_KNN_MFMA_I8 (a u8 code batch has the DOT kind only)
- *   INNR_COPY_SELECTION     the kept selection of innr_batch_knn_filtered_multi: its compact store, mask and map, and every
+ *   INNR_COPY_SELECTION     the kept selection of innr_batch_knn_filtered_multi / innr_batch_knn_u8_filtered: its compact store, mask and map, and every
  *                           copy the selection batch built for itself (its cached norms, 12 bytes per vector at most, are not
  *                           counted)
  * A prefix view is a batch of its own here: it shares the parent's store (corpus_bytes = 0), owns its copies and has its OWN

@@ -109,6 +109,10 @@ SIGNATURES = {
     "innr_batch_scores_u8": (C.c_int, [_vp, _vp, _sz, _vp]),
     "innr_batch_knn_u8": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
     "innr_batch_knn_u8_dev": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_knn_u8_filtered": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_knn_u8_filtered_dev": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _vp, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_range_search_u8": (C.c_int, [_vp, _vp, _sz, _sz, _vp, C.c_int, _vp, _vp, _vp, _sz, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_range_search_u8_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, C.c_int, _vp, _vp, _vp, _sz, _szp, C.POINTER(KnnStats)]),
     "innr_quantize_u8": (None, [_vp, _sz, C.c_float, C.c_float, _vp]),
     "innr_batch_quantize_u8": (C.c_int, [_vp, C.c_float, C.c_float, C.POINTER(_vp)]),
     "innr_batch_prefix_view": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),

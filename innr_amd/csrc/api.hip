@@ -79,6 +79,8 @@ template <int NK, int CT, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Small
 template <int QB, int MET, int EMIT> constexpr auto kernel_of(Inst<kLaunchRangeScan, QB, MET, EMIT>) {
     return &range_scan_kernel<QB, MET == INNR_METRIC_L2SQ, MET == INNR_METRIC_COSINE, EMIT != 0>;
 }
+template <int QB, int RR> constexpr auto kernel_of(Inst<kLaunchScanU8Masked, QB, RR>) { return &scan_u8_filter_kernel<QB, RR, true>; }
+template <int QB, int EMIT> constexpr auto kernel_of(Inst<kLaunchRangeScanU8, QB, EMIT>) { return &range_scan_u8_kernel<QB, EMIT != 0>; }
 
 static auto metric_of(int metric) { return one_of<INNR_METRIC_COSINE, INNR_METRIC_L2SQ, INNR_METRIC_DOT>(metric); }
 // RR (R in the kernels) of a list capacity of 64 RR entries: the GEMM-type filters have lists of 32 / 64 / 128 / 256 candidates
@@ -2595,14 +2597,20 @@ innr_status innr_batch_scores_u8(innr_batch* b, const float* q, size_t D, float*
 }
 
 static innr_status launch_scan_u8(innr_batch* b, uint32_t qb, const float* dQ, size_t ldq, const float* qsum, uint32_t nblocks,
-                                  uint32_t KP, uint32_t cap, uint32_t cps, uint32_t groups, size_t limit_n, uint32_t nvalid_q) {
+                                  uint32_t KP, uint32_t cap, uint32_t cps, uint32_t groups, size_t limit_n, uint32_t nvalid_q,
+                                  const uint8_t* mask) {
     innr_ctx* c = b->ctx;
     const uint32_t nvalid = (uint32_t)((limit_n && limit_n < b->N) ? limit_n : b->N);
     const float a255 = b->alpha / 255.0f;  // scalar.rs:299 (params.alpha / 255.0), f32
     dispatch([&](auto QB, auto rr) {
-        scan_u8_filter_kernel<QB, rr><<<dim3(nblocks, groups), 256, 0, c->stream>>>(
-            b->C8, b->ldN, nvalid, (uint32_t)b->D, dQ, ldq, qsum, a255, b->offset, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(),
-            QB * groups, KP, cps, c->flags.as<uint32_t>(), nvalid_q);
+        if (mask)  // the masked scan is a recorded family; the plain one runs inside most recorded calls and is not (cf. launch_scan_filter)
+            launch_kernel(c, Inst<kLaunchScanU8Masked, QB, rr>(), {dim3(nblocks, groups), 256, 0, groups}, b->C8, b->ldN, nvalid,
+                          (uint32_t)b->D, dQ, ldq, qsum, a255, b->offset, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(),
+                          (uint32_t)(QB * groups), KP, cps, c->flags.as<uint32_t>(), nvalid_q, mask);
+        else
+            scan_u8_filter_kernel<QB, rr><<<dim3(nblocks, groups), 256, 0, c->stream>>>(
+                b->C8, b->ldN, nvalid, (uint32_t)b->D, dQ, ldq, qsum, a255, b->offset, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(),
+                QB * groups, KP, cps, c->flags.as<uint32_t>(), nvalid_q);
     }, one_of<8, 4, 1>(qb), rr_scan(cap));
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
@@ -2610,8 +2618,10 @@ static innr_status launch_scan_u8(innr_batch* b, uint32_t qb, const float* dQ, s
 
 // exact engine for queries [q0, q0+nq): qsum[] precomputed on device for all queries
 // limit_n != 0: only the first limit_n documents take part (threshold seeding of the int8 engine)
+// mask (nullable, [ldN] 0/1 bytes): only the vectors with mask[i] != 0 take part (innr_batch_knn_u8_filtered)
 static innr_status knn_u8_exact_range(innr_batch* b, const float* dQ, size_t ldq, const float* qsum, size_t q0, size_t nq,
-                                      size_t kout, uint64_t* d_out_idx, float* d_out_score, size_t limit_n = 0) {
+                                      size_t kout, uint64_t* d_out_idx, float* d_out_score, size_t limit_n = 0,
+                                      const uint8_t* mask = nullptr) {
     innr_ctx* c = b->ctx;
     const uint32_t KP = pick_kp(kout, 0);
     const uint32_t cap = exact_cap(KP);
@@ -2640,7 +2650,7 @@ static innr_status knn_u8_exact_range(innr_batch* b, const float* dQ, size_t ldq
         const float* q = dQ + (q0 + done) * ldq;
         const float* qs = qsum + q0 + done;
         if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qs));
-        INNR_TRY(launch_scan_u8(b, qb, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu));
+        INNR_TRY(launch_scan_u8(b, qb, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu, mask));
         INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, false, d_out_idx + (q0 + done) * kout,
                                  d_out_score + (q0 + done) * kout));
         done += nreal;
@@ -3436,12 +3446,14 @@ static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
     // The copy budget, for the store, the mask and the map (alloc_batch's and the two hipMallocs' sizes below) in the place of the
     // selection they replace. Not admitted: the selection of the last mask stays (the library frees nothing by itself), the
     // masked exact scan serves this call.
-    const size_t store_bytes = round_up(npass ? npass : 1, 256) * round_up(b->D ? b->D : 1, 32) * sizeof(float);
+    // (a code batch's selection is a code batch with the parent's alpha and offset: alloc_batch_u8's size)
+    const size_t store_bytes = b->C8 ? round_up(npass ? npass : 1, 1024) * round_up(b->D ? b->D : 1, 32)
+                                     : round_up(npass ? npass : 1, 256) * round_up(b->D ? b->D : 1, 32) * sizeof(float);
     const size_t mask_bytes = b->ldN, map_bytes = npass * sizeof(uint32_t);
     if (!budget_admits(b, store_bytes + mask_bytes + map_bytes, corpus_copy_bytes(b))) return INNR_OK;
     free_selection(b);
     innr_batch* s = nullptr;
-    const innr_status st = alloc_batch(c, npass, b->D, &s);
+    const innr_status st = b->C8 ? alloc_batch_u8(c, npass, b->D, b->alpha, b->offset, &s) : alloc_batch(c, npass, b->D, &s);
     if (st == INNR_E_OOM) {
         (void)hipGetLastError();  // the failed hipMalloc must not surface at the next launch check
         return INNR_OK;
@@ -3460,8 +3472,12 @@ static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
     const size_t D = b->D;
     const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
     const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
-    select_gather_kernel<<<grid, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->V, s->ldN,
-                                                      b->fsel_map, slab);
+    if (b->C8)
+        select_gather_u8_kernel<<<grid, 256, 0, c->stream>>>(b->C8, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->C8,
+                                                             s->ldN, b->fsel_map, slab);
+    else
+        select_gather_kernel<<<grid, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->V, s->ldN,
+                                                          b->fsel_map, slab);
     INNR_HIP_CHECK(hipGetLastError());
     INNR_HIP_CHECK(hipMemcpyAsync(b->fsel_mask, c->flt_mask.p, b->ldN, hipMemcpyDeviceToDevice, c->stream));
     ++b->fsel_builds;
@@ -3591,6 +3607,119 @@ innr_status innr_batch_knn_filtered_multi(innr_batch* b, int metric, const float
     INNR_HIP_CHECK(hipMemcpyAsync(c->flt_in.p, mask, b->N, hipMemcpyHostToDevice, c->stream));
     return knn_from_host(c, queries, Q, D, std::min(k, b->N), out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
         return innr_batch_knn_filtered_multi_dev(b, metric, dQ, Q, D, k, c->flt_in.as<uint8_t>(), engine, di, ds, out_k, stats);
+    });
+}
+
+// ---- batch_knn_u8 over the vectors that pass a mask: innr_batch_knn_filtered_multi's scheme on a code batch ----
+// The masked exact scan on the code batch itself: scan_u8_filter_kernel<..., MASK> with the normalised mask for every query, or
+// beyond INNR_MAX_K the masked full sort. kout <= npass.
+static innr_status knn_u8_masked_exact(innr_batch* b, const float* dQ, size_t Q, size_t D, size_t kout, size_t npass,
+                                       uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats) {
+    innr_ctx* c = b->ctx;
+    const uint8_t* nm = c->flt_mask.as<uint8_t>();
+    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
+    INNR_TRY(c->q_norm.ensure(2 * round_up(Q, kBQmax) * sizeof(float)));
+    float* qsum = c->q_norm.as<float>();
+    query_sums_kernel<<<(unsigned)((Q + 63) / 64), 64, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)D, D, qsum, qsum + round_up(Q, kBQmax));
+    INNR_HIP_CHECK(hipGetLastError());
+    uint32_t kept;
+    if (kout > INNR_MAX_K) {
+        INNR_TRY(knn_full_sort(b, -1, dQ, D, qsum, Q, kout, d_out_idx, d_out_score, nm));
+        kept = (uint32_t)npass;
+    } else {
+        INNR_TRY(knn_u8_exact_range(b, dQ, D, qsum, 0, Q, kout, d_out_idx, d_out_score, 0, nm));
+        kept = pick_kp(kout, 0);
+    }
+    return finish_knn(c, INNR_KNN_EXACT, kout, 0, kept, 0.0f, out_k, stats);
+}
+
+// the checks the two entry points share, in the reference's order (scalar.rs:376-378: an empty corpus or k == 0 before any dimension
+// assert); *empty: nothing to search, *out_k stays 0
+static innr_status knn_u8_filtered_args(innr_batch* b, size_t Q, size_t D, size_t k, const uint8_t* mask, size_t* out_k,
+                                        innr_knn_stats* stats, bool* empty) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!b || !b->C8 || !out_k) {
+        set_error("this entry point needs a u8 code batch and out_k");
+        return INNR_E_BAD_ARG;
+    }
+    *out_k = 0;
+    *empty = true;
+    if (b->N == 0 || k == 0) return INNR_OK;
+    INNR_TRY(u8_check(b, D));
+    if (Q == 0) return INNR_OK;
+    if (!mask) {
+        set_error("mask is null");
+        return INNR_E_BAD_ARG;
+    }
+    *empty = false;
+    return INNR_OK;
+}
+
+innr_status innr_batch_knn_u8_filtered_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, size_t k, const uint8_t* d_mask,
+                                           int engine, uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats) {
+    bool empty = false;
+    INNR_TRY(knn_u8_filtered_args(b, Q, D, k, d_mask, out_k, stats, &empty));
+    if (empty) return INNR_OK;
+    if (!d_queries || !d_out_idx || !d_out_score) {
+        set_error("queries / output buffers are null");
+        return INNR_E_BAD_ARG;
+    }
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
+    size_t npass = 0;
+    bool same = false;
+    INNR_TRY(filter_mask(b, d_mask, &npass, &same));
+    if (npass == 0) return INNR_OK;
+    const size_t kout = std::min(k, npass);
+    if (npass == b->N) {
+        // every vector passes: the batch itself, no selection
+        INNR_TRY(innr_batch_knn_u8_dev(b, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
+    } else {
+        bool have = same;
+        if (engine != INNR_KNN_EXACT && !same) INNR_TRY(build_selection(b, npass, &have));
+        if (engine != INNR_KNN_EXACT && have) {
+            // the selection's int8 copy counts against this batch's budget: it gets what this batch's copies and its own store leave
+            const size_t used = corpus_copy_bytes(b) + selection_base_bytes(b);
+            b->fsel->copy_budget = b->copy_budget == UINT64_MAX ? UINT64_MAX : (b->copy_budget > used ? b->copy_budget - used : 0);
+            // the caller's engine on the selection (its own index_base is 0), then selection indices -> this batch's
+            INNR_TRY(innr_batch_knn_u8_dev(b->fsel, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
+            const size_t n = Q * *out_k;
+            if (n) {
+                select_remap_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d_out_idx, n, b->fsel_map, (uint32_t)npass,
+                                                                                     b->index_base);
+                INNR_HIP_CHECK(hipGetLastError());
+            }
+        } else {
+            INNR_TRY(knn_u8_masked_exact(b, d_queries, Q, D, kout, npass, d_out_idx, d_out_score, out_k, stats));
+        }
+    }
+    INNR_HIP_CHECK(hipEventRecord(c->ev[5], c->stream));
+    if (!c->tune.filter_keep_selection) free_selection(b);  // (synchronises)
+    if (stats) {  // the whole call: mask, selection build, search, remap
+        float ms = 0.0f;
+        INNR_HIP_CHECK(hipEventSynchronize(c->ev[5]));
+        if (hipEventElapsedTime(&ms, c->ev[4], c->ev[5]) == hipSuccess) stats->total_ms = ms;
+    }
+    return INNR_OK;
+}
+
+innr_status innr_batch_knn_u8_filtered(innr_batch* b, const float* queries, size_t Q, size_t D, size_t k, const uint8_t* mask, int engine,
+                                       uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats) {
+    bool empty = false;
+    INNR_TRY(knn_u8_filtered_args(b, Q, D, k, mask, out_k, stats, &empty));
+    if (empty) return INNR_OK;
+    if ((!queries && D) || !out_idx || !out_score) {
+        set_error("queries / output buffers are null");
+        return INNR_E_BAD_ARG;
+    }
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_TRY(c->flt_in.ensure(b->N));
+    INNR_HIP_CHECK(hipMemcpyAsync(c->flt_in.p, mask, b->N, hipMemcpyHostToDevice, c->stream));
+    return knn_from_host(c, queries, Q, D, std::min(k, b->N), out_idx, out_score, out_k, [&](const float* dQ, uint64_t* di, float* ds) {
+        return innr_batch_knn_u8_filtered_dev(b, dQ, Q, D, k, c->flt_in.as<uint8_t>(), engine, di, ds, out_k, stats);
     });
 }
 
@@ -4008,6 +4137,119 @@ static innr_status range_search_args(innr_batch* b, int metric, const float* que
     return INNR_OK;
 }
 
+// ---- range search on a u8 code batch (innr_batch_range_search_u8): the exact scan's two launches per round -----
+template <bool EMIT>
+static innr_status launch_range_scan_u8(innr_batch* b, const float* dQ, const float* qsum, const float* thr, uint32_t nq, uint32_t* cnt,
+                                        size_t ldc, const uint64_t* qoff, uint64_t* out_idx, float* out_score, uint64_t cap) {
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kU8Chunk;
+    const uint32_t qb = nq >= 8 ? 8 : (nq >= 4 ? 4 : 1);  // never more than there are queries: the last group ends on the last query
+    // waves per CU as the exact u8 kNN scan (knn_u8_exact_range): 16
+    const dim3 grid((unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * 4), (nq + qb - 1) / qb);
+    dispatch([&](auto QB) {
+        launch_kernel(c, Inst<kLaunchRangeScanU8, QB, EMIT>(), {grid, 256, 0, grid.y}, b->C8, b->ldN, (uint32_t)b->N, (uint32_t)b->D, dQ,
+                      b->D, qsum, b->alpha / 255.0f, b->offset, thr, nq, cnt, ldc, qoff, b->index_base, out_idx, out_score, cap);
+    }, one_of<8, 4, 1>(qb));
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
+static innr_status range_search_u8_dev(innr_batch* b, const float* dQ, size_t Q, const float* dThr, uint64_t* d_off, uint64_t* d_idx,
+                                       float* d_sc, size_t cap, size_t* out_total, innr_knn_stats* stats) {
+    innr_ctx* c = b->ctx;
+    const size_t D = b->D, nchunks = b->ldN / kU8Chunk, ldc = nchunks + 1;
+    const size_t per_query = (ldc + 2) * sizeof(uint32_t) + 2 * sizeof(float);
+    const size_t round = std::min(Q, std::max<size_t>(1, std::min(kRangeMaxRound, kRangeWorkspace / per_query)));
+    INNR_TRY(c->rs_cnt.ensure(round * ldc * sizeof(uint32_t)));
+    INNR_TRY(c->rs_tot.ensure(round * sizeof(uint32_t)));
+    INNR_TRY(c->q_norm.ensure(2 * round * sizeof(float)));
+    uint32_t* cnt = c->rs_cnt.as<uint32_t>();
+    uint32_t* tot = c->rs_tot.as<uint32_t>();
+    float* qsum = c->q_norm.as<float>();
+    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
+    INNR_HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), c->stream));  // the running base, carried in the offsets themselves
+    INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+    for (size_t q0 = 0; q0 < Q; q0 += round) {
+        const uint32_t nq = (uint32_t)std::min(round, Q - q0);
+        const float* Qp = dQ + q0 * D;
+        uint64_t* off = d_off + q0;
+        query_sums_kernel<<<(nq + 63) / 64, 64, 0, c->stream>>>(Qp, nq, (uint32_t)D, D, qsum, qsum + round);
+        INNR_HIP_CHECK(hipGetLastError());
+        INNR_TRY(launch_range_scan_u8<false>(b, Qp, qsum, dThr + q0, nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
+        range_chunk_scan_kernel<<<nq, 1024, 0, c->stream>>>(cnt, ldc, (uint32_t)nchunks, tot);
+        range_offsets_kernel<<<1, 1024, 0, c->stream>>>(tot, nq, off);
+        INNR_HIP_CHECK(hipGetLastError());
+        if (cap == 0) continue;  // a count-only call
+        INNR_TRY(launch_range_scan_u8<true>(b, Qp, qsum, dThr + q0, nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
+    }
+    INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
+    uint64_t total = 0;
+    INNR_HIP_CHECK(copy_out(c, &total, d_off + Q, sizeof(total)));
+    INNR_TRY(check_errflag(c));  // (synchronises)
+    *out_total = (size_t)total;
+    if (stats) {
+        float ms = 0.0f;
+        stats->engine = INNR_KNN_EXACT;
+        if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) stats->gemm_ms = ms;
+        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
+    }
+    return INNR_OK;
+}
+
+// the argument checks both u8 entry points share: range_search_args' order with the batch test inverted
+static innr_status range_search_u8_args(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds,
+                                        uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
+                                        innr_knn_stats* stats, bool* empty) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    INNR_TRY(u8_check(b, D));  // a null or f32 batch: INNR_E_BAD_ARG; then the dimension
+    if (!out_offsets || !out_total || Q >= 0xFFFFFFFFull) {
+        set_error("out_offsets / out_total is null, or more than 2^32 - 2 queries");
+        return INNR_E_BAD_ARG;
+    }
+    *out_total = 0;
+    *empty = b->N == 0 || Q == 0;
+    if (*empty) return INNR_OK;
+    if (!thresholds || (!queries && D) || (cap && (!out_idx || !out_score))) {
+        set_error("thresholds / queries / output buffers are null");
+        return INNR_E_BAD_ARG;
+    }
+    return INNR_OK;
+}
+
+// A range search on host memory: queries, thresholds and offsets staged on the device, and room for min(cap, Q * N) results. Where
+// that room is large (beyond kRangeStageDirect bytes) a count-only pass comes first and the room shrinks to what the result needs: a
+// generous cap costs a second search, not memory for results that do not exist. dev(dQ, dThr, d_off, d_idx, d_sc, room) searches.
+template <class Dev>
+static innr_status range_search_from_host(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds,
+                                          uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
+                                          Dev&& dev) {
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    size_t room = std::min(cap, Q * b->N);
+    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
+    INNR_TRY(c->rs_thr.ensure(Q * sizeof(float)));
+    INNR_TRY(c->rs_off.ensure((Q + 1) * sizeof(uint64_t)));
+    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
+    INNR_HIP_CHECK(copy_in(c, c->rs_thr.p, thresholds, Q * sizeof(float)));
+    if (room * (sizeof(uint64_t) + sizeof(float)) > kRangeStageDirect) {
+        INNR_TRY(dev(c->q_row.as<float>(), c->rs_thr.as<float>(), c->rs_off.as<uint64_t>(), nullptr, nullptr, 0));
+        room = std::min(room, *out_total);
+    }
+    INNR_TRY(c->out_idx.ensure(std::max<size_t>(room, 1) * sizeof(uint64_t)));
+    INNR_TRY(c->out_score.ensure(std::max<size_t>(room, 1) * sizeof(float)));
+    INNR_TRY(dev(c->q_row.as<float>(), c->rs_thr.as<float>(), c->rs_off.as<uint64_t>(), c->out_idx.as<uint64_t>(), c->out_score.as<float>(), room));
+    INNR_HIP_CHECK(copy_out(c, out_offsets, c->rs_off.p, (Q + 1) * sizeof(uint64_t)));
+    const size_t m = std::min<size_t>(*out_total, room);
+    if (m) {
+        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, m * sizeof(uint64_t)));
+        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, m * sizeof(float)));
+    }
+    INNR_HIP_CHECK(ctx_sync(c));
+    return INNR_OK;
+}
+
 }  // namespace innr
 
 extern "C" {
@@ -4036,34 +4278,43 @@ innr_status innr_batch_range_search(innr_batch* b, int metric, const float* quer
         memset(out_offsets, 0, (Q + 1) * sizeof(uint64_t));
         return INNR_OK;
     }
+    return range_search_from_host(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
+                                  [&](const float* dQ, const float* dThr, uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t room) {
+                                      return range_search_dev(b, metric, dQ, Q, dThr, engine, d_off, d_idx, d_sc, room, out_total, stats);
+                                  });
+}
+
+// `engine` is accepted and ignored: the exact scan serves every value (a later matrix-pipe collect mode needs no new symbol)
+innr_status innr_batch_range_search_u8_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, const float* d_thresholds, int engine,
+                                           uint64_t* d_out_offsets, uint64_t* d_out_idx, float* d_out_score, size_t cap, size_t* out_total,
+                                           innr_knn_stats* stats) {
+    (void)engine;
+    bool empty = false;
+    INNR_TRY(range_search_u8_args(b, d_queries, Q, D, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats, &empty));
     innr_ctx* c = b->ctx;
     INNR_ENTER(c);
-    // Staged on the device: queries, thresholds, offsets, and room for min(cap, Q * N) results. Where that room is large (beyond
-    // kRangeStageDirect bytes) a count-only pass comes first and the room shrinks to what the result needs: a generous cap costs a
-    // second search, not memory for results that do not exist.
-    size_t room = std::min(cap, Q * b->N);
-    INNR_TRY(c->q_row.ensure(std::max<size_t>(Q * D, 1) * sizeof(float)));
-    INNR_TRY(c->rs_thr.ensure(Q * sizeof(float)));
-    INNR_TRY(c->rs_off.ensure((Q + 1) * sizeof(uint64_t)));
-    if (D) INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
-    INNR_HIP_CHECK(copy_in(c, c->rs_thr.p, thresholds, Q * sizeof(float)));
-    if (room * (sizeof(uint64_t) + sizeof(float)) > kRangeStageDirect) {
-        INNR_TRY(range_search_dev(b, metric, c->q_row.as<float>(), Q, c->rs_thr.as<float>(), engine, c->rs_off.as<uint64_t>(), nullptr,
-                                  nullptr, 0, out_total, stats));
-        room = std::min(room, *out_total);
+    if (empty) {
+        INNR_HIP_CHECK(hipMemsetAsync(d_out_offsets, 0, (Q + 1) * sizeof(uint64_t), c->stream));
+        INNR_HIP_CHECK(ctx_sync(c));
+        return INNR_OK;
     }
-    INNR_TRY(c->out_idx.ensure(std::max<size_t>(room, 1) * sizeof(uint64_t)));
-    INNR_TRY(c->out_score.ensure(std::max<size_t>(room, 1) * sizeof(float)));
-    INNR_TRY(range_search_dev(b, metric, c->q_row.as<float>(), Q, c->rs_thr.as<float>(), engine, c->rs_off.as<uint64_t>(),
-                              c->out_idx.as<uint64_t>(), c->out_score.as<float>(), room, out_total, stats));
-    INNR_HIP_CHECK(copy_out(c, out_offsets, c->rs_off.p, (Q + 1) * sizeof(uint64_t)));
-    const size_t m = std::min<size_t>(*out_total, room);
-    if (m) {
-        INNR_HIP_CHECK(copy_out(c, out_idx, c->out_idx.p, m * sizeof(uint64_t)));
-        INNR_HIP_CHECK(copy_out(c, out_score, c->out_score.p, m * sizeof(float)));
+    return range_search_u8_dev(b, d_queries, Q, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+}
+
+innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
+                                       uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
+                                       innr_knn_stats* stats) {
+    (void)engine;
+    bool empty = false;
+    INNR_TRY(range_search_u8_args(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total, stats, &empty));
+    if (empty) {
+        memset(out_offsets, 0, (Q + 1) * sizeof(uint64_t));
+        return INNR_OK;
     }
-    INNR_HIP_CHECK(ctx_sync(c));
-    return INNR_OK;
+    return range_search_from_host(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
+                                  [&](const float* dQ, const float* dThr, uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t room) {
+                                      return range_search_u8_dev(b, dQ, Q, dThr, d_off, d_idx, d_sc, room, out_total, stats);
+                                  });
 }
 
 }  // extern "C"

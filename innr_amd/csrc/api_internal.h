@@ -71,7 +71,7 @@ struct innr_tuning {
     long i8_small_free = 0;      // ... its query groups run free (no soft lockstep): A/B
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
-    long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi: keep the selection of the last mask for the next call (0: free it at the end of each call)
+    long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
 };
 
@@ -90,6 +90,8 @@ enum LaunchFamily {
     kLaunchMsGeneric = 9,  // maxsim_mfma_kernel<COS>, once per pass
     kLaunchMsRerank = 10,  // maxsim_rerank_kernel<COS, NQ, MULTI>, once per pass
     kLaunchRangeScan = 11, // range_scan_kernel<QB, L2, COS, EMIT>: args QB, metric (INNR_METRIC_*), EMIT; groups = query groups
+    kLaunchScanU8Masked = 12,  // scan_u8_filter_kernel<QB, R, true> (the masked exact scan of a code batch): args QB, R; groups = query groups
+    kLaunchRangeScanU8 = 13,   // range_scan_u8_kernel<QB, EMIT>: args QB, EMIT; groups = query groups
 };
 struct LaunchRec {
     uint8_t family;    // LaunchFamily
@@ -157,7 +159,7 @@ struct innr_ctx {
     DevBuf flt_in;     // innr_batch_knn_filtered_multi: the caller's mask bytes staged on the device (host-memory entry point)
     DevBuf flt_mask;   // ... the mask normalised to 0/1, [ldN]
     DevBuf flt_scan;   // ... passing vectors per chunk [nchunks], their exclusive scan [nchunks], the total, the mask-differs flag
-    DevBuf rs_cnt;     // innr_batch_range_search: survivors per 256-vector chunk [queries][nchunks + 1], scanned in place
+    DevBuf rs_cnt;     // innr_batch_range_search[_u8]: survivors per 256-vector (codes: 1024-vector) chunk [queries][nchunks + 1], scanned in place
     DevBuf rs_bits;    // ... the collect path's survivor bitmaps [queries][ldN / 32]
     DevBuf rs_tot;     // ... [queries] totals, then [queries] flags: the exact scan finishes this query
     DevBuf rs_thr;     // ... the thresholds and [Q + 1] offsets of the host-memory entry point, staged on the device

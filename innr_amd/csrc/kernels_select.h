@@ -95,6 +95,94 @@ __global__ __launch_bounds__(256) void select_gather_kernel(const float* __restr
     }
 }
 
+// 2b. The gather of a u8 code batch (innr_batch_knn_u8_filtered): S[d * ldS + rank(i)] = C8[d * ldN + i], map[rank(i)] = i, with the
+//    chunks, counts and offsets of the f32 gather (a code batch's ldN is a multiple of 1024, hence of kSelChunk): a lane owns one
+//    dword of 4 codes per row and loads it only if one of them passes; a chunk with no passing vector returns before any load.
+//    The survivors of a chunk are one contiguous run [chunk_off, chunk_off + total) of every destination row.
+//    The wave compacts kSelU8Rows rows' passing bytes in LDS at the run's own alignment (lo = chunk_off % 4: both row strides are
+//    multiples of 4, so every row of S has it) and writes the run as whole dwords; only the dwords at the two ragged ends, which
+//    the neighbouring chunks' runs share, go out byte by byte (never a byte outside the run). One byte store per passing code
+//    instead -- the f32 gather's form -- was measured and lost at every selectivity.
+//    Grid: as select_gather_kernel.
+// rows per LDS round: that many loads in flight per lane (the gather is bound by the latency of its rounds, not by bandwidth:
+// DESIGN.md 4.5e has 4 against 16 rows); 16 rows are 16.5 KiB of LDS a block
+constexpr int kSelU8Rows = 16;
+constexpr int kSelU8Stage = (kSelChunk + 4 + 4) / 4;  // dwords per staged row: 3 + 256 bytes at most, rounded up (66)
+
+__global__ __launch_bounds__(256) void select_gather_u8_kernel(const uint8_t* __restrict__ C8, size_t ldN, uint32_t D,
+                                                               const uint8_t* __restrict__ nm, const uint32_t* __restrict__ chunk_off,
+                                                               size_t nchunks, uint8_t* __restrict__ S, size_t ldS,
+                                                               uint32_t* __restrict__ map, uint32_t slab) {
+    __shared__ uint32_t stage[4][kSelU8Rows][kSelU8Stage];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t ch = (size_t)blockIdx.x * 4 + w;
+    if (ch >= nchunks) return;  // wave-uniform
+    const size_t col = ch * kSelChunk + (size_t)lane * 4;
+    const uint32_t m4 = *reinterpret_cast<const uint32_t*>(nm + col);
+    uint32_t total;
+    const uint32_t below = sel_pass_below(m4, lane, &total);
+    if (total == 0) return;  // wave-uniform
+    const uint32_t base = chunk_off[ch];
+    uint32_t r[4];  // rank within the chunk
+    {
+        uint32_t r_ = below;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            r[c] = r_;
+            r_ += (m4 >> (8 * c)) & 1u;
+        }
+    }
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if ((m4 >> (8 * c)) & 1u) map[base + r[c]] = (uint32_t)(col + c);
+    }
+    const uint32_t d0 = blockIdx.y * slab;
+    const uint32_t d1 = (d0 < D && slab < D - d0) ? d0 + slab : D;
+    const uint8_t* src = C8 + col;
+    const uint32_t lo = base & 3u, hi = lo + total;  // the run's bytes within its staged row: [lo, hi), hi <= 259
+    const uint32_t ndw = (hi + 3) / 4;               // <= 65: lane 0 takes dword 64 as well
+    uint8_t* S0 = S + (base - lo);                   // dword-aligned in every row
+    for (uint32_t d = d0; d < d1; d += kSelU8Rows) {
+        uint32_t v[kSelU8Rows];
+#pragma unroll
+        for (int u = 0; u < kSelU8Rows; ++u) {
+            v[u] = 0;
+            if (m4 && d + u < d1) v[u] = *reinterpret_cast<const uint32_t*>(src + (size_t)(d + u) * ldN);
+        }
+#pragma unroll
+        for (int u = 0; u < kSelU8Rows; ++u) {
+            uint8_t* st = reinterpret_cast<uint8_t*>(stage[w][u]) + lo;
+            if (m4 & 0x1u) st[r[0]] = (uint8_t)v[u];
+            if (m4 & 0x100u) st[r[1]] = (uint8_t)(v[u] >> 8);
+            if (m4 & 0x10000u) st[r[2]] = (uint8_t)(v[u] >> 16);
+            if (m4 & 0x1000000u) st[r[3]] = (uint8_t)(v[u] >> 24);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int u = 0; u < kSelU8Rows; ++u) {
+            if (d + u >= d1) break;
+            uint8_t* row = S0 + (size_t)(d + u) * ldS;
+            for (uint32_t j = (uint32_t)lane; j < ndw; j += 64) {
+                const uint32_t word = stage[w][u][j];
+                const uint32_t b0 = 4 * j;
+                if (b0 >= lo && b0 + 4 <= hi) {
+                    *reinterpret_cast<uint32_t*>(row + b0) = word;
+                } else {
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; ++c)
+                        if (b0 + c >= lo && b0 + c < hi) row[b0 + c] = (uint8_t)(word >> (8 * c));
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();  // the next round overwrites the staged rows
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
 // 3. The results of a search on the selection, in place: idx[t] = base + map[idx[t]] for t < n (a selection index >= npass cannot
 //    come out of an engine; it is left as it is).
 __global__ __launch_bounds__(256) void select_remap_kernel(uint64_t* __restrict__ idx, size_t n, const uint32_t* __restrict__ map,

@@ -402,13 +402,16 @@ __global__ __launch_bounds__(64) void rescore_u8_kernel(const uint8_t* __restric
 }
 
 // fused top-k variant (see kernels_scan.h scan_filter_kernel)
-template <int QB, int R>
+// MASK (innr_batch_knn_u8_filtered's masked exact scan): mask[0, ldN) holds 0/1 bytes (zero beyond N); a vector whose byte is 0 is
+// never appended, and a wave step none of whose 1024 vectors pass is skipped before its codes are read. MASK = false ignores `mask`.
+template <int QB, int R, bool MASK = false>
 __global__ __launch_bounds__(256) void scan_u8_filter_kernel(const uint8_t* __restrict__ C, size_t ldN, uint32_t N,
                                                              uint32_t D, const float* __restrict__ Qm, size_t ldq,
                                                              const float* __restrict__ qsum, float a255, float offset,
                                                              uint64_t* __restrict__ lists, uint32_t* __restrict__ counts,
                                                              uint32_t qstride, uint32_t KP, uint32_t chunks_per_slot,
-                                                             uint32_t* __restrict__ errflag, uint32_t nvalid = 0xFFFFFFFFu) {
+                                                             uint32_t* __restrict__ errflag, uint32_t nvalid = 0xFFFFFFFFu,
+                                                             const uint8_t* __restrict__ mask = nullptr) {
     constexpr uint32_t cap = 64 * R;
     __shared__ uint32_t s_cnt[4][QB];
     __shared__ uint32_t s_thr[4][QB];
@@ -430,6 +433,12 @@ __global__ __launch_bounds__(256) void scan_u8_filter_kernel(const uint8_t* __re
     uint64_t* my_lists = lists + (slot * (size_t)qstride + qoff) * cap;
     for (size_t ch = ch0; ch < ch1; ++ch) {
         const size_t col = ch * kU8Chunk + (size_t)lane * 16;
+        uint32_t mw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (MASK) {
+            const uint4 m = *reinterpret_cast<const uint4*>(mask + col);
+            mw[0] = m.x; mw[1] = m.y; mw[2] = m.z; mw[3] = m.w;
+            if (!__any((mw[0] | mw[1] | mw[2] | mw[3]) != 0u)) continue;  // wave-uniform
+        }
         float acc[QB][16];
         scan_u8_accumulate<QB>(C, ldN, D, col, Qm, ldq, acc);
         // admit in four quarter-steps of 4 codes per lane (256 candidates per query at most, = kBurst), checking
@@ -445,7 +454,8 @@ __global__ __launch_bounds__(256) void scan_u8_filter_kernel(const uint8_t* __re
                     const int c = 4 * c4 + cc;
                     const size_t i = col + c;
                     const uint32_t pref = f32_ord(u8_score(a255, acc[j][c], offset, qs));
-                    if (i < N && pref >= thr && qoff + j < nvalid)  // (beyond nvalid: zero rows padding a ragged query tail)
+                    const bool pass = !MASK || ((mw[c4] >> (8 * cc)) & 0xffu) != 0u;
+                    if (i < N && pass && pref >= thr && qoff + j < nvalid)  // (beyond nvalid: zero rows padding a ragged query tail)
                         cand_append(my_lists + (size_t)j * cap, &s_cnt[w][j], cap, cand_make(pref, (uint32_t)i), errflag);
                 }
             }
@@ -475,6 +485,81 @@ __global__ __launch_bounds__(256) void scan_u8_filter_kernel(const uint8_t* __re
             c = wave_compact<R>(my_lists + (size_t)j * cap, c, KP, &t);
         }
         if (lane == 0) counts[slot * qstride + qoff + j] = c;
+    }
+}
+
+// ---- range search on codes (innr_batch_range_search_u8): range_scan_kernel's two launches (kernels_scan.h) on scan_u8_accumulate --
+// A vector survives for query j iff !(score < thr[j]), score = u8_score(...) with the bits of scan_u8_scores_kernel, so a NaN score or
+// threshold survives. One wave step covers kU8Chunk = 1024 vectors, a lane owns 16 consecutive ones; survivors are counted per chunk:
+//   EMIT = false: cnt[q][ch] = survivors of query q in chunk ch (every chunk is written);
+//   EMIT = true : cnt holds each query's exclusive prefix over the chunks, its total at [nchunks] (range_chunk_scan_kernel). A chunk
+//     where no query of the group has a survivor is skipped before its codes are read; survivor i lands at qoff[q] + cnt[q][ch] +
+//     (survivors of the chunk below i) = the codes of the lower lanes (a wave prefix sum of the lanes' counts 0..16), then this
+//     lane's earlier codes. Only positions < cap are written.
+// Query groups of QB on blockIdx.y; the ragged last group is moved back to end on the last query (nq >= QB) and writes only the
+// queries the group before does not, as in range_scan_kernel.
+template <int QB, bool EMIT>
+__global__ __launch_bounds__(256) void range_scan_u8_kernel(const uint8_t* __restrict__ C, size_t ldN, uint32_t N, uint32_t D,
+                                                            const float* __restrict__ Qm, size_t ldq, const float* __restrict__ qsum,
+                                                            float a255, float offset, const float* __restrict__ thr, uint32_t nq,
+                                                            uint32_t* __restrict__ cnt, size_t ldc, const uint64_t* __restrict__ qoff,
+                                                            uint64_t index_base, uint64_t* __restrict__ out_idx,
+                                                            float* __restrict__ out_score, uint64_t cap) {
+    const uint32_t g0 = blockIdx.y * QB;                // first query this group writes
+    const uint32_t qb0 = g0 + QB <= nq ? g0 : nq - QB;  // first query it scores
+    Qm += (size_t)qb0 * ldq;
+    const size_t nchunks = ldN / kU8Chunk;
+    const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * 256) >> 6;
+    const int lane = threadIdx.x & 63;
+    for (size_t ch = wave; ch < nchunks; ch += nwaves) {
+        if (EMIT) {
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < QB; ++j)
+                if (qb0 + j >= g0) any |= cnt[(size_t)(qb0 + j) * ldc + ch + 1] != cnt[(size_t)(qb0 + j) * ldc + ch];
+            if (!any) continue;  // wave-uniform
+        }
+        const size_t col = ch * kU8Chunk + (size_t)lane * 16;
+        float acc[QB][16];
+        scan_u8_accumulate<QB>(C, ldN, D, col, Qm, ldq, acc);
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
+            if (qb0 + j < g0) continue;  // scored for the group before (wave-uniform)
+            const float t = thr[qb0 + j], qs = qsum[qb0 + j];
+            uint32_t keep = 0;  // bit c: this lane's code c survives
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                acc[j][c] = u8_score(a255, acc[j][c], offset, qs);
+                if (col + c < N && !(acc[j][c] < t)) keep |= 1u << c;
+            }
+            const uint32_t mine = (uint32_t)__popc(keep);
+            if (!EMIT) {
+                uint32_t total = mine;
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) total += (uint32_t)__shfl_xor((int)total, off, 64);
+                if (lane == 0) cnt[(size_t)(qb0 + j) * ldc + ch] = total;
+            } else {
+                uint32_t incl = mine;  // inclusive prefix sum over the lanes
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
+                    if (lane >= off) incl += up;
+                }
+                if (keep) {
+                    uint64_t pos = qoff[qb0 + j] + cnt[(size_t)(qb0 + j) * ldc + ch] + (incl - mine);
+#pragma unroll
+                    for (int c = 0; c < 16; ++c) {
+                        if (keep & (1u << c)) {
+                            if (pos < cap) {
+                                out_idx[pos] = index_base + col + c;
+                                out_score[pos] = acc[j][c];
+                            }
+                            ++pos;
+                        }
+                    }
+                }
+            }
+        }
     }
 }
 

@@ -225,6 +225,117 @@ class QuantizedCorpus(_lib.BatchMemoryMixin):
         r = int(out_k.value)
         return idx[:, :r].reshape(nq, r), sc[:, :r].reshape(nq, r)
 
+    def knn_filtered_multi(self, queries, k: int, mask, engine: int = KNN_AUTO, stats: Optional[KnnStats] = None):
+        """batch_knn_u8 over the documents with mask[i] != 0, for Q queries at once (innr_batch_knn_u8_filtered: the engines other
+        than the exact one search a compact code batch of the passing documents that the corpus keeps for the next call with the
+        same mask). Returns (indices uint64 [Q, k'], scores float32 [Q, k']) with k' = min(k, number passing). `mask`: a NumPy
+        bool / uint8 array of length N; or a device tensor (torch, on the corpus' GPU), and then the device entry point runs: the
+        queries go to the device, the results stay there (int64 / float32 tensors)."""
+        n = self._n
+        st = stats if stats is not None else KnnStats()
+        out_k = C.c_size_t(0)
+        kk = min(int(k), n)
+        if hasattr(mask, "is_cuda") and mask.is_cuda:
+            import torch
+            m = mask.reshape(-1)
+            if m.numel() != n:
+                raise InnrPanic(f"assertion `left == right` failed\n  left: {m.numel()}\n right: {n}")
+            m = m.to(torch.uint8).contiguous() if m.dtype != torch.uint8 else m.contiguous()
+            q = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32))
+            q = q.to(device=m.device, dtype=torch.float32)
+            if q.ndim == 1:
+                q = q.reshape(1, -1)
+            q = q.contiguous()
+            nq, d = q.shape
+            self._ctx.bind_torch_stream()  # the mask and queries were produced on torch's stream, the results are consumed there
+            idx = torch.empty((max(nq * kk, 1),), dtype=torch.int64, device=m.device)
+            sc = torch.empty((max(nq * kk, 1),), dtype=torch.float32, device=m.device)
+            check(load().innr_batch_knn_u8_filtered_dev(self._h, C.c_void_p(q.data_ptr()), nq, d, int(k),
+                                                        C.c_void_p(m.data_ptr()) if n else None, engine, C.c_void_p(idx.data_ptr()),
+                                                        C.c_void_p(sc.data_ptr()), C.byref(out_k), C.byref(st)))
+            r = int(out_k.value)
+            return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+        m = np.asarray(mask)
+        if m.dtype != np.uint8:
+            m = m.astype(bool).astype(np.uint8)
+        m = np.ascontiguousarray(m.reshape(-1))
+        if m.size != n:
+            raise InnrPanic(f"assertion `left == right` failed\n  left: {m.size}\n right: {n}")
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, d = q.shape
+        idx = np.empty(max(nq * kk, 1), dtype=np.uint64)
+        sc = np.empty(max(nq * kk, 1), dtype=np.float32)
+        check(load().innr_batch_knn_u8_filtered(self._h, _vp(q) if q.size else None, nq, d, int(k), _vp(m) if m.size else None, engine,
+                                                _vp(idx), _vp(sc), C.byref(out_k), C.byref(st)))
+        r = int(out_k.value)
+        return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+
+    def range_search(self, queries, thresholds, engine: int = KNN_AUTO, stats: Optional[KnnStats] = None, cap: Optional[int] = None):
+        """Every document whose asymmetric score reaches a per-query threshold (innr_batch_range_search_u8): query j keeps the
+        documents with !(score < thresholds[j]), in index order. Returns (offsets uint64 [Q + 1], indices uint64 [total], scores
+        float32 [total]); query j owns [offsets[j], offsets[j + 1]). A scalar threshold is broadcast to all queries. cap: room for
+        that many results -- the offsets are the full ones, indices / scores hold the first min(total, cap) entries, 0 only
+        counts; None: one call with a guessed capacity and, only if that was exceeded, a second one with room for everything.
+        Torch device tensors (queries on the corpus' GPU) take the device entry point: thresholds go to the device, offsets
+        (int64), indices (int64) and scores stay there."""
+        n = self._n
+        lib = load()
+        st = stats if stats is not None else KnnStats()
+        total = C.c_size_t(0)
+        if hasattr(queries, "is_cuda") and queries.is_cuda:
+            import torch
+            q = queries.to(torch.float32)
+            if q.ndim == 1:
+                q = q.reshape(1, -1)
+            q = q.contiguous()
+            nq, d = q.shape
+            t = thresholds if isinstance(thresholds, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1))
+            t = t.to(device=q.device, dtype=torch.float32).reshape(-1)
+            if t.numel() == 1 and nq != 1:
+                t = t.expand(nq)
+            if t.numel() != nq:
+                raise InnrPanic(f"assertion `left == right` failed\n  left: {t.numel()}\n right: {nq}")
+            t = t.contiguous()
+            self._ctx.bind_torch_stream()  # the queries were produced on torch's stream, the results are consumed there
+            off = torch.zeros((nq + 1,), dtype=torch.int64, device=q.device)
+
+            def call(room: int):
+                idx = torch.empty((max(room, 1),), dtype=torch.int64, device=q.device)
+                sc = torch.empty((max(room, 1),), dtype=torch.float32, device=q.device)
+                check(lib.innr_batch_range_search_u8_dev(self._h, C.c_void_p(q.data_ptr()), nq, d,
+                                                         C.c_void_p(t.data_ptr()) if nq else None, engine, C.c_void_p(off.data_ptr()),
+                                                         C.c_void_p(idx.data_ptr()), C.c_void_p(sc.data_ptr()), room, C.byref(total),
+                                                         C.byref(st)))
+                return idx, sc
+        else:
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            if q.ndim == 1:
+                q = q.reshape(1, -1)
+            nq, d = q.shape
+            t = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+            if t.size == 1 and nq != 1:
+                t = np.full(nq, t[0], dtype=np.float32)
+            if t.size != nq:
+                raise InnrPanic(f"assertion `left == right` failed\n  left: {t.size}\n right: {nq}")
+            off = np.zeros(nq + 1, dtype=np.uint64)
+
+            def call(room: int):
+                idx = np.empty(max(room, 1), dtype=np.uint64)
+                sc = np.empty(max(room, 1), dtype=np.float32)
+                check(lib.innr_batch_range_search_u8(self._h, _vp(q) if q.size else None, nq, d, _vp(t) if t.size else None, engine,
+                                                     _vp(off), _vp(idx), _vp(sc), room, C.byref(total), C.byref(st)))
+                return idx, sc
+        room = int(cap) if cap is not None else min(nq * n, max(1 << 16, 256 * nq))
+        idx, sc = call(room)
+        if cap is None and int(total.value) > room:
+            room = int(total.value)
+            idx, sc = call(room)
+        r = min(int(total.value), room)
+        return off, idx[:r], sc[:r]
+
     # ---- persistence: the codes in their device order data[d*N + i] behind a 32-byte header (cf. VerticalBatch.save) -----
     _MAGIC = b"INNRU8C1"  # magic, u64 n, u64 dim, f32 alpha, f32 offset, then dim x n bytes
 

@@ -83,6 +83,10 @@ pub mod ffi {
         pub fn innr_batch_scores_u8(b: *mut InnrBatch, q: *const f32, d: usize, out: *mut f32) -> c_int;
         pub fn innr_batch_knn_u8(b: *mut InnrBatch, queries: *const f32, q: usize, d: usize, k: usize, engine: c_int, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_knn_u8_dev(b: *mut InnrBatch, d_queries: *const f32, q: usize, d: usize, k: usize, engine: c_int, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_knn_u8_filtered(b: *mut InnrBatch, queries: *const f32, q: usize, d: usize, k: usize, mask: *const u8, engine: c_int, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_knn_u8_filtered_dev(b: *mut InnrBatch, d_queries: *const f32, q: usize, d: usize, k: usize, d_mask: *const u8, engine: c_int, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_range_search_u8(b: *mut InnrBatch, queries: *const f32, q: usize, d: usize, thresholds: *const f32, engine: c_int, out_offsets: *mut u64, out_idx: *mut u64, out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_range_search_u8_dev(b: *mut InnrBatch, d_queries: *const f32, q: usize, d: usize, d_thresholds: *const f32, engine: c_int, d_out_offsets: *mut u64, d_out_idx: *mut u64, d_out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_quantize_u8(values: *const f32, n: usize, alpha: f32, offset: f32, out: *mut u8);
         pub fn innr_mixed_dot_u8_f32(a: *const f32, b: *const u8, n: usize) -> f32;
         pub fn innr_batch_quantize_u8(f32_batch: *mut InnrBatch, alpha: f32, offset: f32, out: *mut *mut InnrBatch) -> c_int;
@@ -576,6 +580,38 @@ pub mod scalar {
             check(unsafe { ffi::innr_batch_knn_u8(self.h, query.as_ptr(), 1, query.len(), k, ffi::INNR_KNN_AUTO,
                                                   idx.as_mut_ptr(), sc.as_mut_ptr(), &mut n, std::ptr::null_mut()) });
             (0..n).map(|i| (idx[i] as usize, sc[i])).collect()
+        }
+        /// scalar.rs:370-393 over the documents with `mask[i]`, for every query of `queries` (row-major, `dimension()` values
+        /// each): `(index, score)` best first, min(k, number passing) per query (innr_batch_knn_u8_filtered)
+        #[must_use] pub fn knn_filtered_multi(&self, engine: i32, queries: &[f32], k: usize, mask: &[bool]) -> Vec<Vec<(usize, f32)>> {
+            assert_eq!(mask.len(), self.n);
+            let q = if self.dim == 0 { 0 } else { queries.len() / self.dim };
+            assert_eq!(queries.len(), q * self.dim);
+            let bytes: Vec<u8> = mask.iter().map(|&m| m as u8).collect();
+            let kk = k.min(self.n);
+            let (mut idx, mut sc, mut out_k) = (vec![0u64; q * kk.max(1)], vec![0f32; q * kk.max(1)], 0usize);
+            check(unsafe { ffi::innr_batch_knn_u8_filtered(self.h, queries.as_ptr(), q, self.dim, k, bytes.as_ptr(), engine,
+                                                           idx.as_mut_ptr(), sc.as_mut_ptr(), &mut out_k, std::ptr::null_mut()) });
+            (0..q).map(|j| (j * out_k..(j + 1) * out_k).map(|i| (idx[i] as usize, sc[i])).collect()).collect()
+        }
+        /// every document with `!(score < thresholds[j])` for query j, in index order (innr_batch_range_search_u8): a count-only
+        /// call sizes the buffers, a second one fills them
+        #[must_use] pub fn range_search(&self, engine: i32, queries: &[f32], thresholds: &[f32]) -> Vec<Vec<(usize, f32)>> {
+            let q = thresholds.len();
+            assert_eq!(queries.len(), q * self.dim);
+            let mut off = vec![0u64; q + 1];
+            let mut total = 0usize;
+            check(unsafe { ffi::innr_batch_range_search_u8(self.h, queries.as_ptr(), q, self.dim, thresholds.as_ptr(), engine,
+                                                           off.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total,
+                                                           std::ptr::null_mut()) });
+            let cap = total;
+            let (mut idx, mut sc) = (vec![0u64; cap.max(1)], vec![0f32; cap.max(1)]);
+            if cap > 0 {
+                check(unsafe { ffi::innr_batch_range_search_u8(self.h, queries.as_ptr(), q, self.dim, thresholds.as_ptr(), engine,
+                                                               off.as_mut_ptr(), idx.as_mut_ptr(), sc.as_mut_ptr(), cap, &mut total,
+                                                               std::ptr::null_mut()) });
+            }
+            (0..q).map(|j| (off[j] as usize..off[j + 1] as usize).map(|i| (idx[i] as usize, sc[i])).collect()).collect()
         }
         pub fn len(&self) -> usize { self.n }
         pub fn is_empty(&self) -> bool { self.n == 0 }
