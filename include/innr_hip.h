@@ -110,7 +110,8 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * no_auto_i8, u8_no_i8, rescore_all, maxsim_generic, no_k_rule, no_completion, no_rows_copy, i8_slices_per_cu, i8_no_small, i8_no_small4, i8_small_max_q, i8_small_free, trace, fail_local_search (a test
  * switch of the sharded calls), filter_keep_selection (default 1; 0: innr_batch_knn_filtered_multi and innr_batch_knn_u8_filtered
  * free their selection at the end of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
- * innr_batch_set_copy_budget) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
+ * innr_batch_set_copy_budget), scan_max_slots (default 0 = fill the chip: the most wave slots an exact scan is cut into, rounded
+ * up to a multiple of 4, so that a wave owns several chunks of a small corpus) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
 const char* innr_last_error(void);

@@ -44,7 +44,7 @@ static const TuneName kTuneNames[] = {
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
     {"split_min_q", &innr_tuning::split_min_q}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
-    {"copy_budget_mib", &innr_tuning::copy_budget_mib},
+    {"copy_budget_mib", &innr_tuning::copy_budget_mib}, {"scan_max_slots", &innr_tuning::scan_max_slots},
 };
 static void tuning_from_env(innr_tuning* t) {
     for (const TuneName& n : kTuneNames) {
@@ -357,7 +357,8 @@ struct ScanExt {
 };
 
 // one launch of scan_filter_kernel: `groups` groups of qb (8, 4 or 1) queries. (The exact scans are not a recorded family: one runs
-// inside most recorded calls -- threshold seeding, the redo of unproven queries -- and the record's readers decode a closed set.)
+// inside most recorded calls -- threshold seeding, the redo of unproven queries -- and the record's readers decode a closed set.
+// They have a record of their own, innr_ctx::scan_log, with the geometry of each launch.)
 static innr_status launch_scan_filter(innr_batch* b, int metric, uint32_t qb, const float* dQ, size_t ldq, const float* dQn,
                                       uint32_t nblocks, uint32_t qstride, uint32_t KP, uint32_t cap, uint32_t cps,
                                       const ScanExt& ext, uint32_t groups) {
@@ -366,6 +367,7 @@ static innr_status launch_scan_filter(innr_batch* b, int metric, uint32_t qb, co
     // the extended kernel: a mask (innr_batch_knn_filtered_multi, every metric) or a dimension order (squared L2 only)
     const uint32_t* order = l2 ? ext.order : nullptr;
     dispatch([&](auto QB, auto met, auto rr, auto extended) {
+        record_scan(c, kScanF32, QB, met, rr, extended != 0, cps, (size_t)nblocks * (kScanThreads / 64), groups);
         scan_filter_kernel<QB, met == INNR_METRIC_L2SQ, met == INNR_METRIC_COSINE, rr, extended != 0>
             <<<dim3(nblocks, groups), kScanThreads, 0, c->stream>>>(
                 b->V, b->ldN, (uint32_t)b->N, (uint32_t)b->D, dQ, ldq, cos ? b->norms : nullptr, cos ? dQn : nullptr, c->lists.as<uint64_t>(),
@@ -425,7 +427,7 @@ static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* 
     // wave slots: fill the chip to the occupancy the register budget allows (HBM latency needs the waves: the
     // single-query kernel holds 72 VGPRs = 7 waves/SIMD) but never more than there are chunks
     const size_t waves_per_cu = nq >= 8 ? 16 : 24;
-    size_t nslots = std::min<size_t>(nchunks, (size_t)c->num_cus * waves_per_cu);
+    size_t nslots = cap_scan_slots(c, std::min<size_t>(nchunks, (size_t)c->num_cus * waves_per_cu));
     nslots = round_up(nslots, kScanThreads / 64);
     const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
     const uint32_t nblocks = (uint32_t)(nslots / (kScanThreads / 64));
@@ -1860,6 +1862,26 @@ extern "C" void innrdbg_launch_log_reset(innr_ctx* c) {
     c->launch_total = 0;
 }
 
+// Test hook: the context's record of exact-scan launches (innr_ctx::scan_log), oldest first: up to `cap` entries of 20 bytes
+// (ScanRec) into `out`, the number written returned; *total = scans recorded since the last reset (beyond kScanLogCap the oldest
+// are gone).
+extern "C" size_t innrdbg_scan_log(innr_ctx* c, void* out, size_t cap, uint64_t* total) {
+    if (!c) return 0;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    static_assert(sizeof(ScanRec) == 20, "the hook's reader decodes 20-byte entries");
+    if (total) *total = c->scan_total;
+    const uint64_t have = std::min<uint64_t>(c->scan_total, kScanLogCap);
+    const size_t n = out ? (size_t)std::min<uint64_t>(have, cap) : 0;
+    for (size_t i = 0; i < n; ++i)  // the last n entries
+        static_cast<ScanRec*>(out)[i] = c->scan_log[(c->scan_total - n + i) % kScanLogCap];
+    return n;
+}
+extern "C" void innrdbg_scan_log_reset(innr_ctx* c) {
+    if (!c) return;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    c->scan_total = 0;
+}
+
 #endif  // INNR_TEST_HOOKS
 
 // Second stage of the two-stage pipeline the reference describes (scalar.rs:366-368: batch_knn_u8 first pass, then an
@@ -2603,6 +2625,7 @@ static innr_status launch_scan_u8(innr_batch* b, uint32_t qb, const float* dQ, s
     const uint32_t nvalid = (uint32_t)((limit_n && limit_n < b->N) ? limit_n : b->N);
     const float a255 = b->alpha / 255.0f;  // scalar.rs:299 (params.alpha / 255.0), f32
     dispatch([&](auto QB, auto rr) {
+        record_scan(c, kScanU8, QB, INNR_METRIC_DOT, rr, mask != nullptr, cps, (size_t)nblocks * 4, groups);
         if (mask)  // the masked scan is a recorded family; the plain one runs inside most recorded calls and is not (cf. launch_scan_filter)
             launch_kernel(c, Inst<kLaunchScanU8Masked, QB, rr>(), {dim3(nblocks, groups), 256, 0, groups}, b->C8, b->ldN, nvalid,
                           (uint32_t)b->D, dQ, ldq, qsum, a255, b->offset, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(),
@@ -2627,7 +2650,7 @@ static innr_status knn_u8_exact_range(innr_batch* b, const float* dQ, size_t ldq
     const uint32_t cap = exact_cap(KP);
     const size_t cols = (limit_n && limit_n < b->N) ? round_up(limit_n, kU8Chunk) : b->ldN;  // columns that are scanned
     const size_t nchunks = cols / kU8Chunk;
-    size_t nslots = std::min<size_t>(nchunks, (size_t)c->num_cus * 16);
+    size_t nslots = cap_scan_slots(c, std::min<size_t>(nchunks, (size_t)c->num_cus * 16));
     nslots = round_up(nslots, 4);
     const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
     const uint32_t nblocks = (uint32_t)(nslots / 4);

@@ -73,6 +73,7 @@ struct innr_tuning {
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
+    long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip
 };
 
 // One templated kernel launch of the filter and scan families, as its dispatch site chose it (innr_ctx::launch_log). Written by
@@ -101,6 +102,23 @@ struct LaunchRec {
 };
 constexpr size_t kLaunchLogCap = 64;
 
+// One launch of an exact scan with per-wave candidate lists (topk_dev.h), with the geometry its launch site derived
+// (innr_ctx::scan_log). A record of its own, beside launch_log: an exact scan runs inside most recorded calls, and launch_log's
+// readers decode a closed set of families. Written by plain host stores at the three launch sites, in every build; read only by
+// the test hook innrdbg_scan_log, which tests/test_gpu_scan_threshold.py decodes.
+enum ScanKind { kScanF32 = 1, kScanU8 = 2, kScanDense = 3 };  // scan_filter_kernel / scan_u8_filter_kernel / dense_filter_kernel
+struct ScanRec {
+    uint8_t kind;    // ScanKind
+    uint8_t qb;      // QB: queries per corpus pass (dense: 1)
+    uint8_t metric;  // INNR_METRIC_* of the f32 scan (u8, dense: INNR_METRIC_DOT)
+    uint8_t rr;      // R: list capacity / 64
+    uint8_t ext;     // EXT of the f32 scan (a mask or a dimension order), MASK of the u8 scan
+    uint8_t pad[3];
+    uint32_t cps;     // chunks per wave slot
+    uint32_t nslots;  // wave slots
+    uint32_t groups;  // query groups of the launch
+};
+constexpr size_t kScanLogCap = 16;
 struct innr_ctx {
     innr_tuning tune;
     // One call at a time per context: the workspace below (grow-by-free DevBufs, the pinned bump allocator, `pending`,
@@ -169,7 +187,22 @@ struct innr_ctx {
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
+    ScanRec scan_log[kScanLogCap] = {};        // ring of the last exact-scan launches (record_scan; read by a test hook)
+    uint64_t scan_total = 0;                   // ... recorded so far: entry i lives at scan_log[i % kScanLogCap]
 };
+
+// wave slots of an exact scan under the option scan_max_slots (a multiple of 4, at least 4); applied before cps, the block count
+// and the groups per launch are derived from the slot count
+static inline size_t cap_scan_slots(const innr_ctx* c, size_t nslots) {
+    const long v = c->tune.scan_max_slots;
+    return v > 0 ? std::min<size_t>(nslots, round_up((size_t)std::max<long>(v, 4), 4)) : nslots;
+}
+// (the caller holds the context's lock, as every launch site does)
+static inline void record_scan(innr_ctx* c, ScanKind kind, int qb, int metric, int rr, bool ext, uint32_t cps, size_t nslots,
+                               uint32_t groups) {
+    c->scan_log[c->scan_total++ % kScanLogCap] =
+        ScanRec{(uint8_t)kind, (uint8_t)qb, (uint8_t)metric, (uint8_t)rr, (uint8_t)ext, {0, 0, 0}, cps, (uint32_t)nslots, groups};
+}
 
 // ---- choosing a kernel instantiation from run-time values ------------------------------------------------------------
 // One instantiation of a recorded family, as compile-time constants: the family and the template arguments in the order of

@@ -217,7 +217,7 @@ static innr_status maxsim_select(innr_docs* d, uint32_t KP, const float* sc) {
     innr_ctx* c = d->ctx;
     const uint32_t cap = exact_cap(KP);
     const size_t nchunks = (d->ndocs + 255) / 256;
-    size_t nslots = round_up(std::min<size_t>(nchunks, (size_t)c->num_cus * 8), 4);
+    size_t nslots = round_up(cap_scan_slots(c, std::min<size_t>(nchunks, (size_t)c->num_cus * 8)), 4);
     const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
     INNR_TRY(c->lists.ensure(nslots * cap * sizeof(uint64_t)));
     INNR_TRY(c->counts.ensure(nslots * sizeof(uint32_t)));
@@ -226,6 +226,7 @@ static innr_status maxsim_select(innr_docs* d, uint32_t KP, const float* sc) {
     uint32_t* counts = c->counts.as<uint32_t>();
     uint32_t* err = c->flags.as<uint32_t>();
     dispatch([&](auto rr) {
+        record_scan(c, kScanDense, 1, INNR_METRIC_DOT, rr, false, cps, nslots, 1);
         dense_filter_kernel<rr><<<nb, 256, 0, c->stream>>>(sc, (uint32_t)d->ndocs, lists, counts, KP, cps, err);
     }, rr_scan(cap));
     INNR_HIP_CHECK(hipGetLastError());

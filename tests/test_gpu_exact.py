@@ -3,9 +3,11 @@ C ABI (ctypes -> libinnr_hip.so), compared with the CPU oracle on the same seede
 Bar: bit-exact scores, identical index lists."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import os
+from typing import NamedTuple
 
 import numpy as np
 import pytest
@@ -299,17 +301,85 @@ def test_generated_nan_sign_and_rank_are_pinned(B, innr):
     assert int(oi[-1]) == 1234 and os_[-1:].view(np.uint32)[0] == 0xFFC00000
 
 
-def test_knn_monotone_scores_force_many_compactions(B, innr):
+# The record of exact-scan launches (api_internal.h: innr_ctx::scan_log, ScanRec; read through the test hooks innrdbg_scan_log /
+# innrdbg_scan_log_reset): which instantiation ran, and with which geometry.
+SCAN_KINDS = {1: "f32", 2: "u8", 3: "dense"}  # api_internal.h ScanKind
+_SCAN_REC = np.dtype({"names": ["kind", "qb", "metric", "rr", "ext", "cps", "nslots", "groups"],
+                      "formats": ["u1", "u1", "u1", "u1", "u1", "<u4", "<u4", "<u4"], "offsets": [0, 1, 2, 3, 4, 8, 12, 16],
+                      "itemsize": 20})
+SCAN_LOG_CAP = 16  # api_internal.h kScanLogCap
+
+
+class Scan(NamedTuple):
+    kind: str     # SCAN_KINDS
+    qb: int       # queries per corpus pass
+    metric: int   # INNR_METRIC_* (f32 scan)
+    rr: int       # list capacity / 64
+    ext: bool     # EXT (f32) / MASK (u8)
+    cps: int      # chunks per wave slot
+    nslots: int   # wave slots
+    groups: int   # query groups of the launch
+
+    @property
+    def inst(self):
+        """("f32", QB, metric, R, EXT), ("u8", QB, R, MASK) or ("dense", R)"""
+        if self.kind == "f32":
+            return ("f32", self.qb, self.metric, self.rr, int(self.ext))
+        return ("u8", self.qb, self.rr, int(self.ext)) if self.kind == "u8" else ("dense", self.rr)
+
+
+def _scan_hook():
+    from conftest import hooks_lib
+    L = hooks_lib()
+    L.innrdbg_scan_log.restype = C.c_size_t
+    L.innrdbg_scan_log.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.innrdbg_scan_log_reset.restype = None
+    L.innrdbg_scan_log_reset.argtypes = [C.c_void_p]
+    return L
+
+
+def scanned(call):
+    """reset the scan record, run `call`, return (its result, the exact scans it launched, oldest first)"""
+    from innr_amd import _lib
+    h = _lib.default_context().handle
+    L = _scan_hook()
+    L.innrdbg_scan_log_reset(h)
+    res = call()
+    buf = np.zeros(SCAN_LOG_CAP, _SCAN_REC)
+    total = C.c_uint64(0)
+    n = L.innrdbg_scan_log(h, buf.ctypes.data, SCAN_LOG_CAP, C.byref(total))
+    assert total.value == n, f"{total.value} exact scans since the reset: more than the record's {SCAN_LOG_CAP} entries"
+    return res, [Scan(SCAN_KINDS[int(r["kind"])], int(r["qb"]), int(r["metric"]), int(r["rr"]), bool(r["ext"]), int(r["cps"]),
+                      int(r["nslots"]), int(r["groups"])) for r in buf[:n]]
+
+
+def test_knn_monotone_scores_force_many_compactions(B, innr, ctx_option):
     # scores increase with the index: every vector beats the running threshold, so candidate lists fill and
-    # compact over and over (the worst case of the threshold filter).
+    # compact over and over (the worst case of the threshold filter). At the default geometry every wave of this corpus owns ONE
+    # chunk and compacts at most once; the second run cuts the scan into four wave slots (scan_max_slots), so that each wave
+    # walks 196 chunks -- the scan record shows it -- and really compacts over and over.
     n = 200_000
     rows = np.zeros((n, 2), dtype=np.float32)
     rows[:, 0] = np.arange(n, dtype=np.float32) * np.float32(0.001)
     rows[:, 1] = 1.0
     data = oracle.from_rows(rows)
     q = np.float32([[1.0, 0.5], [-1.0, 0.25], [0.0, 1.0]])
+    vb = B.VerticalBatch.from_rows(rows)
+    fns = {"dot": (B.batch_knn_dot_multi, oracle.batch_knn_dot), "cos": (B.batch_knn_cosine_multi, oracle.batch_knn_cosine),
+           "l2": (B.batch_knn_multi, oracle.batch_knn)}
     for metric, k in (("dot", 10), ("l2", 10), ("dot", 100), ("cos", 33)):
-        _check_knn(B, innr, metric, rows, data, q, k, innr.KNN_EXACT)
+        fn, ofn = fns[metric]
+        expect = [ofn(qj, data, k) for qj in q]
+        for max_slots in (0, 4):
+            if max_slots:
+                ctx_option("scan_max_slots", max_slots)
+            (idx, sc), log = scanned(lambda: fn(q, vb, k, engine=innr.KNN_EXACT))
+            assert idx.shape == (len(q), k)
+            for j, (oi, os_) in enumerate(expect):
+                assert same_knn(metric, idx[j], sc[j], oi, os_), (metric, max_slots, j, idx[j], oi, sc[j], os_)
+            if max_slots:
+                assert log and all(e.kind == "f32" and e.nslots == 4 and e.cps >= 6 for e in log), log
+                ctx_option("scan_max_slots", 0)
 
 
 def test_index_base_offsets_reported_indices(B, innr):
