@@ -413,6 +413,51 @@ innr_status innr_batch_knn_adaptive(innr_batch* b, const float* queries, size_t 
 innr_status innr_batch_knn_adaptive_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, size_t k, size_t warmup_dims,
                                         uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats);
 
+/* ---- search by stored vector (no reference counterpart beyond the accessor: the reference's corpus lives in host memory) ---- */
+/* VerticalBatch::extract_vector (batch.rs:217) for n vectors at once: out[j*D + d] = vector idx[j], dimension d. Nothing but the
+ * n rows moves: the corpus is not downloaded, and the row-major copy (INNR_COPY_ROWS) is read when the batch already has one
+ * (and the option no_rows_copy is off) but never built for this -- reading a few rows allocates nothing of the corpus' size.
+ * Indices are GLOBAL (index base + local index), like innr_batch_rerank's candidates; duplicates and any order are allowed. An
+ * index outside [base, base + N): INNR_E_BAD_ARG with a message naming the range. The host entry point checks before it moves
+ * anything; the _dev entry point finds such an index on the device and reports it at the end of the call -- the kernels neither
+ * read nor write out of bounds for it, the output is then unspecified.
+ * A copy, no arithmetic: every bit pattern arrives unchanged (a NaN's sign and payload, -0.0, denormals, +-inf). On a prefix view D
+ * and the rows are the view's.
+ * Order of the checks: a null batch or a u8 code batch: INNR_E_BAD_ARG; n == 0 or D == 0: INNR_OK, nothing written; null idx /
+ * out with work to do: INNR_E_BAD_ARG.
+ * Memory: the host entry point stages indices and rows in the context's workspace, at most 256 MiB at a time. */
+innr_status innr_batch_gather_rows(innr_batch* b, const uint64_t* idx, size_t n, float* out);
+/* same, d_idx and d_out resident on the device; writes exactly n*D floats; the call synchronises with the host (the index check) */
+innr_status innr_batch_gather_rows_dev(innr_batch* b, const uint64_t* d_idx, size_t n, float* d_out);
+/* innr_batch_knn with the queries taken from the batch itself: query j = vector idx[j] (global indices as above, duplicates and
+ * any order allowed; an index outside the batch: INNR_E_BAD_ARG as above, outputs unspecified). There is no D argument: the
+ * queries have the batch's dimension by construction (a prefix view's: its own). "More like this", k-NN graphs, near-duplicates.
+ * exclude_self == 0: query j's result equals, bit for bit and position for position, innr_batch_knn[_dev]'s for the query
+ *   gather_rows(idx[j]) with the same metric, engine and k; *out_k = min(k, N).
+ * exclude_self != 0: the best k' = min(k, N - 1) of all vectors except idx[j] itself, in the metric's order: innr_batch_knn's
+ *   answer for min(k + 1, N) with the entry whose index is idx[j] removed or, where that entry is absent, the last one removed.
+ *   It is absent in two ways: with the dot metric a vector need not be among its own best, and among duplicates the lower indices
+ *   come first. Exactly one entry is always dropped; when min(k + 1, N) == N the self entry is always present. Other vectors
+ *   equal to idx[j] stay in: the index is excluded, not the value. *out_k = k' (N == 1: 0).
+ * Results at out_idx[j*k' + r], out_score[j*k' + r]. Any k is accepted. With exclude_self the inner search runs with k + 1, so
+ * k = 240 = INNR_MAX_K already takes the path beyond INNR_MAX_K (all N scores sorted, one query at a time).
+ * Order of the checks: a null batch or out_k, a u8 code batch, an unknown metric: INNR_E_BAD_ARG; N == 0, k == 0, Q == 0 or
+ * k' == 0: *out_k = 0; null idx / outputs with work to do: INNR_E_BAD_ARG.
+ * The call works in rounds of at most 4096 queries: gather, search, strip. A round's workspace -- round*D*4 bytes of gathered
+ * rows and, with exclude_self, round*(k + 1)*12 bytes of staged results -- stays within 256 MiB: the round shrinks to fit (by
+ * k + 1 as given, also where N is smaller), never below one query. The host entry point stages the Q indices and the Q*k' results on the device besides.
+ * innr_ctx_memory counts all of it, innr_ctx_trim returns it.
+ * stats: engine = the last round's, queries_fallback and gemm_ms summed over the rounds, candidates_kept their maximum, total_ms
+ * the whole call, gather and strip included.
+ * Out of scope: u8 code batches (a code row is not an f32 query, and the reference defines no de-quantised search), document
+ * corpora, a sharded variant, updating or appending rows, a fused range self-join (compose innr_batch_gather_rows_dev and
+ * innr_batch_range_search_dev), excluding vectors EQUAL to the query. */
+innr_status innr_batch_knn_rows(innr_batch* b, int metric, const uint64_t* idx, size_t Q, size_t k, int exclude_self, int engine,
+                                uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats);
+/* same, d_idx and the outputs resident on the device (innr_batch_knn_dev's conventions) */
+innr_status innr_batch_knn_rows_dev(innr_batch* b, int metric, const uint64_t* d_idx, size_t Q, size_t k, int exclude_self, int engine,
+                                    uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats);
+
 /* ---- pairwise surface kept on the host: called per PAIR by graph indexes, so a kernel
  * launch cannot pay for itself. Plain host functions in the reference's portable arithmetic order. ------------ */
 float innr_dot_f32(const float* a, const float* b, size_t n);    /* dense::dot_portable dense.rs:103; DistDot = -dot, distance.rs:88 */

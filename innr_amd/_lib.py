@@ -145,7 +145,11 @@ SIGNATURES = {
                                               C.POINTER(KnnStats)]),
     "innr_batch_knn_adaptive": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _szp, C.POINTER(KnnStats)]),
     "innr_batch_knn_adaptive_dev": (C.c_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _szp, C.POINTER(KnnStats)]),
-    "innr_merge_topk_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "innr_batch_gather_rows": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "innr_batch_gather_rows_dev": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "innr_batch_knn_rows": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_knn_rows_dev": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_merge_topk_dev":(C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "innr_dot_f32": (C.c_float, [_vp, _vp, _sz]),
     "innr_cosine_f32": (C.c_float, [_vp, _vp, _sz]),
     "innr_l2sq_f32": (C.c_float, [_vp, _vp, _sz]),

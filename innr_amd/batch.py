@@ -8,7 +8,8 @@ A reference panic (assert_eq! on a dimension mismatch) is raised as InnrPanic (a
 Vec<f32> <-> numpy float32 arrays; `_into` variants refill a caller-owned Python list in place.
 
 Additions (the reference has no multi-query API; parity = "the reference called in a loop"):
-  batch_knn_dot_multi / batch_knn_cosine_multi / batch_knn_multi / batch_knn_adaptive_multi.
+  batch_knn_dot_multi / batch_knn_cosine_multi / batch_knn_multi / batch_knn_adaptive_multi;
+  search by stored vector: VerticalBatch.rows, batch_knn_rows, batch_knn_graph.
 
 Every computation runs on the GPU through include/innr_hip.h; nothing here computes scores on the CPU.
 """
@@ -45,6 +46,7 @@ class VerticalBatch(_lib.BatchMemoryMixin):
         self._ctx = ctx
         ctx._children.add(self)
         self._host: Optional[np.ndarray] = None  # lazily downloaded dimension-major copy
+        self._base = 0  # what set_index_base set: rows() takes global indices
 
     # ---- constructors --------------------------------------------------------------------------
     @classmethod
@@ -143,18 +145,48 @@ class VerticalBatch(_lib.BatchMemoryMixin):
             self._host = out
         return self._host
 
+    def rows(self, indices):
+        """Vectors of the batch by GLOBAL index (index base + local index; duplicates and any order allowed), row-major: a NumPy
+        (n, dimension) array for host indices, a float32 tensor on the device for a CUDA int64 tensor (innr_batch_gather_rows[_dev]).
+        Only the n rows move, bit for bit; an index outside the batch raises InnrError."""
+        if hasattr(indices, "is_cuda") and indices.is_cuda:
+            import torch
+            ids = indices.to(torch.int64).reshape(-1).contiguous()
+            n = ids.numel()
+            self._ctx.bind_torch_stream()  # the indices were produced on torch's stream, the rows are consumed there
+            out = torch.empty((n, self._d), dtype=torch.float32, device=ids.device)
+            check(load().innr_batch_gather_rows_dev(self._h, C.c_void_p(ids.data_ptr()) if n else None, n,
+                                                    C.c_void_p(out.data_ptr()) if out.numel() else None))
+            return out
+        ids = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        out = np.empty((ids.size, self._d), dtype=np.float32)
+        check(load().innr_batch_gather_rows(self._h, _vp(ids) if ids.size else None, ids.size, _vp(out) if out.size else None))
+        return out
+
+    def _local_index(self, vec_idx: int) -> int:
+        i = int(vec_idx)
+        if not 0 <= i < self._n:  # the reference indexes a Vec: a panic
+            raise IndexError(f"index out of bounds: the len is {self._n} but the index is {i}")
+        return i
+
     def get(self, dim: int, vec_idx: int) -> float:
-        return float(self.data()[dim, vec_idx])
+        if self._host is not None:
+            return float(self._host[dim, vec_idx])
+        return float(self.extract_vector(vec_idx)[dim])
 
     def dimension_slice(self, dim: int) -> np.ndarray:
         return self.data()[dim]
 
     def extract_vector(self, vec_idx: int) -> np.ndarray:
-        return self.data()[:, vec_idx].copy()
+        """batch.rs:217. From the host copy when data() has made one, otherwise a one-row gather: never a download of the corpus."""
+        if self._host is not None:
+            return self._host[:, vec_idx].copy()
+        return self.rows([self._base + self._local_index(vec_idx)])[0]
 
     def set_index_base(self, base: int) -> None:
         """Range-partitioned corpus: indices reported by kNN become base + local index."""
         check(load().innr_batch_set_index_base(self._h, C.c_uint64(base)))
+        self._base = int(base)
 
     def prefix(self, prefix_dims: int) -> "VerticalBatch":
         """The batch restricted to its first min(prefix_dims, dimension) dimensions -- the batch-level form of
@@ -164,6 +196,7 @@ class VerticalBatch(_lib.BatchMemoryMixin):
         check(load().innr_batch_prefix_view(self._h, int(prefix_dims), C.byref(h)))
         v = VerticalBatch(h, self._n, min(int(prefix_dims), self._d), self._ctx)
         v._parent = self
+        v._base = self._base
         if not hasattr(self, "_views"):
             self._views = weakref.WeakSet()
         self._views.add(v)
@@ -539,6 +572,59 @@ def batch_range_search(queries, batch: VerticalBatch, thresholds, metric: int = 
         idx, sc = call(room)
     r = min(int(total.value), room)
     return off, idx[:r], sc[:r]
+
+
+def batch_knn_rows(indices, batch: VerticalBatch, k: int, metric: int = METRIC_L2SQ, exclude_self: bool = True,
+                   engine: int = KNN_AUTO, stats: Optional[KnnStats] = None):
+    """k-NN of vectors the batch already holds (innr_batch_knn_rows): query j is vector indices[j] (GLOBAL indices, duplicates and
+    any order allowed). exclude_self=False: what knn_multi gives for rows(indices). exclude_self=True: the best k' = min(k, N - 1) of
+    all vectors except indices[j] itself -- the index is excluded, vectors equal to it stay. Returns (indices uint64 [Q, k'], scores
+    float32 [Q, k']). A CUDA int64 index tensor takes the device entry point: the results stay there (int64 / float32 tensors)."""
+    n = batch.num_vectors()
+    st = stats if stats is not None else KnnStats()
+    out_k = C.c_size_t(0)
+    kk = max(min(int(k), n - 1 if exclude_self else n), 0)
+    if hasattr(indices, "is_cuda") and indices.is_cuda:
+        import torch
+        ids = indices.to(torch.int64).reshape(-1).contiguous()
+        nq = ids.numel()
+        batch._ctx.bind_torch_stream()  # the indices were produced on torch's stream, the results are consumed there
+        idx = torch.empty((max(nq * kk, 1),), dtype=torch.int64, device=ids.device)
+        sc = torch.empty((max(nq * kk, 1),), dtype=torch.float32, device=ids.device)
+        check(load().innr_batch_knn_rows_dev(batch._h, metric, C.c_void_p(ids.data_ptr()) if nq else None, nq, int(k),
+                                             int(bool(exclude_self)), engine, C.c_void_p(idx.data_ptr()), C.c_void_p(sc.data_ptr()),
+                                             C.byref(out_k), C.byref(st)))
+        r = int(out_k.value)
+        return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+    ids = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    nq = ids.size
+    idx = np.empty(max(nq * kk, 1), dtype=np.uint64)
+    sc = np.empty(max(nq * kk, 1), dtype=np.float32)
+    check(load().innr_batch_knn_rows(batch._h, metric, _vp(ids) if nq else None, nq, int(k), int(bool(exclude_self)), engine, _vp(idx),
+                                     _vp(sc), C.byref(out_k), C.byref(st)))
+    r = int(out_k.value)
+    return idx[:nq * r].reshape(nq, r), sc[:nq * r].reshape(nq, r)
+
+
+def batch_knn_graph(batch: VerticalBatch, k: int, metric: int = METRIC_L2SQ, engine: int = KNN_AUTO, first: int = 0,
+                    count: Optional[int] = None):
+    """The k-NN graph of the batch's vectors first .. first + count - 1 (local positions; count=None: to the end): row i holds the
+    k' = min(k, N - 1) nearest other vectors of vector first + i, as global indices. Filled by batch_knn_rows calls of at most
+    65536 consecutive ids each. Returns (indices uint64 [count, k'], scores float32 [count, k'])."""
+    n = batch.num_vectors()
+    first = int(first)
+    count = max(n - first, 0) if count is None else int(count)
+    if first < 0 or count < 0 or first + count > n:
+        raise IndexError(f"rows [{first}, {first + count}) are not inside a batch of {n} vectors")
+    kk = max(min(int(k), n - 1), 0)
+    idx = np.empty((count, kk), dtype=np.uint64)
+    sc = np.empty((count, kk), dtype=np.float32)
+    if kk:
+        for i0 in range(0, count, 65536):
+            m = min(65536, count - i0)
+            ids = np.arange(batch._base + first + i0, batch._base + first + i0 + m, dtype=np.uint64)
+            idx[i0:i0 + m], sc[i0:i0 + m] = batch_knn_rows(ids, batch, k, metric=metric, exclude_self=True, engine=engine)
+    return idx, sc
 
 
 def batch_knn_adaptive_multi(queries, batch: VerticalBatch, k: int, warmup_dims: int, stats: Optional[KnnStats] = None):

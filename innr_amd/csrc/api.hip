@@ -66,7 +66,8 @@ static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
             &c->redo[0].q, &c->redo[0].idx, &c->redo[0].sc, &c->redo[0].map, &c->redo[0].qn,
             &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
             &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan,
-            &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off, &c->adp_scan, &c->adp_list};
+            &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off, &c->adp_scan, &c->adp_list,
+            &c->rows_q, &c->rows_stage, &c->rows_io, &c->rows_flag};
 }
 
 // kernel_of(Inst) of the recorded families whose kernels this file owns (api_internal.h: Inst, launch_kernel)

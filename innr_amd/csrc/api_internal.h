@@ -1,7 +1,7 @@
 // api_internal.h -- what more than one translation unit of the library shares: the context and its workspace, the launch record
 // and dispatch, the corpus handles, the entry guard, and the host functions that cross a unit boundary. The units: api.hip (the C
-// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), comm.hip (the multi-GPU layer),
-// sort_full.hip.
+// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), rows.hip (search by stored vector),
+// comm.hip (the multi-GPU layer), sort_full.hip.
 // Nothing here may depend on INNR_TEST_HOOKS: every object but api.o is linked into the product library and the hook library
 // alike, so the struct layouts must be the same in every object.
 #pragma once
@@ -184,6 +184,10 @@ struct innr_ctx {
     DevBuf rs_off;
     DevBuf adp_scan;   // innr_batch_knn_adaptive: the AdaptiveState, then per-chunk counts and their scans [4][chunks of the corpus]
     DevBuf adp_list;   // ... the live list twice (indices, distances: a compaction writes the other copy) and its death dimensions
+    DevBuf rows_q;     // innr_batch_knn_rows (rows.hip): a round's gathered query rows [round][D]; shared with nothing, the inner search uses the buffers above
+    DevBuf rows_stage; // ... with exclude_self: the inner search's [round][k + 1] indices, then scores
+    DevBuf rows_io;    // ... and innr_batch_gather_rows, host-memory entry points: indices in, results out
+    DevBuf rows_flag;  // ... the gathers' own error word (an index outside the batch): every entry point clears c->flags
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]

@@ -114,6 +114,10 @@ pub mod ffi {
         pub fn innr_batch_range_search_dev(b: *mut InnrBatch, metric: c_int, d_queries: *const f32, q: usize, d: usize, d_thresholds: *const f32, engine: c_int, d_out_offsets: *mut u64, d_out_idx: *mut u64, d_out_score: *mut f32, cap: usize, out_total: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_knn_adaptive(b: *mut InnrBatch, queries: *const f32, q: usize, d: usize, k: usize, warmup_dims: usize, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_knn_adaptive_dev(b: *mut InnrBatch, d_queries: *const f32, q: usize, d: usize, k: usize, warmup_dims: usize, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_gather_rows(b: *mut InnrBatch, idx: *const u64, n: usize, out: *mut f32) -> c_int;
+        pub fn innr_batch_gather_rows_dev(b: *mut InnrBatch, d_idx: *const u64, n: usize, d_out: *mut f32) -> c_int;
+        pub fn innr_batch_knn_rows(b: *mut InnrBatch, metric: c_int, idx: *const u64, q: usize, k: usize, exclude_self: c_int, engine: c_int, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_knn_rows_dev(b: *mut InnrBatch, metric: c_int, d_idx: *const u64, q: usize, k: usize, exclude_self: c_int, engine: c_int, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_dot_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_cosine_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_l2sq_f32(a: *const f32, b: *const f32, n: usize) -> f32;
@@ -240,6 +244,7 @@ pub mod batch {
         num_vectors: usize,
         dimension: usize,
         host: std::sync::OnceLock<Vec<f32>>, // lazily downloaded data() copy
+        base: std::sync::atomic::AtomicU64,  // what set_index_base set: gather_rows / knn_rows take global indices
     }
     unsafe impl Send for VerticalBatch {}
     unsafe impl Sync for VerticalBatch {}
@@ -251,7 +256,7 @@ pub mod batch {
         fn upload_rows(flat: &[f32], n: usize, d: usize) -> Self {
             let mut h = std::ptr::null_mut();
             check(unsafe { ffi::innr_batch_upload_rowmajor(ctx(), flat.as_ptr(), n, d, &mut h) });
-            Self { h, num_vectors: n, dimension: d, host: Default::default() }
+            Self { h, num_vectors: n, dimension: d, host: Default::default(), base: Default::default() }
         }
         /// batch.rs:103-131
         pub fn from_rows(vectors: &[Vec<f32>]) -> Self {
@@ -290,18 +295,52 @@ pub mod batch {
                 v
             })
         }
-        pub fn get(&self, dim: usize, vec_idx: usize) -> f32 { self.data()[dim * self.num_vectors + vec_idx] }
+        /// batch.rs:187: from the host copy when data() has made one, otherwise a one-row gather (never a download of the corpus)
+        pub fn get(&self, dim: usize, vec_idx: usize) -> f32 {
+            match self.host.get() {
+                Some(v) => v[dim * self.num_vectors + vec_idx],
+                None => self.extract_vector(vec_idx)[dim],
+            }
+        }
         pub fn dimension_slice(&self, dim: usize) -> &[f32] {
             let s = dim * self.num_vectors;
             &self.data()[s..s + self.num_vectors]
         }
+        /// batch.rs:217, through innr_batch_gather_rows: the one row moves, not the corpus
         pub fn extract_vector(&self, vec_idx: usize) -> Vec<f32> {
-            (0..self.dimension).map(|d| self.get(d, vec_idx)).collect()
+            assert!(vec_idx < self.num_vectors, "index out of bounds: the len is {} but the index is {}", self.num_vectors, vec_idx);
+            if let Some(v) = self.host.get() {
+                return (0..self.dimension).map(|d| v[d * self.num_vectors + vec_idx]).collect();
+            }
+            self.gather_rows(&[self.index_base() + vec_idx as u64])
         }
+        /// Vectors by GLOBAL index (index base + local index; duplicates and any order allowed), row-major `[indices.len() * dimension]`
+        pub fn gather_rows(&self, indices: &[u64]) -> Vec<f32> {
+            let mut out = vec![0.0f32; indices.len() * self.dimension];
+            check(unsafe { ffi::innr_batch_gather_rows(self.h, indices.as_ptr(), indices.len(), out.as_mut_ptr()) });
+            out
+        }
+        /// k-NN of vectors the batch holds (innr_batch_knn_rows): query j = vector `indices[j]` (global). `exclude_self`: the best
+        /// min(k, N - 1) of all vectors except `indices[j]` itself; otherwise what `batch_knn_multi` gives for the gathered rows.
+        pub fn knn_rows(&self, metric: i32, indices: &[u64], k: usize, exclude_self: bool) -> Vec<BatchKnnResult> {
+            let q = indices.len();
+            let kk = k.min(if exclude_self { self.num_vectors.saturating_sub(1) } else { self.num_vectors });
+            let (mut idx, mut sc, mut out_k) = (vec![0u64; q * kk.max(1)], vec![0f32; q * kk.max(1)], 0usize);
+            check(unsafe { ffi::innr_batch_knn_rows(self.h, metric, indices.as_ptr(), q, k, exclude_self as i32, ffi::INNR_KNN_AUTO,
+                                                    idx.as_mut_ptr(), sc.as_mut_ptr(), &mut out_k, std::ptr::null_mut()) });
+            (0..q).map(|j| BatchKnnResult {
+                indices: idx[j * out_k..(j + 1) * out_k].iter().map(|&i| i as usize).collect(),
+                scores: sc[j * out_k..(j + 1) * out_k].to_vec(),
+            }).collect()
+        }
+        fn index_base(&self) -> u64 { self.base.load(std::sync::atomic::Ordering::Relaxed) }
         pub(crate) fn handle(&self) -> *mut ffi::InnrBatch { self.h }
         /// range-partitioned corpus (sharded::Comm): this batch holds rows [base, base + num_vectors) of the global
         /// corpus; every index it reports is `base + local index`
-        pub fn set_index_base(&self, base: u64) { check(unsafe { ffi::innr_batch_set_index_base(self.h, base) }) }
+        pub fn set_index_base(&self, base: u64) {
+            check(unsafe { ffi::innr_batch_set_index_base(self.h, base) });
+            self.base.store(base, std::sync::atomic::Ordering::Relaxed);
+        }
         /// device bytes of this batch (innr_batch_memory)
         #[must_use] pub fn memory(&self) -> crate::memory::BatchMemory { crate::memory::batch_memory(self.h) }
         /// bytes of the derived kinds in `mask` (`memory::COPY_*`)
@@ -368,7 +407,8 @@ pub mod batch {
         pub fn prefix(&self, prefix_dims: usize) -> PrefixBatch<'_> {
             let mut h = std::ptr::null_mut();
             check(unsafe { ffi::innr_batch_prefix_view(self.handle(), prefix_dims, &mut h) });
-            PrefixBatch { inner: VerticalBatch { h, num_vectors: self.num_vectors, dimension: prefix_dims.min(self.dimension), host: Default::default() },
+            PrefixBatch { inner: VerticalBatch { h, num_vectors: self.num_vectors, dimension: prefix_dims.min(self.dimension), host: Default::default(),
+                                                   base: std::sync::atomic::AtomicU64::new(self.index_base()) },
                           _parent: std::marker::PhantomData }
         }
     }
