@@ -1883,6 +1883,48 @@ extern "C" void innrdbg_scan_log_reset(innr_ctx* c) {
     c->scan_total = 0;
 }
 
+// Test hook: sort_full.hip's full_topk_keys on caller-given composites -- the radix select, the gather and the bitonic network with
+// nothing in front of them. host_keys[0..n) -> host_sorted[0..min(k, n)), best (largest) first. Buffers as knn_full_sort lays them
+// out: c->sort_keys = [n keys][full_topk_out_capacity(min(k, n)) sorted], c->sort_tmp = the selection state.
+innr_status innrdbg_full_topk_keys(innr_ctx* c, const uint64_t* host_keys, size_t n, size_t k, uint64_t* host_sorted) {
+    if (!c || !host_keys || !host_sorted) return INNR_E_BAD_ARG;
+    INNR_ENTER(c);
+    const size_t kout = std::min(k, n);
+    if (kout == 0) return INNR_OK;
+    size_t tmp_bytes = 0;
+    INNR_HIP_CHECK(full_sort_scratch_bytes(n, &tmp_bytes));
+    INNR_TRY(c->sort_keys.ensure((n + full_topk_out_capacity(kout)) * sizeof(uint64_t)));
+    INNR_TRY(c->sort_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    uint64_t* keys = c->sort_keys.as<uint64_t>();
+    INNR_HIP_CHECK(hipMemcpyAsync(keys, host_keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    INNR_HIP_CHECK(full_topk_keys(keys, n, kout, keys + n, c->sort_tmp.p, c->stream));
+    INNR_HIP_CHECK(hipMemcpyAsync(host_sorted, keys + n, kout * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    INNR_HIP_CHECK(ctx_sync(c));
+    return INNR_OK;
+}
+
+// Test hook: segmented_topk_keys on caller-given composites, host_keys[nseg][len] -> host_sorted[nseg][min(k, len)], every segment
+// best first. Buffers as innr_batch_rerank_dev lays them out: c->sort_keys = [nseg * len keys][nseg * len sorted][tmp of
+// full_topk_out_capacity(min(k, len))].
+innr_status innrdbg_segmented_topk_keys(innr_ctx* c, const uint64_t* host_keys, size_t nseg, size_t len, size_t k,
+                                        uint64_t* host_sorted) {
+    if (!c || !host_keys || !host_sorted) return INNR_E_BAD_ARG;
+    INNR_ENTER(c);
+    const size_t kout = std::min(k, len);
+    if (kout == 0 || nseg == 0) return INNR_OK;
+    size_t tmp_bytes = 0;
+    INNR_HIP_CHECK(segmented_sort_scratch_bytes(nseg, len, &tmp_bytes));
+    INNR_TRY(c->sort_keys.ensure((2 * nseg * len + full_topk_out_capacity(kout)) * sizeof(uint64_t)));
+    INNR_TRY(c->sort_tmp.ensure(std::max<size_t>(tmp_bytes, 16)));
+    uint64_t* keys = c->sort_keys.as<uint64_t>();
+    INNR_HIP_CHECK(hipMemcpyAsync(keys, host_keys, nseg * len * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    INNR_HIP_CHECK(segmented_topk_keys(keys, keys + nseg * len, nseg, len, kout, keys + 2 * nseg * len, c->sort_tmp.p, c->stream));
+    INNR_HIP_CHECK(hipMemcpy2DAsync(host_sorted, kout * sizeof(uint64_t), keys + nseg * len, len * sizeof(uint64_t),
+                                    kout * sizeof(uint64_t), nseg, hipMemcpyDeviceToHost, c->stream));
+    INNR_HIP_CHECK(ctx_sync(c));
+    return INNR_OK;
+}
+
 #endif  // INNR_TEST_HOOKS
 
 // Second stage of the two-stage pipeline the reference describes (scalar.rs:366-368: batch_knn_u8 first pass, then an

@@ -349,6 +349,7 @@ innr_status exclusive_scan_u32(innr_ctx* c, const uint32_t* counts, uint32_t n, 
 // sort_full.hip
 hipError_t full_sort_scratch_bytes(size_t n, size_t* bytes);
 size_t full_topk_out_capacity(size_t k);  // keys the `sorted` buffer must hold for the best k (the next power of two)
+hipError_t full_topk_keys(const uint64_t* keys, size_t n, size_t k, uint64_t* sorted, void* scratch, hipStream_t stream);
 hipError_t full_sort_scores(const float* scores, size_t n, bool smaller_is_better, uint64_t* keys, uint64_t* sorted,
                             void* scratch, size_t scratch_bytes, hipStream_t stream, const uint8_t* mask, size_t k);
 hipError_t segmented_sort_scratch_bytes(size_t nseg, size_t len, size_t* bytes);
