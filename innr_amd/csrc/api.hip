@@ -43,7 +43,7 @@ static const TuneName kTuneNames[] = {
     {"i8_slices_per_cu", &innr_tuning::i8_slices_per_cu}, {"i8_no_small", &innr_tuning::i8_no_small},
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
-    {"split_min_q", &innr_tuning::split_min_q}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
+    {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
     {"copy_budget_mib", &innr_tuning::copy_budget_mib}, {"scan_max_slots", &innr_tuning::scan_max_slots},
 };
 static void tuning_from_env(innr_tuning* t) {
@@ -74,6 +74,8 @@ static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
 template <int KIND, int RR, int MODE, int WV> constexpr auto kernel_of(Inst<kLaunchGemmF32, KIND, RR, MODE, WV>) { return &gemm_filter_kernel<KIND, RR, MODE, WV>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmBf16, RR, MODE, 1>) { return &gemm_bf16_filter_kernel<RR, MODE, 1>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmSplit, RR, MODE, 3>) { return &gemm_bf16_filter_kernel<RR, MODE, 3>; }
+// ... the same record's screened form (MODE 0: hi.hi K-loop, lo products where a wave can hit; launch_gemm_split chooses)
+template <int RR> constexpr auto screened_kernel_of(Inst<kLaunchGemmSplit, RR, 0, 3>) { return &gemm_bf16_filter_kernel<RR, 0, 3, 1>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8One, RR, MODE>) { return &gemm_i8h_filter_kernel<RR, MODE>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Two, RR, MODE>) { return &gemm_i8_filter_kernel<RR, MODE>; }
 template <int NK, int CT, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Small, NK, CT, MODE>) { return &gemm_i8s_filter_kernel<12, NK, CT, MODE>; }
@@ -476,17 +478,19 @@ static innr_status close_padding_queries(innr_ctx* c, uint32_t* gthr, size_t nre
 
 // Chip-wide threshold state of one GEMM-type launch (topk_dev.h): [Qpad][kSlotMul * KP] slots and [Qpad] bounds, zeroed for every
 // launch (the bounds then seeded / closed for padding queries), followed by [Qpad] floats: the k rule's margin 2E per query
-// (kmargin == null or kk == 0: +inf, the rule is off).
+// (kmargin == null or kk == 0: +inf, the rule is off), and [Qpad] more floats that only the screened split filter reads: its screen
+// margin per query (smargin).
 static innr_status prep_gthr(innr_ctx* c, size_t Qpad, uint32_t KP, const uint32_t* seed, size_t nreal_q, const float* kmargin,
-                             uint32_t** gslots, size_t* nslot_out) {
+                             uint32_t** gslots, size_t* nslot_out, const float* smargin = nullptr) {
     const size_t nslot = Qpad * (size_t)kSlotMul * KP;
-    INNR_TRY(c->gthr.ensure((nslot + 2 * Qpad) * sizeof(uint32_t)));
+    INNR_TRY(c->gthr.ensure((nslot + 3 * Qpad) * sizeof(uint32_t)));
     INNR_HIP_CHECK(hipMemsetAsync(c->gthr.p, 0, (nslot + Qpad) * sizeof(uint32_t), c->stream));
     uint32_t* gs = c->gthr.as<uint32_t>();
     if (seed) INNR_HIP_CHECK(hipMemcpyAsync(gs + nslot, seed, Qpad * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     INNR_TRY(close_padding_queries(c, gs + nslot, nreal_q, Qpad));
     if (kmargin) INNR_HIP_CHECK(hipMemcpyAsync(gs + nslot + Qpad, kmargin, Qpad * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     else INNR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(gs + nslot + Qpad), 0x7f800000, Qpad, c->stream));
+    if (smargin) INNR_HIP_CHECK(hipMemcpyAsync(gs + nslot + 2 * Qpad, smargin, Qpad * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     *gslots = gs;
     *nslot_out = nslot;
     return INNR_OK;
@@ -1136,6 +1140,54 @@ static float split_filter_scale(const innr_batch* b, int metric) {
            (metric == INNR_METRIC_COSINE ? 1.0f : b->max_norm);
 }
 
+// The screened split filter's margin: its K-loop accumulates s_hh = qh.vh alone and rejects a 32 x 32 sub-tile
+// without the two small products when max s_hh < thr - m. What the reject has to cover is the score the correction would have
+// produced from the same accumulator, s = fl(s_hh + qh.vl + ql.vh), the small products added behind all of hi.hi:
+//   * bf16 keeps 8 significant bits: |x - h| <= 2^-8 |x| for h = rne_bf16(x) (half a last place; reached just above a power of
+//     two), so |l| <= (1 + 2^-8) 2^-8 |x| for l = rne_bf16(x - h) and |h| <= (1 + 2^-8) |x|. Per dimension
+//     |qh vl + ql vh| <= 2 (1 + 2^-8)^2 2^-8 |q_d v_d| <= 2^-7 1.004 |q_d v_d|, and Cauchy-Schwarz over the row:
+//     |qh.vl + ql.vh| <= 2^-7 1.004 |q| max|v|. (Half of that, 2^-8 1.004, holds for most data but not for all: values whose lo
+//     limbs sit at half a last place with aligned signs exceed it -- tests/test_gpu_split_screen.py measures 1.07 x 2^-8.)
+//   * the f32 accumulation of the 2D small products on top of s_hh: within the (6D + 8) u 1.04 |q| max|v| that split_filter_scale
+//     allows for all 3D products in any order (the same assumption, the same magnitudes).
+//   * flushed limbs or products at the bottom of the range: the allowance of split_filter_scale, at most
+//     2^-126 (sqrt(D) (|q| + max|v|) + 6D), added per query by screen_margin_kernel.
+// So s <= s_hh + m with m = 1.05 (2^-7 1.004 + (6D + 8) u 1.04) |q| max|v| (cosine: 1 for |q^||v^|, the (1 + D u)^2 inside the 1.05):
+// a sub-tile below thr - m holds nothing that the full loop would have kept, and is rejected exactly as its full scores would be.
+// The scores of corrected sub-tiles accumulate in another order than the full loop's; E covers any order.
+static float split_screen_scale(const innr_batch* b, int metric) {
+    return 1.05f * (0.0078125f * 1.004f + (6.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.04f) *
+           (metric == INNR_METRIC_COSINE ? 1.0f : b->max_norm);
+}
+// m per query: scale * |q_j| (dot) or scale (cosine: |q^| = 1) + the flush allowance 2^-126 (flush_c + flush_v |q_j|), rounded up;
+// +inf (no screening: every sub-tile is corrected) where that is not a finite non-negative number. Padding queries are closed
+// (close_padding_queries): their margin plays no part.
+__global__ void screen_margin_kernel(int cosine, float scale, float flush_v, float flush_c, const float* __restrict__ qnorm, uint32_t Q,
+                                     uint32_t Qpad, float* __restrict__ out) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= Qpad) return;
+    float m = 0.0f;
+    if (j < Q) {
+        const float qn = cosine ? 1.0f : qnorm[j];
+        const float x = (scale * (cosine ? 1.0f : qn) + 1.17549435e-38f * (flush_c + flush_v * qn)) * 1.0002f;
+        m = (x - x == 0.0f && x >= 0.0f) ? x : __builtin_inff();
+    }
+    out[j] = m;
+}
+// c->kmargin [Qpad .. 2 Qpad): behind the k rule's margins (make_kmargin sizes the buffer for both when asked first)
+static innr_status make_screen_margin(innr_batch* b, int metric, size_t Q, size_t Qpad, const float** out) {
+    innr_ctx* c = b->ctx;
+    const bool cos = metric == INNR_METRIC_COSINE;
+    const float sd = sqrtf((float)b->D), vmax = cos ? 1.0f : b->max_norm;
+    float* m = c->kmargin.as<float>() + Qpad;
+    screen_margin_kernel<<<(unsigned)((Qpad + 255) / 256), 256, 0, c->stream>>>(cos ? 1 : 0, split_screen_scale(b, metric), sd,
+                                                                               sd * vmax + 6.0f * (float)b->D, c->q_norm.as<float>(),
+                                                                               (uint32_t)Q, (uint32_t)Qpad, m);
+    INNR_HIP_CHECK(hipGetLastError());
+    *out = m;
+    return INNR_OK;
+}
+
 // One collect pass of the f32 GEMM filter (MODE 2) over nr queries Qr (row-major [nr][D]) with the FIXED per-query thresholds
 // x[j] - E (x: exact scores -- distances for squared L2 -- on the device): every site whose approximate score clears its query's
 // threshold goes to c->lists [Qpad][kCollectCap] (indices), c->counts [Qpad] (lengths; an overfull list keeps counting). Leaves the
@@ -1238,6 +1290,11 @@ enum LastFilter { kFilterNone = 0, kFilterF32 = 1, kFilterBf16 = 2, kFilterSplit
 // (tools/split_ab.py, profiles/r04_split_ab.txt): 64 queries 13.9 ms split vs 9.2 f32 (one-wave tile), 128 queries 14.5 vs 15.7
 // (two-wave tile), 256 queries 15.5 vs 28.8.
 constexpr size_t kSplitMinQ = 65;
+// Largest share of a call's wave tiles the screened form may correct before the batch's later calls take the full loop: between
+// the measured winners and losers at C2 (profiles/r05_split_ab.txt): 18 % corrected (k = 10) 21.2 against 34.5 ms at 1024 queries,
+// 31 % (k = 100, 65 queries) 12.0 against 13.9; 58 % (k = 100, 128 ... 4096 queries) 14.8 ... 151.1 against 14.6 ... 137.4, LCG data
+// 98 % and 182.0 against 145.3 ms for first pass + completion. A line through the first and the last crosses near 45 %.
+constexpr float kScreenMaxShare = 0.45f;
 
 // the lo limbs of the dot / cosine kind (the cosine kind needs b->invn); soft: under the memory rule, else as a filter copy
 static innr_status ensure_bf16_lo(innr_batch* b, int metric, bool soft) {
@@ -1295,17 +1352,29 @@ static innr_status pack_queries_split(innr_batch* b, const GemmPlan& p, const fl
 
 template <int MODE>
 static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nreal_q, int metric, const uint32_t* seed,
-                                     const float* kmargin = nullptr, uint32_t kk = 0, float* dump = nullptr, size_t ld_dump = 0) {
+                                     const float* kmargin = nullptr, uint32_t kk = 0, float* dump = nullptr, size_t ld_dump = 0,
+                                     const float* smargin = nullptr) {
     innr_ctx* c = b->ctx;
     const CorpusCopy &hi = b->copy[bf16_kind(metric)], &lo = b->copy[bf16_kind(metric, true)];
     uint32_t* gslots = nullptr;
     size_t nslot = 0;
     if (!kmargin) kk = 0;
-    INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot));
+    if (hi.nk % kBfLead != 0) {  // bf16_nk: the K-loop's ring position and the correction's two K-steps per batch rely on it
+        set_error("internal: the bf16 copy has an odd number of K-steps (%u)", hi.nk);
+        return INNR_E_BAD_ARG;
+    }
+    INNR_TRY(prep_gthr(c, p.Qpad, p.KP, seed, nreal_q, kmargin, &gslots, &nslot, smargin));
+    // smargin: the screened form (hi.hi K-loop, lo products where a wave can hit) -- one record for both forms
+    const bool screened = MODE == 0 && smargin != nullptr;
     const auto launch = [&](auto rr) {
-        launch_kernel(c, Inst<kLaunchGemmSplit, rr, MODE, 3>(), {p.nblocks, 64 * kBfWaves, 0, p.nqt}, hi.p, lo.p, c->q_bf16.as<char>(),
-                      (uint32_t)(b->ldN / 128), (uint32_t)b->N, hi.nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(),
-                      c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump);
+        const Inst<kLaunchGemmSplit, rr, MODE, 3> inst;
+        auto kernel = kernel_of(inst);
+        if constexpr (MODE == 0) {
+            if (screened) kernel = screened_kernel_of(inst);
+        }
+        launch_kernel_as(c, inst, kernel, {p.nblocks, 64 * kBfWaves, 0, p.nqt}, hi.p, lo.p, c->q_bf16.as<char>(),
+                         (uint32_t)(b->ldN / 128), (uint32_t)b->N, hi.nk, p.Qpad, p.nqt, p.qtg, p.tps, c->lists.as<uint64_t>(),
+                         c->counts.as<uint32_t>(), p.KP, kk, c->flags.as<uint32_t>(), gslots, gslots + nslot, dump, ld_dump);
     };
     if constexpr (MODE == 1) launch(IntC<6>());  // the dense-score dump: the list geometry plays no part
     else dispatch(launch, rr_gemm(p.cap));       // (every instantiation has a row in tests/test_gpu_kernel_variants.py: GEMM_SPLIT)
@@ -1429,11 +1498,31 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
 
     // the k rule of topk_dev.h: 2E per query, in the score space of the kind
     const float* kmargin = nullptr;
+    // the screened form of the split filter (hi.hi K-loop, lo products where a wave can hit), measured at C2 against the full loop
+    // (tools/split_ab.py, profiles/r05_split_ab.txt): lists of 32 win at every size, 65 ... 4096 queries 6.8 ... 77.6 ms against
+    // 13.5 ... 134.9 (18 % of the wave tiles corrected), cosine at 4096 73.1 against 135.0; lists of 128 (k = 100) at 65 / 128 / 256 /
+    // 1024 / 4096 queries 12.0 / 14.8 / 17.4 / 37.9 / 151.1 against 13.9 / 14.6 / 15.8 / 35.1 / 137.4 -- long lists keep lower
+    // thresholds (58 % corrected from 128 queries on, 31 % at 65) and R = 12 / 20 reload spilled registers per tile: those keep
+    // the full loop beyond 128 queries, and at 128 the share rule below sends the batch's later calls there
+    // Data decides as well: where the thresholds sit among near-ties (the reference example's LCG rows) nearly every sub-tile is
+    // corrected and a corrected tile costs more than the full loop's (182.7 against 146.3 ms at 1024 queries). The kernel counts
+    // the wave tiles it corrects (flag words kScreenCountWord); the first pass reads them with its proof flags and the batch
+    // remembers the share per list class. Above kScreenMaxShare later calls take the full loop and every 64th screens again
+    // (the data or the batch size may have changed). no_split_screen: 1 never screens, -1 always does.
+    const int scls = p.KP <= 64 ? 0 : 1;
+    bool screen = use_split && c->tune.no_split_screen <= 0;
+    if (screen && c->tune.no_split_screen == 0) {
+        screen = p.KP <= 64 || Q <= 128;
+        if (screen && level == 0 && b->screen_share[scls] > kScreenMaxShare && (++b->screen_skips[scls] % 64u) != 0) screen = false;
+    }
+    if (screen) INNR_TRY(c->kmargin.ensure(2 * p.Qpad * sizeof(float)));  // (before make_kmargin: growing the buffer drops its contents)
     INNR_TRY(make_kmargin(c, metric_space(metric), err_scale, c->q_norm.as<float>(), Cj, nullptr, 0.0f, nullptr, Q, p.Qpad, &kmargin));
+    const float* smargin = nullptr;
+    if (screen) INNR_TRY(make_screen_margin(b, metric, Q, p.Qpad, &smargin));
     const uint32_t kk = (uint32_t)kout;
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     if (use_bf16) INNR_TRY(launch_gemm_bf16(b, p, Q, seed, bfv, kmargin, kk));
-    else if (use_split) INNR_TRY(launch_gemm_split<0>(b, p, Q, metric, seed, kmargin, kk));
+    else if (use_split) INNR_TRY(launch_gemm_split<0>(b, p, Q, metric, seed, kmargin, kk, nullptr, 0, smargin));
     else if (cos) INNR_TRY((launch_gemm<kGemmCos, 0>(b, p, Q, c->q_kmajor.as<float>(), b->invn, invq, nullptr, 0, seed, kmargin, kk)));
     else if (l2) INNR_TRY((launch_gemm<kGemmL2, 0>(b, p, Q, c->q_kmajor.as<float>(), b->sqn, invq, nullptr, 0, seed, kmargin, kk)));
     // (A first pass of the same kernel over 1/16 of the corpus, only to harvest tighter bounds for the full pass, was
@@ -1458,8 +1547,12 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
         if (q >= qn_host.size()) return false;
         return use_bf16 ? !(qn_host[q] * b->max_norm >= 1e-25f) : !(qn_host[q] == 0.0f || (qn_host[q] >= 1e-12f && qn_host[q] <= 1e18f));
     };
+    uint32_t screened[2] = {0u, 0u};  // corrected wave tiles / sub-tiles of this first pass (delivered by the harvest's synchronise)
+    if (screen && level == 0) INNR_HIP_CHECK(copy_out(c, screened, c->flags.as<uint32_t>() + kScreenCountWord, sizeof(screened)));
     std::vector<uint32_t> redo;  // margin proof failed (near-tie at the cut, or non-finite scores)
     INNR_TRY(harvest_proof(c, fallback, Q, p.KP, &redo, nfallback, kept, gemm_ms, unprovable));
+    if (screen && level == 0)  // of the wave tiles that hold a real query (padding queries are closed and never corrected)
+        b->screen_share[scls] = (float)screened[0] / (float)((b->ldN / 128) * ((Q + 63) / 64));
     // f32 engine: ONE completion pass resolves what the first pass could not prove (knn_complete); a handful of queries is
     // cheaper on the exact engine (one 8-query corpus pass costs less than a GEMM pass over a 256-query tile)
     bool completed = false;
@@ -1840,6 +1933,16 @@ innr_status innrdbg_split_scores(innr_batch* b, int metric, const float* queries
 // Test hook: the filter kernel of the last INNR_KNN_MFMA / _BF16 first pass on this batch's context: 0 none yet, 1 the f32 kernel
 // (gemm_filter_kernel), 2 the bf16 filter, 3 the split-bf16 filter (LastFilter).
 int innrdbg_last_filter(const innr_batch* b) { return b && b->ctx ? b->ctx->last_filter : -1; }
+
+// Test hook: what the screened split filter corrected in the launches since the call's entry cleared the flag words: counts[0] =
+// wave tiles (128 rows x 64 queries) with at least one flagged sub-tile, counts[1] = their flagged 32 x 32 sub-tiles.
+innr_status innrdbg_split_screen_counts(innr_batch* b, uint32_t* counts) {
+    if (!b || !counts) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(hipMemcpy(counts, c->flags.as<uint32_t>() + kScreenCountWord, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return INNR_OK;
+}
 
 // Test hook: how many selections innr_batch_knn_filtered_multi has built for this batch (its cache misses)
 uint32_t innrdbg_filter_selection_builds(const innr_batch* b) { return b ? b->fsel_builds : 0u; }

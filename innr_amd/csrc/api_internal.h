@@ -71,6 +71,7 @@ struct innr_tuning {
     long i8_small_free = 0;      // ... its query groups run free (no soft lockstep): A/B
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
+    long no_split_screen = 0;    // ... 1: its full three-product K-loop, never the hi.hi loop with screened corrections; -1: always the screened loop; 0: by list length, batch size and the share of wave tiles the batch's last screened call corrected (A/B, tests)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
     long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip
@@ -228,6 +229,12 @@ static void launch_kernel(innr_ctx* c, Inst<FAMILY, ARGS...> inst, const LaunchD
     c->launch_log[c->launch_total++ % kLaunchLogCap] = LaunchRec{(uint8_t)FAMILY, (uint8_t)d.lockstep, {ARGS...}, d.groups};
     kernel_of(inst)<<<d.grid, d.block, d.lds, c->stream>>>(args...);
 }
+// ... where one record stands for two forms of a kernel with the same arguments: `kernel` is the form the dispatch site chose
+template <int FAMILY, int... ARGS, class Kernel, class... KernelArgs>
+static void launch_kernel_as(innr_ctx* c, Inst<FAMILY, ARGS...>, Kernel kernel, const LaunchDims& d, KernelArgs... args) {
+    c->launch_log[c->launch_total++ % kLaunchLogCap] = LaunchRec{(uint8_t)FAMILY, (uint8_t)d.lockstep, {ARGS...}, d.groups};
+    kernel<<<d.grid, d.block, d.lds, c->stream>>>(args...);
+}
 
 // A run-time value that selects one of the constants Vs; any other value selects the LAST of them (a switch's `default:`).
 // dispatch(f, one_of<..>(a), one_of<..>(b), ...) calls f(IntC<A>(), IntC<B>(), ...) with the selected constants and returns what it
@@ -299,6 +306,8 @@ struct innr_batch {
     uint32_t i8l2_R = 0;
     float i8l2_nmax = 0.0f;
     uint32_t i8_weak_skips = 0;              // AUTO calls that skipped the int8 filter since (every 64th tries it again)
+    float screen_share[2] = {0.0f, 0.0f};    // split filter: share of wave tiles the last screened first pass corrected, lists <= 64 / longer (knn_mfma)
+    uint32_t screen_skips[2] = {0, 0};       // ... calls that took the full loop since (every 64th screens again)
     uint32_t auto_small_calls = 0;           // AUTO calls with fewer than four queries while no int8 copy existed: the fourth builds it
     // innr_batch_knn_filtered_multi (kernels_select.h): the selection of the last mask -- its passing vectors compacted into a batch
     // of their own (npass * Dpad * 4 bytes, plus the filter copies the engines build on it), the normalised mask it was built from

@@ -51,6 +51,7 @@ __device__ __forceinline__ uint16_t bf16_limb(float x, int l) {
     return h;
 }
 constexpr uint32_t kBfL2Extra = 6;  // the squared-L2 copy's additional K columns
+constexpr uint32_t kScreenCountWord = 32;  // errflag words [32, 34): wave tiles the screened split filter corrected, and their sub-tiles
 
 // one thread per 16-byte output unit (8 dimensions of one corpus row)
 // limb: 0 = the rounded values (the hi limb: kCopyBfDot / -Cos / -L2), 1 = their lo limbs (kCopyBfDotLo / -CosLo, the split filter; not with sqn)
@@ -141,10 +142,26 @@ struct alignas(16) GemmBf16Lds {
     uint32_t thr[64 * kBfWaves];
 };
 
+// The screen's threshold of one query as raw float bits: the sub-tile's best hi.hi score, compared as a signed int, must reach it
+// for the sub-tile to be corrected. key: the query's threshold as an order key, m: its screen margin (>= 0, +inf: no screening).
+// thr - m is rounded to nearest and then taken one place down, so the result is never above the real difference.
+__device__ __forceinline__ int32_t screen_raw(uint32_t key, float m) {
+    if (!(key & 0x80000000u)) return INT32_MIN;  // no usable non-negative bound: everything is corrected
+    const uint32_t bits = key & 0x7fffffffu;
+    if (bits > 0x7f800000u) return INT32_MAX;    // a closed query (padding: the largest key): nothing reaches it
+    const float t = __uint_as_float(bits) - m;
+    if (!(t > 0.0f)) return INT32_MIN;           // (also inf - inf)
+    return (int32_t)__float_as_uint(t) - 1;
+}
+
 // MODE 0: fused top-k filter. MODE 1: dump the dense score matrix (layout test).
 // LIMBS 1: the bf16 filter (Abx unused). LIMBS 3: the split filter -- Abx the corpus' lo-limb copy, Bb holds nk K-steps of query hi
 // limbs followed by nk K-steps of lo limbs.
-template <int R, int MODE, int LIMBS>
+// SCREEN (LIMBS 3, MODE 0 only): the K-loop is the LIMBS = 1 loop -- hi.hi alone, the lo copies untouched. At the
+// end of a tile every 32 x 32 sub-tile whose best hi.hi score stays more than the queries' screen margin (gthr + 2 Qpad: a bound of
+// |qh.vl + ql.vh| and of their accumulation) below the threshold is rejected as its full score would have been; to the others the
+// wave alone adds the two small products from global memory, and the shared epilogue runs on the full split scores.
+template <int R, int MODE, int LIMBS, int SCREEN = 0>
 __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     const char* __restrict__ Ab, const char* __restrict__ Abx, const char* __restrict__ Bb, uint32_t ntiles, uint32_t N, uint32_t nk, size_t Qpad, uint32_t nqt,
     uint32_t qtg, uint32_t tiles_per_slice, uint64_t* __restrict__ lists, uint32_t* __restrict__ counts, uint32_t KP, uint32_t kk,
@@ -156,13 +173,16 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     const float scale = 1.0f;
     const float iq_lane[2] = {1.0f, 1.0f};
     constexpr int kBQ = 64 * kBfWaves;
-    using G = BfGeom<LIMBS>;
-    constexpr bool kSplit = LIMBS == 3;
+    constexpr bool kScreen = SCREEN != 0;
+    static_assert(!kScreen || (LIMBS == 3 && MODE == 0), "the screen belongs to the split filter's top-k mode");
+    constexpr int kLoop = kScreen ? 1 : LIMBS;  // limbs the K-loop multiplies
+    using G = BfGeom<kLoop>;
+    constexpr bool kSplit = kLoop == 3;
     // gemm_epilogue.inc: nothing this wave still prefetches is waited for. Split filter: the oldest op still needed at the epilogue
     // (end of step s+1) is the DMA of step s+2, issued at the top of step s-4: six whole steps of ops from it on.
     constexpr int kEpiTgWait = kSplit ? G::kPerStep * (kBfStages - 2) : 5 * (kBfStages - 3) + 4 + 5;
     static_assert(kEpiTgWait <= 63 && G::kPerStep * (kBfStages - 4) + G::kPerStep - G::kDma <= 63, "vmcnt is 6 bits");
-    __shared__ GemmBf16Lds<LIMBS> s;
+    __shared__ GemmBf16Lds<kLoop> s;
     constexpr uint32_t cap = 64 * R;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wu = __builtin_amdgcn_readfirstlane(w);
@@ -180,6 +200,11 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     s.cnt[threadIdx.x] = 0;
     s.thr[threadIdx.x] = 0;
     uint64_t* my_lists = lists + ((size_t)slice * Qpad + q0) * cap;
+    float smarg[2] = {0.0f, 0.0f};  // screen margin of this lane's two queries: they never change
+    if (kScreen) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) smarg[ct] = reinterpret_cast<const float*>(gthr + 2 * Qpad)[q0 + 64 * w + 2 * (lane & 31) + ct];
+    }
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -235,6 +260,7 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     for (int r = 0; r < kBfLead; ++r)
 #pragma unroll
         for (int x = 0; x < 2 * kB; x += 2) use_after<0>(breg[r][x], breg[r][x + 1]);
+    if (kScreen) asm volatile("" : "+v"(smarg[0]), "+v"(smarg[1]));  // landed here: no compiler-made wait for them inside the loop
     __syncthreads();
 
     uint32_t tg_next[2] = {0u, 0u};
@@ -296,7 +322,94 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
 #else
             if (r == kBfLead - 1 && ks + 1 == nk) {
 #endif
+                bool run_epilogue = true;
+                if constexpr (kScreen) {
+                    // ---- screen: which of the wave's eight 32 x 32 sub-tiles (rt, ct) can still reach their queries' thresholds ----
+                    // thr as the epilogue derives it (its own wait, kEpiTgWait of the LIMBS = 1 sequence; a bound read early
+                    // is the older, lower one: thresholds only rise, so the epilogue's is never below the screen's)
+                    use_after<kEpiTgWait>(tg_next[0], tg_next[1]);
+                    int32_t traw[2];
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        const uint32_t tl = __hip_atomic_load(&s.thr[64 * w + 2 * (lane & 31) + ct], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        traw[ct] = screen_raw(tl > tg_next[ct] ? tl : tg_next[ct], smarg[ct]);
+                    }
+                    uint32_t smask = 0;  // bit 2 rt + ct, wave-uniform
+#pragma unroll
+                    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct) {
+                            int32_t best = INT32_MIN;  // raw-bit maximum, as the epilogue's fast reject
+#pragma unroll
+                            for (int g = 0; g < 16; ++g) {
+                                const int32_t raw = (int32_t)__float_as_uint(acc[rt][ct][g]);
+                                best = best > raw ? best : raw;
+                            }
+                            if (__any(best >= traw[ct])) smask |= 1u << (2 * rt + ct);
+                        }
+                    if (smask == 0) {
+                        // nothing of this tile can pass: the epilogue's tail alone. The same two threshold loads as the
+                        // epilogue issues, so every tile adds the same VMEM ops behind the K-loop's constant sequence
+                        // (more ops behind an awaited one only make a counted wait stricter, fewer never happen).
+                        run_epilogue = false;
+#pragma unroll
+                        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                                for (int g = 0; g < 16; ++g) acc[rt][ct][g] = 0.0f;
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct) gload1_agent(tg_next[ct], gthr + q0 + 64 * wu + ct, 8u * (uint32_t)(lane & 31));
+                    } else {
+                        // ---- correction: qh.vl + ql.vh of the flagged sub-tiles, by this wave alone ----
+                        // Fragments straight from global memory in the layouts the K-loop reads: A fragment (K-step ks, depth m,
+                        // row tile rt) = 64 lanes x 16 B at ((2 m + lane / 32) 128 + 32 rt + lane % 32) 16 of the tile's 8-KiB
+                        // piece of step ks (hi: Ab, lo: Abx), B fragment as issue_b addresses it (lo: b_lo behind). Plain loads:
+                        // the compiler waits for them itself (no asm load is issued between a load and its use), and these extra
+                        // VMEM ops only make the K-loop's counted waits stricter. No LDS, no barrier.
+                        if (lane == 0) {
+                            atomicAdd(errflag + kScreenCountWord, 1u);
+                            atomicAdd(errflag + kScreenCountWord + 1, (uint32_t)__builtin_popcount(smask));
+                        }
+                        const char* ca = Ab + (size_t)tile * nk * kBfStageBytes;
+                        const char* cx = Abx + (size_t)tile * nk * kBfStageBytes;
+                        const uint32_t fo = ((uint32_t)(lane >> 5) * 128u + (uint32_t)(lane & 31)) * 16u;
+                        constexpr int kCorrSteps = 2;  // K-steps of loads per wait: 16 loads, 64 registers
+                        static_assert(kCorrSteps == kBfLead, "nk is a multiple of kBfLead (launch_gemm_split checks it): a batch never leaves the tile");
+#pragma unroll
+                        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                            for (int ct = 0; ct < 2; ++ct) {
+                                if (!(smask & (1u << (2 * rt + ct)))) continue;  // wave-uniform; the accumulator index is static
+                                for (uint32_t k0 = 0; k0 < nk; k0 += kCorrSteps) {
+                                    u32x4_t fa[kCorrSteps][2], fl[kCorrSteps][2], fb[kCorrSteps][2], fbl[kCorrSteps][2];
+#pragma unroll
+                                    for (int j = 0; j < kCorrSteps; ++j)
+#pragma unroll
+                                        for (int m = 0; m < 2; ++m) {
+                                            const size_t ao = (size_t)(k0 + j) * kBfStageBytes + (size_t)((2 * m * 128 + rt * 32) * 16) + fo;
+                                            const char* pb = sb + (size_t)(k0 + j) * b_step + (size_t)m * b_depth + (size_t)ct * b_ct + vb;
+                                            fa[j][m] = *reinterpret_cast<const u32x4_t*>(ca + ao);
+                                            fl[j][m] = *reinterpret_cast<const u32x4_t*>(cx + ao);
+                                            fb[j][m] = *reinterpret_cast<const u32x4_t*>(pb);
+                                            fbl[j][m] = *reinterpret_cast<const u32x4_t*>(pb + b_lo);
+                                        }
+#pragma unroll
+                                    for (int j = 0; j < kCorrSteps; ++j)
+#pragma unroll
+                                        for (int m = 0; m < 2; ++m) {
+                                            acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                                                __builtin_bit_cast(bf16x8_t, fa[j][m]), __builtin_bit_cast(bf16x8_t, fbl[j][m]), acc[rt][ct], 0, 0, 0);
+                                            acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                                                __builtin_bit_cast(bf16x8_t, fl[j][m]), __builtin_bit_cast(bf16x8_t, fb[j][m]), acc[rt][ct], 0, 0, 0);
+                                        }
+                                }
+                            }
+                    }
+                }
+                if (run_epilogue) {
 #include "gemm_epilogue.inc"
+                }
                 ks = 0;
                 ++tile;
             } else {

@@ -99,12 +99,14 @@ for name in names:
                 continue
             bad.append(t)
     short = re.sub(r".*gemm_filter_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E.*", r"<\1,\2,\3,\4>", name)
-    short = re.sub(r".*gemm_bf16_filter_kernelILi(\d+)ELi(\d+)ELi(\d+)E.*", r"bf16<\1,\2,\3>", short)
+    short = re.sub(r".*gemm_bf16_filter_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E.*", r"bf16<\1,\2,\3,\4>", short)
     short = re.sub(r".*gemm_i8_filter_kernelILi(\d+)ELi(\d+)E.*", r"i8<\1,\2>", short)
     short = re.sub(r".*gemm_i8h_filter_kernelILi(\d+)ELi(\d+)E.*", r"i8h<\1,\2>", short)
     want_pairs = 8  # f32: 8 k-pairs of one K-step; bf16 / int8: 2 ring positions x 2 depths x 2 fragments
-    if short.startswith("bf16<") and short.endswith(",3>"):
-        want_pairs = 16  # split-bf16 filter: 2 ring positions x 2 depths x (hi, lo) x 2 fragments
+    if short.startswith("bf16<") and short.endswith(",3,0>"):
+        # split-bf16 filter, full loop (MODE 1 and no_split_screen): 2 ring positions x 2 depths x (hi, lo) x 2 fragments;
+        # its screened form bf16<R,0,3,1> runs the one-limb K-loop: 8 (the correction's loads are the compiler's, not asm)
+        want_pairs = 16
     status = "ok" if (len(pairs) == want_pairs and not bad and not unsafe) else "FAIL"
     print(f"{short}: {len(pairs)} operand pairs, {len(bad)} foreign reads, {len(unsafe)} asm loads without s_mov_b64 base  {status}")
     for b in (bad + unsafe)[:5]:
