@@ -1509,8 +1509,15 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     // the wave tiles it corrects (flag words kScreenCountWord); the first pass reads them with its proof flags and the batch
     // remembers the share per list class. Above kScreenMaxShare later calls take the full loop and every 64th screens again
     // (the data or the batch size may have changed). no_split_screen: 1 never screens, -1 always does.
+    // Round 6 (pair correction for lists up to 64, profiles/r06_split_ab.txt): a flagged wave tile of a short list costs one or two
+    // round trips instead of a sub-tile's dozen, so the screen's lead at 18 % grows (1024 queries: 15 against 34 ms); the long lists'
+    // kernels have no room for the pair path and keep rule and figures. The share still counts flagged wave tiles (word 32): between
+    // the 18 % of uniform data and the 98 % of LCG data, whose wave tiles overflow the pair queue and pay the sub-tile correction
+    // as before, the sweep has no point that would place the constant anywhere else.
     const int scls = p.KP <= 64 ? 0 : 1;
-    bool screen = use_split && c->tune.no_split_screen <= 0;
+    // (lists up to 64 run the pair correction, whose query offsets are 32 bits up to kPairMaxQpad = 2^20 queries: larger batches of
+    //  short lists take the full loop whatever no_split_screen says; the long lists' kernels have no pair path and no such limit)
+    bool screen = use_split && c->tune.no_split_screen <= 0 && (p.KP > 64 || p.Qpad <= kPairMaxQpad);
     if (screen && c->tune.no_split_screen == 0) {
         screen = p.KP <= 64 || Q <= 128;
         if (screen && level == 0 && b->screen_share[scls] > kScreenMaxShare && (++b->screen_skips[scls] % 64u) != 0) screen = false;
@@ -1941,6 +1948,54 @@ innr_status innrdbg_split_screen_counts(innr_batch* b, uint32_t* counts) {
     innr_ctx* c = b->ctx;
     INNR_ENTER(c);
     INNR_HIP_CHECK(hipMemcpy(counts, c->flags.as<uint32_t>() + kScreenCountWord, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return INNR_OK;
+}
+// ... and with how the flagged wave tiles were corrected: counts[2] = (row, query) pairs corrected one by one (the pair path),
+// counts[3] = wave tiles with more than kPairCap flagged pairs (the MFMA correction of their flagged sub-tiles)
+innr_status innrdbg_split_screen_counts4(innr_batch* b, uint32_t* counts) {
+    if (!b || !counts) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(hipMemcpy(counts, c->flags.as<uint32_t>() + kScreenCountWord, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return INNR_OK;
+}
+// the pair path's capacity P (kPairCap) of this build
+int innrdbg_split_pair_cap(void) { return kPairCap; }
+
+// Test hook: the pair correction's arithmetic and addressing. out[i] = qh.vl + ql.vh of corpus row pairs[2 i] and query pairs[2 i + 1]
+// (i < n), from the batch's limb copies and the queries packed as knn_mfma packs them (cosine: limbs of the normalised values), by
+// split_pair_delta -- the function the screened kernel corrects its flagged pairs with. INNR_E_UNSUPPORTED when the limb copies do
+// not fit.
+innr_status innrdbg_split_pair_scores(innr_batch* b, const float* queries, size_t Q, int metric, const uint32_t* pairs, size_t n, float* out) {
+    if (b && !b->V) return INNR_E_BAD_ARG;
+    if (!b || !queries || !pairs || !out || Q == 0 || n == 0 || n > (1u << 20) || b->N == 0 || metric == INNR_METRIC_L2SQ || !metric_ok(metric))
+        return INNR_E_BAD_ARG;
+    for (size_t i = 0; i < n; ++i)
+        if (pairs[2 * i] >= b->N || pairs[2 * i + 1] >= Q) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    const bool cos = metric == INNR_METRIC_COSINE;
+    const size_t D = b->D;
+    const GemmPlan p = plan_gemm(b, Q, 1, /*waves=*/8);
+    if (p.Qpad > kPairMaxQpad) return INNR_E_BAD_ARG;
+    INNR_TRY(ensure_norms(b));
+    if (cos) INNR_TRY(ensure_invnorms(b));
+    bool ok = false;
+    INNR_TRY(ensure_split_corpus(b, metric, &ok));
+    if (!ok) return INNR_E_UNSUPPORTED;
+    INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
+    INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
+    INNR_TRY(prep_queries(b, p, c->q_row.as<float>(), Q, cos));
+    INNR_TRY(pack_queries_split(b, p, c->q_row.as<float>(), Q, cos ? c->misc.as<float>() : nullptr));
+    INNR_TRY(c->scores.ensure(n * 3 * sizeof(uint32_t)));
+    uint32_t* d_pairs = c->scores.as<uint32_t>();
+    float* d_out = c->scores.as<float>() + 2 * n;
+    INNR_HIP_CHECK(hipMemcpyAsync(d_pairs, pairs, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const CorpusCopy &hi = b->copy[bf16_kind(metric)], &lo = b->copy[bf16_kind(metric, true)];
+    split_pair_scores_kernel<<<(unsigned)((n + kPairNP - 1) / kPairNP), 64, 0, c->stream>>>(hi.p, lo.p, c->q_bf16.as<char>(), hi.nk, p.Qpad, d_pairs, (uint32_t)n, d_out);
+    INNR_HIP_CHECK(hipGetLastError());
+    INNR_HIP_CHECK(hipMemcpyAsync(out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    INNR_HIP_CHECK(ctx_sync(c));
     return INNR_OK;
 }
 

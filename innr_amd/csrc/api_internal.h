@@ -71,7 +71,7 @@ struct innr_tuning {
     long i8_small_free = 0;      // ... its query groups run free (no soft lockstep): A/B
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
-    long no_split_screen = 0;    // ... 1: its full three-product K-loop, never the hi.hi loop with screened corrections; -1: always the screened loop; 0: by list length, batch size and the share of wave tiles the batch's last screened call corrected (A/B, tests)
+    long no_split_screen = 0;    // ... 1: its full three-product K-loop, never the hi.hi loop with screened corrections; -1: always the screened loop; 0: by list length, batch size and the share of wave tiles the batch's last screened call corrected (A/B, tests); lists up to 64 beyond 2^20 padded queries always take the full loop (kPairMaxQpad)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
     long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip

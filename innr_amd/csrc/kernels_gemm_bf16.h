@@ -29,6 +29,7 @@ namespace innr {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x4s __attribute__((ext_vector_type(4)));
 
 constexpr int kBfStages = 8, kBfLead = 2, kBfStageBytes = 8192, kBfWaves = 8, kBfK = 32;
 static_assert(kBfStages == 8 && kBfLead == 2, "the one-barrier-per-two-steps schedule is derived for an 8-stage ring and a 2-step register ring");
@@ -51,7 +52,20 @@ __device__ __forceinline__ uint16_t bf16_limb(float x, int l) {
     return h;
 }
 constexpr uint32_t kBfL2Extra = 6;  // the squared-L2 copy's additional K columns
-constexpr uint32_t kScreenCountWord = 32;  // errflag words [32, 34): wave tiles the screened split filter corrected, and their sub-tiles
+// errflag words [32, 36) of the screened split filter: wave tiles that flagged something, their flagged sub-tiles, the (row, query)
+// pairs corrected one by one (the pair path), and the wave tiles that flagged more than kPairCap pairs (the MFMA fallback)
+constexpr uint32_t kScreenCountWord = 32;
+// P: the most flagged pairs of one wave tile that the pair path corrects (DESIGN.md 4.4e has the sweep over 8 / 16 / 32)
+#ifndef INNR_PAIR_CAP
+#define INNR_PAIR_CAP 16
+#endif
+constexpr int kPairCap = INNR_PAIR_CAP;
+static_assert(kPairCap >= 2 && kPairCap <= 64, "a queue entry's slot is a count of flagged lanes; the queue is a few LDS words per wave");
+// pairs whose loads are in flight behind one wait. ONE: with two (64 registers beside the 128 accumulators and the K-loop's operand
+// ring) the allocator spills 65 registers, the in-flight ring among them (tools/check_gemm_asm.py fails)
+constexpr int kPairNP = 1;
+static_assert(kPairCap % kPairNP == 0, "the finish loop takes the queue kPairNP entries at a time");
+constexpr size_t kPairMaxQpad = (size_t)1 << 20;  // split_pair_delta: 128 query units of Qpad x 16 bytes are a 32-bit lane offset
 
 // one thread per 16-byte output unit (8 dimensions of one corpus row)
 // limb: 0 = the rounded values (the hi limb: kCopyBfDot / -Cos / -L2), 1 = their lo limbs (kCopyBfDotLo / -CosLo, the split filter; not with sqn)
@@ -154,13 +168,115 @@ __device__ __forceinline__ int32_t screen_raw(uint32_t key, float m) {
     return (int32_t)__float_as_uint(t) - 1;
 }
 
+// The split filter's two small products of single (corpus row, query) pairs, qh.vl + ql.vh, by the whole wave from global memory:
+// out[p] for NP pairs at once (NP x 2 units x 4 loads in flight behind one wait, 32 NP registers; the screened kernel takes its
+// queue kPairNP pairs at a time). tile / row: the corpus row 128 tile + row (row 0..127), pos: the query's position within Qpad (position
+// 64 w + 32 ct + j holds query 64 w + 2 j + ct). A pair is 4 nk 16-byte units (K-step ks, group kg: u = 4 ks + kg) of each of the
+// four limb vectors, addressed as the pack kernels above write them: corpus ((tile nk + ks) 8192 + kg 2048 + (row % 4) 512 +
+// (row / 4) 16, the same in Ab and Abx), queries (u Qpad + pos) 16, the lo limbs nk 4 Qpad 16 bytes behind the hi limbs. Lane l
+// takes units l, l + 64 (every row up to D = 1024 in one trip) and so on in trips of 128. bf16 -> f32 is a shift, every product
+// is exact, the 2D of them are summed in f32: another order of the sum the MFMA correction forms, within the same bound (4.4e).
+// Plain loads: the compiler waits for them. The result is the same in every lane.
+template <int NP>
+__device__ __forceinline__ void split_pair_delta(const char* __restrict__ Ab, const char* __restrict__ Abx, const char* __restrict__ Bb,
+                                                 const uint32_t (&tile)[NP], const uint32_t (&row)[NP], const size_t (&pos)[NP], uint32_t nk,
+                                                 size_t Qpad, int lane, float (&out)[NP]) {
+    const uint32_t nu = 4 * nk;
+    const size_t b_lo = (size_t)nu * Qpad * 16;
+    const uint32_t q_unit = (uint32_t)Qpad * 16u;  // (128 of them fit 32 bits: kPairMaxQpad)
+    float sum[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) sum[p] = 0.0f;
+    for (uint32_t u0 = 0; u0 < nu; u0 += 128) {
+        // every address is a wave-uniform base (the pair, the trip) plus a 32-bit lane offset (the unit): no address registers
+        const char *pv[NP], *pl[NP], *pq[NP], *pql[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const size_t ao = (size_t)tile[p] * nk * kBfStageBytes + (size_t)((row[p] & 3) * 512 + (row[p] >> 2) * 16);
+            pv[p] = uniform_ptr(Ab + ao);
+            pl[p] = uniform_ptr(Abx + ao);
+            pq[p] = uniform_ptr(Bb + ((size_t)u0 * Qpad + pos[p]) * 16);
+            pql[p] = uniform_ptr(Bb + b_lo + ((size_t)u0 * Qpad + pos[p]) * 16);
+        }
+        u32x4_t vh[NP][2], vl[NP][2], qh[NP][2], ql[NP][2];
+        bool live[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t u = u0 + 64 * j + (uint32_t)lane;
+            live[j] = u < nu;
+            const uint32_t uc = live[j] ? u : nu - 1;  // past the row's end: its last unit again, not summed
+            const uint32_t co = (uc >> 2) * (uint32_t)kBfStageBytes + (uc & 3) * 2048u, qo = (uc - u0) * q_unit;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                vh[p][j] = *reinterpret_cast<const u32x4_t*>(pv[p] + co);
+                vl[p][j] = *reinterpret_cast<const u32x4_t*>(pl[p] + co);
+                qh[p][j] = *reinterpret_cast<const u32x4_t*>(pq[p] + qo);
+                ql[p][j] = *reinterpret_cast<const u32x4_t*>(pql[p] + qo);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                float t = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {  // two bf16 per word: the low half shifted up, the high half masked
+                    t = __builtin_fmaf(__uint_as_float(qh[p][j][e] << 16), __uint_as_float(vl[p][j][e] << 16), t);
+                    t = __builtin_fmaf(__uint_as_float(ql[p][j][e] << 16), __uint_as_float(vh[p][j][e] << 16), t);
+                    t = __builtin_fmaf(__uint_as_float(qh[p][j][e] & 0xffff0000u), __uint_as_float(vl[p][j][e] & 0xffff0000u), t);
+                    t = __builtin_fmaf(__uint_as_float(ql[p][j][e] & 0xffff0000u), __uint_as_float(vh[p][j][e] & 0xffff0000u), t);
+                }
+                sum[p] += live[j] ? t : 0.0f;
+            }
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) sum[p] += __shfl_xor(sum[p], off, 64);
+        out[p] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sum[p])));
+    }
+}
+
+// row within its 32 x 32 sub-tile of a queue entry (lane | g << 6 | ct << 10 | rt << 11) of the screened kernel: the MFMA's output layout
+__device__ __forceinline__ uint32_t prow_in_subtile(uint32_t en) {
+    const uint32_t g = (en >> 6) & 15;
+    return (g & 3) + 8 * (g >> 2) + 4 * ((en >> 5) & 1);
+}
+
+#ifdef INNR_TEST_HOOKS
+// innrdbg_split_pair_scores: split_pair_delta as the screened kernel calls it (kPairNP pairs per call), one wave per kPairNP
+// caller-given pairs; pairs[2 i] = corpus row, pairs[2 i + 1] = query (both checked by the host), out[i] = qh.vl + ql.vh of pair i
+__global__ __launch_bounds__(64) void split_pair_scores_kernel(const char* __restrict__ Ab, const char* __restrict__ Abx, const char* __restrict__ Bb,
+                                                               uint32_t nk, size_t Qpad, const uint32_t* __restrict__ pairs, uint32_t n,
+                                                               float* __restrict__ out) {
+    const uint32_t i0 = kPairNP * blockIdx.x;
+    uint32_t tile[kPairNP], row[kPairNP];
+    size_t pos[kPairNP];
+#pragma unroll
+    for (int p = 0; p < kPairNP; ++p) {
+        const uint32_t i = i0 + p < n ? i0 + p : n - 1;
+        const uint32_t r = pairs[2 * i], q = pairs[2 * i + 1];
+        tile[p] = r / 128;
+        row[p] = r % 128;
+        pos[p] = (q & ~63u) + 32 * (q & 1) + ((q & 63) >> 1);
+    }
+    float d[kPairNP];
+    split_pair_delta<kPairNP>(Ab, Abx, Bb, tile, row, pos, nk, Qpad, (int)threadIdx.x, d);
+#pragma unroll
+    for (int p = 0; p < kPairNP; ++p)
+        if (threadIdx.x == (uint32_t)p && i0 + p < n) out[i0 + p] = d[p];
+}
+#endif
+
 // MODE 0: fused top-k filter. MODE 1: dump the dense score matrix (layout test).
 // LIMBS 1: the bf16 filter (Abx unused). LIMBS 3: the split filter -- Abx the corpus' lo-limb copy, Bb holds nk K-steps of query hi
 // limbs followed by nk K-steps of lo limbs.
 // SCREEN (LIMBS 3, MODE 0 only): the K-loop is the LIMBS = 1 loop -- hi.hi alone, the lo copies untouched. At the
 // end of a tile every 32 x 32 sub-tile whose best hi.hi score stays more than the queries' screen margin (gthr + 2 Qpad: a bound of
 // |qh.vl + ql.vh| and of their accumulation) below the threshold is rejected as its full score would have been; to the others the
-// wave alone adds the two small products from global memory, and the shared epilogue runs on the full split scores.
+// wave alone adds the two small products from global memory, and the shared epilogue runs on the full split scores. Lists up to 64
+// (R <= 8): a wave tile with at most kPairCap (row, query) pairs at thr - m corrects exactly those pairs, each by the whole wave in
+// one memory round trip (split_pair_delta); a wave tile with more keeps the MFMA correction of its flagged sub-tiles.
 template <int R, int MODE, int LIMBS, int SCREEN = 0>
 __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     const char* __restrict__ Ab, const char* __restrict__ Abx, const char* __restrict__ Bb, uint32_t ntiles, uint32_t N, uint32_t nk, size_t Qpad, uint32_t nqt,
@@ -174,6 +290,7 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     const float iq_lane[2] = {1.0f, 1.0f};
     constexpr int kBQ = 64 * kBfWaves;
     constexpr bool kScreen = SCREEN != 0;
+    constexpr bool kPairPath = kScreen && R <= 8;  // lists up to 64: the longer lists' kernels have no room for it
     static_assert(!kScreen || (LIMBS == 3 && MODE == 0), "the screen belongs to the split filter's top-k mode");
     constexpr int kLoop = kScreen ? 1 : LIMBS;  // limbs the K-loop multiplies
     using G = BfGeom<kLoop>;
@@ -315,6 +432,9 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
                 __builtin_amdgcn_sched_barrier(0);
             }
             b_ks = (b_ks + 1 == nk) ? 0 : b_ks + 1;
+            // (a use in the hot loop, no instruction: with the pair path the allocator otherwise spills the margin and reloads it at every
+            //  tile's screen behind a full wait, as it does for R = 12 / 20)
+            if (kPairPath) asm volatile("" : "+v"(smarg[0]), "+v"(smarg[1]));
             // nk is a multiple of kBfLead, so a tile always ends on the last ring position: ONE copy of the epilogue in
             // the unrolled loop (two copies made the kernel 81 KB, more than the 64 KB instruction cache)
 #ifdef INNR_GEMM_PROBE_SKIPEPI  // tools/bf16_epi_probe.hip: the same code, the epilogue never taken (dump == nullptr at run time)
@@ -361,19 +481,100 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
 #pragma unroll
                         for (int ct = 0; ct < 2; ++ct) gload1_agent(tg_next[ct], gthr + q0 + 64 * wu + ct, 8u * (uint32_t)(lane & 31));
                     } else {
-                        // ---- correction: qh.vl + ql.vh of the flagged sub-tiles, by this wave alone ----
+                        // ---- which PAIRS of the flagged sub-tiles reach thr - m: a per-wave LDS queue of (rt, ct, g, lane) ----
+                        // (lists up to 64, kPairPath: the longer lists' kernels have neither the registers nor, at R = 20, the room
+                        //  below the 64 KB instruction cache; they correct every flagged wave tile by MFMA as before.)
+                        // Wave scope only: the queue and the deltas are this wave's own, LDS operations of a wave complete in
+                        // order, no block barrier. One runtime loop over the set bits of smask: the sub-tile's 16 values are
+                        // selected into one register tuple (the only code per sub-tile; a static walk over the 128 values,
+                        // written out 8 x 16 times, put the kernel past the instruction cache), a lane collects their flags in
+                        // a mask, and an inner loop takes every lane's lowest flagged g per trip (one trip unless a lane holds
+                        // two flagged values of the sub-tile): a value's slot is the running count plus its lane's rank among
+                        // the lanes of the trip. Nothing is written past kPairCap.
+                        __shared__ uint32_t pairq[kBfWaves][kPairCap];
+                        __shared__ uint2 pairw[kBfWaves][kPairCap];  // a pair's delta as three bf16 limbs
+                        // (the lane and wave numbers made opaque here: nothing derived from them for this branch -- LDS addresses,
+                        //  lane masks -- is computed ahead of the K-loop and held in registers across it)
+                        int ln = lane, wq = wu;
+                        asm volatile("" : "+v"(ln), "+s"(wq));
+                        uint32_t npair = 0;
+#pragma unroll 1
+                        for (uint32_t sm = kPairPath ? smask : 0u; sm != 0; sm &= sm - 1) {
+                            const uint32_t sidx = (uint32_t)__builtin_ctz(sm);  // 2 rt + ct, wave-uniform
+                            f32x16 sv = acc[0][0];  // this sub-tile's 16 values: 16 moves per sub-tile, one code path behind them
+#pragma unroll
+                            for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                                for (int ct = 0; ct < 2; ++ct)
+                                    if (sidx == (uint32_t)(2 * rt + ct)) sv = acc[rt][ct];
+                            const int32_t t = (sidx & 1) ? traw[1] : traw[0];
+                            uint32_t gm = 0;
+#pragma unroll
+                            for (int g = 0; g < 16; ++g) gm |= (int32_t)__float_as_uint(sv[g]) >= t ? 1u << g : 0u;
+#pragma unroll 1
+                            for (unsigned long long fm = __ballot(gm != 0); fm != 0; fm = __ballot(gm != 0)) {
+                                const uint32_t slot = npair + __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+                                if (gm != 0 && slot < (uint32_t)kPairCap) pairq[wq][slot] = (uint32_t)ln | (uint32_t)__builtin_ctz(gm) << 6 | sidx << 10;
+                                gm &= gm - 1;
+                                npair += (uint32_t)__builtin_popcountll(fm);
+                            }
+                        }
+                        const bool by_pairs = kPairPath && npair <= (uint32_t)kPairCap;  // wave-uniform
+                        if (ln < 4) {  // words 32 .. 35, one atomic instruction
+                            const uint32_t add = ln == 0 ? 1u : ln == 1 ? (uint32_t)__builtin_popcount(smask) : ln == 2 ? (by_pairs ? npair : 0u) : (by_pairs ? 0u : 1u);
+                            const uint32_t l4 = 4u * (uint32_t)ln;
+                            atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(errflag + kScreenCountWord) + l4), add);
+                        }
+                        if (by_pairs) {
+                            // ---- pair correction: qh.vl + ql.vh of each queued pair by the whole wave (split_pair_delta), one
+                            // memory round trip per kPairNP pairs; the deltas wait in LDS as three bf16 limbs each. They reach
+                            // the accumulators in the sub-tile loop below, shared with the MFMA correction: one MFMA per pair on
+                            // its sub-tile with A = 1.0 in row i at k = 0, 1, 2 and B = the limbs of d in column j, so exactly
+                            // (i, j) receives d1 + d2 + d3 (= d up to 2^-24 |d|, inside the accumulation term of E and of the
+                            // margin) and every other value of the sub-tile + 0. (The accumulator tuples change only there, in
+                            // place, by MFMA: single elements assigned under a branch, MFMAs under a runtime sub-tile index, or a
+                            // second static loop of their own made the register allocator copy and spill the tuples.) An
+                            // unflagged value keeps its hi.hi score, below thr - m: rejected as its full score would have been.
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll 1
+                            for (uint32_t e = 0; e < npair; e += kPairNP) {  // (a ragged end: the last pair again, its delta unused)
+                                uint32_t prow[kPairNP], ptile[kPairNP];
+                                size_t ppos[kPairNP];
+#pragma unroll
+                                for (int p = 0; p < kPairNP; ++p) {
+                                    const uint32_t en = __builtin_amdgcn_readfirstlane(pairq[wq][e + p < npair ? e + p : npair - 1]);
+                                    const uint32_t L = en & 63, g = (en >> 6) & 15;
+                                    ptile[p] = tile;
+                                    prow[p] = 4 * ((g & 3) + 8 * (g >> 2) + 4 * (L >> 5)) + (en >> 11);  // the epilogue's row of (rt, g, lane)
+                                    ppos[p] = q0 + 64 * (size_t)wq + 32 * ((en >> 10) & 1) + (L & 31);
+                                }
+                                float d[kPairNP];
+                                split_pair_delta<kPairNP>(Ab, Abx, Bb, ptile, prow, ppos, nk, Qpad, ln, d);
+                                if (ln < kPairNP) {  // (kPairCap is a multiple of kPairNP: e + lane is a slot)
+                                    float dl = d[0];
+#pragma unroll
+                                    for (int p = 1; p < kPairNP; ++p) dl = ln == p ? d[p] : dl;
+                                    pairw[wq][e + ln] = uint2{(uint32_t)bf16_limb(dl, 0) | (uint32_t)bf16_limb(dl, 1) << 16, (uint32_t)bf16_limb(dl, 2)};
+                                }
+                            }
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        }
+                        {
+                        // ---- per flagged sub-tile: the queued pairs' deltas (by_pairs), or the MFMA correction (more than kPairCap
+                        // pairs: near ties, tiles without a bound, long lists): qh.vl + ql.vh of the whole sub-tile, by this wave alone ----
                         // Fragments straight from global memory in the layouts the K-loop reads: A fragment (K-step ks, depth m,
                         // row tile rt) = 64 lanes x 16 B at ((2 m + lane / 32) 128 + 32 rt + lane % 32) 16 of the tile's 8-KiB
                         // piece of step ks (hi: Ab, lo: Abx), B fragment as issue_b addresses it (lo: b_lo behind). Plain loads:
                         // the compiler waits for them itself (no asm load is issued between a load and its use), and these extra
-                        // VMEM ops only make the K-loop's counted waits stricter. No LDS, no barrier.
-                        if (lane == 0) {
-                            atomicAdd(errflag + kScreenCountWord, 1u);
-                            atomicAdd(errflag + kScreenCountWord + 1, (uint32_t)__builtin_popcount(smask));
-                        }
+                        // VMEM ops only make the K-loop's counted waits stricter. No barrier.
                         const char* ca = Ab + (size_t)tile * nk * kBfStageBytes;
                         const char* cx = Abx + (size_t)tile * nk * kBfStageBytes;
-                        const uint32_t fo = ((uint32_t)(lane >> 5) * 128u + (uint32_t)(lane & 31)) * 16u;
+                        const uint32_t fo = ((uint32_t)(ln >> 5) * 128u + (uint32_t)(ln & 31)) * 16u;
+                        const uint32_t vbq = ((uint32_t)(ln >> 5) * (uint32_t)Qpad + (uint32_t)(ln & 31)) * 16u;  // vb, made here
                         constexpr int kCorrSteps = 2;  // K-steps of loads per wait: 16 loads, 64 registers
                         static_assert(kCorrSteps == kBfLead, "nk is a multiple of kBfLead (launch_gemm_split checks it): a batch never leaves the tile");
 #pragma unroll
@@ -381,6 +582,20 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
 #pragma unroll
                             for (int ct = 0; ct < 2; ++ct) {
                                 if (!(smask & (1u << (2 * rt + ct)))) continue;  // wave-uniform; the accumulator index is static
+                                if (by_pairs) {
+#pragma unroll 1
+                                    for (uint32_t e = 0; e < npair; ++e) {
+                                        const uint32_t en = __builtin_amdgcn_readfirstlane(pairq[wq][e]);
+                                        if ((en >> 10) != (uint32_t)(2 * rt + ct)) continue;
+                                        const uint2 dw = pairw[wq][e];
+                                        const bool ra = (uint32_t)ln == prow_in_subtile(en), cb = (uint32_t)ln == (en & 31);  // lanes 0 .. 31 hold k = 0 .. 7
+                                        const u32x4_t fa = {ra ? 0x3F803F80u : 0u, ra ? 0x3F80u : 0u, 0u, 0u};
+                                        const u32x4_t fb = {cb ? dw.x : 0u, cb ? dw.y : 0u, 0u, 0u};
+                                        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa), __builtin_bit_cast(bf16x8_t, fb),
+                                                                                              acc[rt][ct], 0, 0, 0);
+                                    }
+                                    continue;
+                                }
                                 for (uint32_t k0 = 0; k0 < nk; k0 += kCorrSteps) {
                                     u32x4_t fa[kCorrSteps][2], fl[kCorrSteps][2], fb[kCorrSteps][2], fbl[kCorrSteps][2];
 #pragma unroll
@@ -388,7 +603,7 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
 #pragma unroll
                                         for (int m = 0; m < 2; ++m) {
                                             const size_t ao = (size_t)(k0 + j) * kBfStageBytes + (size_t)((2 * m * 128 + rt * 32) * 16) + fo;
-                                            const char* pb = sb + (size_t)(k0 + j) * b_step + (size_t)m * b_depth + (size_t)ct * b_ct + vb;
+                                            const char* pb = sb + (size_t)(k0 + j) * b_step + (size_t)m * b_depth + (size_t)ct * b_ct + vbq;
                                             fa[j][m] = *reinterpret_cast<const u32x4_t*>(ca + ao);
                                             fl[j][m] = *reinterpret_cast<const u32x4_t*>(cx + ao);
                                             fb[j][m] = *reinterpret_cast<const u32x4_t*>(pb);
@@ -405,6 +620,7 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
                                         }
                                 }
                             }
+                        }
                     }
                 }
                 if (run_epilogue) {
