@@ -43,7 +43,7 @@ static const TuneName kTuneNames[] = {
     {"i8_slices_per_cu", &innr_tuning::i8_slices_per_cu}, {"i8_no_small", &innr_tuning::i8_no_small},
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
-    {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
+    {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"split_screen_worst_case", &innr_tuning::split_screen_worst_case}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
     {"copy_budget_mib", &innr_tuning::copy_budget_mib}, {"scan_max_slots", &innr_tuning::scan_max_slots},
 };
 static void tuning_from_env(innr_tuning* t) {
@@ -1155,35 +1155,86 @@ static float split_filter_scale(const innr_batch* b, int metric) {
 // So s <= s_hh + m with m = 1.05 (2^-7 1.004 + (6D + 8) u 1.04) |q| max|v| (cosine: 1 for |q^||v^|, the (1 + D u)^2 inside the 1.05):
 // a sub-tile below thr - m holds nothing that the full loop would have kept, and is rejected exactly as its full scores would be.
 // The scores of corrected sub-tiles accumulate in another order than the full loop's; E covers any order.
+//
+// The first term above is the WORST CASE over all data: every lo limb at half a last place of its hi limb, signs aligned. The
+// limbs the copies really hold give a bound of the same kind that is never larger: Cauchy-Schwarz on the limb vectors themselves,
+//     |qh.vl_i + ql.vh_i| <= |qh| |vl_i| + |ql| |vh_i| <= |qh| Lmax + |ql| Hmax,   Hmax = max_i |vh_i|, Lmax = max_i |vl_i|
+// over the rows the copies hold (limb_maxima_kernel, kept in CorpusCopy::limb_max of the hi / the lo copy) and |qh_j|, |ql_j| of the
+// limbs pack_queries_bf16_kernel writes (cosine: of the normalised values on both sides) -- every norm summed in double and
+// rounded up. It is as rigorous as the worst case and at most (1 + 2^-8)^2 2^-7 |q| max|v| <= the worst case's term, since
+// |qh| <= (1 + 2^-8) |q|, |vl| <= (1 + 2^-8) 2^-8 |v| and the same with the roles exchanged. Lo limbs of real data are spread over
+// (-1/2, 1/2) last places: root-mean-square 1 / sqrt(12) of the worst case's 1/2 each, so the sum of the two products is about
+// 0.38 of the worst case on uniform data, 0.43 on normal data, and close to 1 only on data built to sit at half a last place.
+// The screen's margin of a query (screen_margin_kernel) is
+//     m_j = 1.0002 [ 1.05 ( |qh_j| Lmax + |ql_j| Hmax + (6D + 8) u 1.04 |q_j| max|v| ) + the flush allowance ]
+// (cosine: 1 for |q_j| max|v|), or the worst-case m_j where that is smaller, the maxima are missing or not finite, or the
+// tuning word split_screen_worst_case asks for it. The accumulation term and the flush allowance are the worst case's.
 static float split_screen_scale(const innr_batch* b, int metric) {
     return 1.05f * (0.0078125f * 1.004f + (6.0f * (float)b->D + 8.0f) * 5.9604645e-08f * 1.04f) *
            (metric == INNR_METRIC_COSINE ? 1.0f : b->max_norm);
 }
-// m per query: scale * |q_j| (dot) or scale (cosine: |q^| = 1) + the flush allowance 2^-126 (flush_c + flush_v |q_j|), rounded up;
+// m per query, one wave each. Worst case: scale * |q_j| (dot) or scale (cosine: |q^| = 1) + the flush allowance
+// 2^-126 (flush_c + flush_v |q_j|), rounded up. From the limb norms (hmax, lmax >= 0; the host passes -1 for "worst case only"):
+// the formula above in double, with |qh_j|, |ql_j| of row j of Qm ([Q][D]; qscale as pack_queries_bf16_kernel takes it) and
+// accv = (6D + 8) u 1.04 max|v|, rounded up to float and one more float up; the smaller of the two counts.
 // +inf (no screening: every sub-tile is corrected) where that is not a finite non-negative number. Padding queries are closed
 // (close_padding_queries): their margin plays no part.
-__global__ void screen_margin_kernel(int cosine, float scale, float flush_v, float flush_c, const float* __restrict__ qnorm, uint32_t Q,
-                                     uint32_t Qpad, float* __restrict__ out) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void screen_margin_kernel(int cosine, float scale, float flush_v, float flush_c, float hmax, float lmax,
+                                                             double accv, const float* __restrict__ qnorm, const float* __restrict__ Qm,
+                                                             const float* __restrict__ qscale, uint32_t D, uint32_t Q, uint32_t Qpad,
+                                                             float* __restrict__ out) {
+    const uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
+    const uint32_t lane = threadIdx.x & 63;
     if (j >= Qpad) return;
     float m = 0.0f;
     if (j < Q) {
         const float qn = cosine ? 1.0f : qnorm[j];
-        const float x = (scale * (cosine ? 1.0f : qn) + 1.17549435e-38f * (flush_c + flush_v * qn)) * 1.0002f;
+        float x = (scale * (cosine ? 1.0f : qn) + 1.17549435e-38f * (flush_c + flush_v * qn)) * 1.0002f;
+        if (hmax >= 0.0f && lmax >= 0.0f) {
+            const float qs = qscale ? qscale[j] : 1.0f;
+            double sh = 0.0, sl = 0.0;
+            for (uint32_t d = lane; d < D; d += 64) {
+                const float xs = Qm[(size_t)j * D + d] * qs;
+                const double h = (double)__uint_as_float((uint32_t)bf16_limb(xs, 0) << 16);
+                const double l = (double)__uint_as_float((uint32_t)bf16_limb(xs, 1) << 16);
+                sh += h * h;
+                sl += l * l;
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                sh += __shfl_xor(sh, off, 64);
+                sl += __shfl_xor(sl, off, 64);
+            }
+            const double qh = (double)f32_round_up(sqrt(sh)), ql = (double)f32_round_up(sqrt(sl));
+            const double y = 1.0002 * (1.05 * (qh * (double)lmax + ql * (double)hmax + accv * (double)qn) +
+                                       1.1754943508222875e-38 * ((double)flush_c + (double)flush_v * (double)qn));
+            float yf = f32_round_up(y);
+            if (yf - yf == 0.0f) yf = __uint_as_float(__float_as_uint(yf) + 1u);
+            if (yf < x) x = yf;  // (a NaN compares false: the worst case stays)
+        }
         m = (x - x == 0.0f && x >= 0.0f) ? x : __builtin_inff();
     }
-    out[j] = m;
+    if (lane == 0) out[j] = m;
 }
 // c->kmargin [Qpad .. 2 Qpad): behind the k rule's margins (make_kmargin sizes the buffer for both when asked first)
-static innr_status make_screen_margin(innr_batch* b, int metric, size_t Q, size_t Qpad, const float** out) {
+// dQ: the call's queries, row-major [Q][D]; qscale: what pack_queries_split was given (cosine: 1/||q||, else null)
+static innr_status make_screen_margin(innr_batch* b, int metric, const float* dQ, const float* qscale, size_t Q, size_t Qpad,
+                                      const float** out) {
     innr_ctx* c = b->ctx;
     const bool cos = metric == INNR_METRIC_COSINE;
     const float sd = sqrtf((float)b->D), vmax = cos ? 1.0f : b->max_norm;
     float* m = c->kmargin.as<float>() + Qpad;
-    screen_margin_kernel<<<(unsigned)((Qpad + 255) / 256), 256, 0, c->stream>>>(cos ? 1 : 0, split_screen_scale(b, metric), sd,
-                                                                               sd * vmax + 6.0f * (float)b->D, c->q_norm.as<float>(),
-                                                                               (uint32_t)Q, (uint32_t)Qpad, m);
+    // the limb maxima of the pair (ensure_limb_maxima); missing or not finite: the worst case alone
+    float hmax = b->copy[bf16_kind(metric)].limb_max, lmax = b->copy[bf16_kind(metric, true)].limb_max;
+    if (c->tune.split_screen_worst_case || !(hmax >= 0.0f && lmax >= 0.0f && hmax - hmax == 0.0f && lmax - lmax == 0.0f)) hmax = lmax = -1.0f;
+    const double accv = (6.0 * (double)b->D + 8.0) * 5.9604644775390625e-08 * 1.04 * (double)vmax;
+    screen_margin_kernel<<<(unsigned)((Qpad + 3) / 4), 256, 0, c->stream>>>(cos ? 1 : 0, split_screen_scale(b, metric), sd,
+                                                                           sd * vmax + 6.0f * (float)b->D, hmax, lmax, accv,
+                                                                           c->q_norm.as<float>(), dQ, qscale, (uint32_t)b->D, (uint32_t)Q,
+                                                                           (uint32_t)Qpad, m);
     INNR_HIP_CHECK(hipGetLastError());
+    c->screen_q = Q;
+    c->screen_qpad = Qpad;
     *out = m;
     return INNR_OK;
 }
@@ -1313,6 +1364,38 @@ static innr_status ensure_bf16_lo(innr_batch* b, int metric, bool soft) {
     return INNR_OK;
 }
 
+// The largest limb norms of a split pair that exists (CorpusCopy::limb_max of the hi and of the lo copy: the screen margin reads
+// them, split_screen_scale): one pass over the f32 store with the copies' own row scaling, once per pair -- when the pair is
+// built or prebuilt, or at the first split call on a hi copy another engine built. Synchronises (two words come back).
+static innr_status ensure_limb_maxima(innr_batch* b, int metric) {
+    CorpusCopy &hi = b->copy[bf16_kind(metric)], &lo = b->copy[bf16_kind(metric, true)];
+    if (!hi.p || !lo.p || (!(hi.limb_max < 0.0f) && !(lo.limb_max < 0.0f))) return INNR_OK;
+    innr_ctx* c = b->ctx;
+    uint32_t* d = nullptr;
+    INNR_HIP_CHECK(hipMalloc((void**)&d, 2 * sizeof(uint32_t)));
+    uint32_t h[2] = {0u, 0u};
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(h), c->stream);
+    uint32_t nrows = (uint32_t)b->N;
+#if defined(INNR_MUTATE_LIMB_MAX) && INNR_MUTATE_LIMB_MAX == 2  // mutation check, never the product: all rows but the last tile's
+    nrows = nrows ? (nrows - 1) / 128 * 128 : 0;
+#endif
+    if (e == hipSuccess) {
+        limb_maxima_kernel<<<(unsigned)((b->ldN / 4 + 255) / 256), 256, 0, c->stream>>>(
+            b->V, b->ldN, nrows, (uint32_t)b->D, metric == INNR_METRIC_COSINE ? b->invn : nullptr, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    INNR_HIP_CHECK(e);
+#if defined(INNR_MUTATE_LIMB_MAX) && INNR_MUTATE_LIMB_MAX == 1  // ... Lmax forced to 0
+    h[1] = 0u;
+#endif
+    memcpy(&hi.limb_max, &h[0], sizeof(float));
+    memcpy(&lo.limb_max, &h[1], sizeof(float));
+    return INNR_OK;
+}
+
 // The hi and lo limb copies of the dot / cosine kind. Each copy is built only when it fits (copy_fits, the rule of the other
 // filter copies); *ok == false: one did not fit, the call filters on the f32 kernel instead.
 static innr_status ensure_split_corpus(innr_batch* b, int metric, bool* ok) {
@@ -1333,6 +1416,7 @@ static innr_status ensure_split_corpus(innr_batch* b, int metric, bool* ok) {
     }
     INNR_TRY(ensure_bf16_lo(b, metric, true));
     *ok = lo.p != nullptr;
+    if (*ok) INNR_TRY(ensure_limb_maxima(b, metric));
     return INNR_OK;
 }
 
@@ -1514,6 +1598,10 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     // kernels have no room for the pair path and keep rule and figures. The share still counts flagged wave tiles (word 32): between
     // the 18 % of uniform data and the 98 % of LCG data, whose wave tiles overflow the pair queue and pay the sub-tile correction
     // as before, the sweep has no point that would place the constant anywhere else.
+    // Round 7 (margin from the limbs' norms, publish cadence 4; profiles/r07_split_ab.txt): uniform data flags 8.4 % (k = 10) and
+    // 40 % (k = 100) of its wave tiles, and lists of 128 are now faster screened at every size swept (256 queries 14.4 against
+    // 15.7 ms, 4096 125.6 against 136.4). Both rules are left as they were: 40 % sits just under kScreenMaxShare, and lists of 256
+    // and data between uniform and LCG have not been swept.
     const int scls = p.KP <= 64 ? 0 : 1;
     // (lists up to 64 run the pair correction, whose query offsets are 32 bits up to kPairMaxQpad = 2^20 queries: larger batches of
     //  short lists take the full loop whatever no_split_screen says; the long lists' kernels have no pair path and no such limit)
@@ -1525,7 +1613,7 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     if (screen) INNR_TRY(c->kmargin.ensure(2 * p.Qpad * sizeof(float)));  // (before make_kmargin: growing the buffer drops its contents)
     INNR_TRY(make_kmargin(c, metric_space(metric), err_scale, c->q_norm.as<float>(), Cj, nullptr, 0.0f, nullptr, Q, p.Qpad, &kmargin));
     const float* smargin = nullptr;
-    if (screen) INNR_TRY(make_screen_margin(b, metric, Q, p.Qpad, &smargin));
+    if (screen) INNR_TRY(make_screen_margin(b, metric, dQ, cos ? c->misc.as<float>() : nullptr, Q, p.Qpad, &smargin));
     const uint32_t kk = (uint32_t)kout;
     INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     if (use_bf16) INNR_TRY(launch_gemm_bf16(b, p, Q, seed, bfv, kmargin, kk));
@@ -1961,6 +2049,26 @@ innr_status innrdbg_split_screen_counts4(innr_batch* b, uint32_t* counts) {
 }
 // the pair path's capacity P (kPairCap) of this build
 int innrdbg_split_pair_cap(void) { return kPairCap; }
+
+// Test hook: what the screen margin was made of. maxima[0] / [1] = the largest hi / lo limb norm of the batch's split pair of
+// `metric` (CorpusCopy::limb_max; -1: not computed), info[0] = max_norm; margins[0 .. n) = the margins of the context's last
+// screened call (n = min(cap, its queries); *nq = its queries, 0 when no call has screened yet), qnorm[0 .. n) its query norms.
+innr_status innrdbg_split_margins(innr_batch* b, int metric, float* maxima, float* info, float* margins, float* qnorm, size_t cap, size_t* nq) {
+    if (!b || !maxima || !info || !nq || metric == INNR_METRIC_L2SQ || !metric_ok(metric)) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(ctx_sync(c));
+    maxima[0] = b->copy[bf16_kind(metric)].limb_max;
+    maxima[1] = b->copy[bf16_kind(metric, true)].limb_max;
+    info[0] = b->max_norm;
+    const bool kept = c->kmargin.p && c->kmargin.bytes >= (c->screen_qpad + c->screen_q) * sizeof(float) && c->q_norm.p &&
+                      c->q_norm.bytes >= c->screen_q * sizeof(float);  // (a trimmed workspace holds none)
+    *nq = kept ? c->screen_q : 0;
+    const size_t n = std::min(cap, *nq);
+    if (n && margins) INNR_HIP_CHECK(hipMemcpy(margins, c->kmargin.as<float>() + c->screen_qpad, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (n && qnorm) INNR_HIP_CHECK(hipMemcpy(qnorm, c->q_norm.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return INNR_OK;
+}
 
 // Test hook: the pair correction's arithmetic and addressing. out[i] = qh.vl + ql.vh of corpus row pairs[2 i] and query pairs[2 i + 1]
 // (i < n), from the batch's limb copies and the queries packed as knn_mfma packs them (cosine: limbs of the normalised values), by
@@ -4013,6 +4121,7 @@ innr_status innr_batch_release_copies(innr_batch* b, uint32_t mask) {
         cc.p = nullptr;
         cc.bytes = 0;
         cc.nk = 0;
+        cc.limb_max = -1.0f;
         cc.refused = false;  // "try again": the next call that wants the copy asks the memory rule anew (weak is about the data: kept)
     }
     if (mask & INNR_COPY_SELECTION) free_selection(b);
@@ -4058,6 +4167,7 @@ innr_status innr_batch_build_copies(innr_batch* b, uint32_t mask, uint32_t* buil
                     if (cos) INNR_TRY(ensure_invnorms(b));
                     INNR_TRY(ensure_bf16_corpus(b, hk));
                     INNR_TRY(ensure_bf16_lo(b, metric, false));
+                    INNR_TRY(ensure_limb_maxima(b, metric));
                 }
                 if (wants(i8_kind(metric)) && f32_i8_eligible(b, metric, 1, 1) && budget_admits(b, f32_i8_copy_bytes(b, metric))) {
                     bool usable = false;

@@ -72,6 +72,7 @@ struct innr_tuning {
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
     long no_split_screen = 0;    // ... 1: its full three-product K-loop, never the hi.hi loop with screened corrections; -1: always the screened loop; 0: by list length, batch size and the share of wave tiles the batch's last screened call corrected (A/B, tests); lists up to 64 beyond 2^20 padded queries always take the full loop (kPairMaxQpad)
+    long split_screen_worst_case = 0;  // ... the screen's margin by the worst-case formula alone (every lo limb at half a last place), never from the limbs' measured norms (A/B, tests)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
     long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip
@@ -190,6 +191,7 @@ struct innr_ctx {
     DevBuf rows_io;    // ... and innr_batch_gather_rows, host-memory entry points: indices in, results out
     DevBuf rows_flag;  // ... the gathers' own error word (an index outside the batch): every entry point clears c->flags
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
+    size_t screen_q = 0, screen_qpad = 0;  // queries of the last screen margins written to kmargin + Qpad (0: none yet; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]
     ScanRec scan_log[kScanLogCap] = {};        // ring of the last exact-scan launches (record_scan; read by a test hook)
@@ -262,6 +264,9 @@ struct CorpusCopy {
     uint32_t nk = 0;       // K-steps of this copy (the rows copy: Dr)
     bool refused = false;  // rows, lo limbs (for the split pair): it did not fit -- do not try again on every call
     bool weak = false;     // int8 kinds: most proofs failed on this corpus (a range blown up by outliers): AUTO stops picking the filter
+    // bf16 dot / cosine kinds and their lo limbs: the largest norm of a row of this copy's limbs, rounded up (limb_maxima_kernel;
+    // the split filter's screen margin); < 0: not computed for the copy that exists now. Lives and dies with the copy.
+    float limb_max = -1.0f;
 };
 }  // namespace innr
 

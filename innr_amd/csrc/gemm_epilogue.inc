@@ -3,7 +3,7 @@
 // gemm_bf16_filter_kernel in kernels_gemm_bf16.h): MODE 1 dumps the scores; MODE 0 runs the fast reject against the
 // list / chip-wide thresholds and, on a hit, the append path (topk_dev.h). Expects in scope: acc[4][2] (f32x16), tile,
 // lane, w, wu, q0, N, KP, cap, R, MODE, the kind flags COS / U8 / L2K with invn, invq, iq_lane, scale, the LDS object s
-// (cnt, thr), my_lists, errflag, gslots, gthr, kk, kmargin (the k rule of topk_dev.h), tg_next[2], dump, ld_dump, and kEpiTgWait = a vmcnt count no larger than the
+// (cnt, thr), my_lists, errflag, gslots, gthr, kk, kmargin (the k rule of topk_dev.h), tg_next[2], dump, ld_dump, kEpiPubEvery (one admission in so many re-derives the chip-wide bound), and kEpiTgWait = a vmcnt count no larger than the
 // number of VMEM ops the wave issues per tile (the thresholds were requested a whole tile ago) and no smaller than the ops
 // it keeps in flight (or the wait drains its prefetches). Ends by clearing acc and re-requesting tg_next.
             // ---------------- epilogue for corpus tile `tile` ----------------
@@ -169,9 +169,10 @@
                                             const size_t i = tb + 4 * (g3 + 8 * gq + 4 * half) + rt;
                                             if (o >= thr[ct] && i < N) {
                                                 // the chip-wide bound is re-derived (the expensive half of a visit) for one
-                                                // admitted candidate in kPubEvery: the bound of a query moves by ~1/KP of
+                                                // admitted candidate in kEpiPubEvery (the including kernel's: kPubEvery, or the
+                                                // screened split filter's own cadence): the bound of a query moves by ~1/KP of
                                                 // itself per admission, a few admissions of lag cost next to nothing
-                                                admitted = admitted || (((uint32_t)i & (kPubEvery - 1)) == 0);
+                                                admitted = admitted || (((uint32_t)i & (kEpiPubEvery - 1)) == 0);
 #ifdef INNR_GEMM_PROBE_COUNT
                                                 atomicAdd(errflag + 10, 1u);
 #endif

@@ -164,6 +164,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 1 : 2) void gemm_filter_ke
     // corpus DMA pieces (1 KiB = two dimension rows of the 16 x 128 stage) this wave issues per K-step
     constexpr int NP = (KIND == kGemmU8) ? 1 : 8 / WAVES;
     constexpr int kEpiTgWait = 8 + NP;  // gemm_epilogue.inc: at most this many VMEM ops of the wave are in flight at a tile end
+    constexpr uint32_t kEpiPubEvery = kPubEvery;
     const float* V = static_cast<const float*>(Vraw);
     const uint8_t* C8 = static_cast<const uint8_t*>(Vraw);
     constexpr int kBQ = 64 * WAVES;

@@ -100,6 +100,71 @@ __global__ __launch_bounds__(256) void pack_corpus_bf16_kernel(const float* __re
     Ab[u] = o;
 }
 
+// a non-negative double rounded UP to float (NaN stays NaN, +inf stays +inf)
+__device__ __forceinline__ float f32_round_up(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = __uint_as_float(__float_as_uint(f) + 1u);
+    return f;
+}
+
+// The largest limb norms of the split filter's corpus copies (the screen margin, api.hip split_screen_scale): out[0] = bits of
+// max_i |vh_i|, out[1] = bits of max_i |vl_i| over the rows i < N, with vh / vl exactly the limbs pack_corpus_bf16_kernel writes
+// (bf16_limb(V[d ldN + row] * rs, 0 / 1), d < D; rowscale as there). One pass over the f32 store, one lane = 4 rows (float4 rows,
+// coalesced like norms_kernel); a row's sums run in double, the square root is rounded up to float. A block maximum, then
+// one atomic max per block and limb on the raw bits (non-negative floats order like their bits; a NaN norm poisons the maximum as in
+// norms_kernel, an infinite one stays infinite: the host then keeps the worst-case margin). out is zeroed by the caller.
+__global__ __launch_bounds__(256) void limb_maxima_kernel(const float* __restrict__ V, size_t ldN, uint32_t N, uint32_t D,
+                                                           const float* __restrict__ rowscale, uint32_t* __restrict__ out) {
+    const size_t i4 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    uint32_t hb = 0, lb = 0;
+    if (i4 < ldN) {
+        float rs[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) rs[c] = (rowscale && i4 + c < N) ? rowscale[i4 + c] : 1.0f;
+        const float4* p = reinterpret_cast<const float4*>(V + i4);
+        const size_t stride = ldN / 4;
+        double sh[4] = {0.0, 0.0, 0.0, 0.0}, sl[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+        for (uint32_t d = 0; d < D; ++d) {
+            const float4 v = p[(size_t)d * stride];
+            const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float xs = x[c] * rs[c];
+                const double h = (double)__uint_as_float((uint32_t)bf16_limb(xs, 0) << 16);
+                const double l = (double)__uint_as_float((uint32_t)bf16_limb(xs, 1) << 16);
+                sh[c] += h * h;
+                sl[c] += l * l;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (i4 + c >= N) continue;
+            const float nh = f32_round_up(sqrt(sh[c])), nl = f32_round_up(sqrt(sl[c]));
+            const uint32_t bh = nh != nh ? 0x7fc00000u : __float_as_uint(nh), bl = nl != nl ? 0x7fc00000u : __float_as_uint(nl);
+            hb = hb > bh ? hb : bh;
+            lb = lb > bl ? lb : bl;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t oh = (uint32_t)__shfl_xor((int)hb, off, 64), ol = (uint32_t)__shfl_xor((int)lb, off, 64);
+        hb = hb > oh ? hb : oh;
+        lb = lb > ol ? lb : ol;
+    }
+    __shared__ uint32_t wmax[2][4];
+    if ((threadIdx.x & 63) == 0) {
+        wmax[0][threadIdx.x >> 6] = hb;
+        wmax[1][threadIdx.x >> 6] = lb;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const uint32_t* w = wmax[threadIdx.x];
+        const uint32_t a = w[0] > w[1] ? w[0] : w[1], b = w[2] > w[3] ? w[2] : w[3];
+        atomicMax(out + threadIdx.x, a > b ? a : b);
+    }
+}
+
 // queries row-major [Q][D] -> Bb; one thread per 16-byte unit
 // l2c (nullable; [Qpad] c_j = C_j - |q_j|^2): the squared-L2 packing, see pack_corpus_bf16_kernel
 // limb: 0 = the rounded values (hi limb), 1 = their lo limbs (the split filter; not with l2c)
@@ -299,6 +364,7 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     // (end of step s+1) is the DMA of step s+2, issued at the top of step s-4: six whole steps of ops from it on.
     constexpr int kEpiTgWait = kSplit ? G::kPerStep * (kBfStages - 2) : 5 * (kBfStages - 3) + 4 + 5;
     static_assert(kEpiTgWait <= 63 && G::kPerStep * (kBfStages - 4) + G::kPerStep - G::kDma <= 63, "vmcnt is 6 bits");
+    constexpr uint32_t kEpiPubEvery = kScreen ? kScreenPubEvery : kPubEvery;  // gemm_epilogue.inc: the publish cadence
     __shared__ GemmBf16Lds<kLoop> s;
     constexpr uint32_t cap = 64 * R;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;

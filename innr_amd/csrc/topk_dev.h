@@ -80,6 +80,15 @@ constexpr uint32_t kSlotMul = INNR_SLOT_MUL;
 #define INNR_PUB_EVERY 16
 #endif
 constexpr uint32_t kPubEvery = INNR_PUB_EVERY;
+// The screened split filter's kernels (kernels_gemm_bf16.h, SCREEN) publish on a cadence of their own: there a visit already
+// costs several memory round trips (the pair path), and a lagging bound costs whole flagged wave tiles, not a direct append.
+// Builds with -DINNR_SCREEN_PUB_EVERY; DESIGN.md 4.4e has the sweep over 16 / 4 / 1 at the C2 shape.
+#ifndef INNR_SCREEN_PUB_EVERY
+#define INNR_SCREEN_PUB_EVERY 4
+#endif
+constexpr uint32_t kScreenPubEvery = INNR_SCREEN_PUB_EVERY;
+static_assert((kPubEvery & (kPubEvery - 1)) == 0 && (kScreenPubEvery & (kScreenPubEvery - 1)) == 0 && kPubEvery && kScreenPubEvery,
+              "the cadences mask a corpus index");
 
 // The chip-wide bound of one query, re-derived from its S = kSlotMul*KP slot values (wave-uniform arguments). Two rules, both
 // certificates, the better one wins:
