@@ -6,6 +6,7 @@ graph clustering) and near-duplicate detection, both without a second copy of th
      each vector's own index is taken out of its list (only the index: an identical vector stays in, at distance 0).
   2. near-duplicates: rows(ids) on the device hands the vectors to batch_range_search as they are -- every vector within a small
      squared distance of each probe, the probe itself included.
+  3. append: the resident corpus grows in place (VerticalBatch.append), and the graph of the grown corpus includes the new vectors.
 
     python examples/knn_graph.py [corpus_size]          (needs a GPU)
 """
@@ -65,6 +66,17 @@ def main(corpus_size: int = 20_000, dim: int = 64, k: int = 8, planted: int = 12
     assert pairs == want, (sorted(pairs), sorted(want))
     assert np.array_equal(vb.rows(ids[:4]), d_probes[:4].cpu().numpy())  # host and device gathers agree
     print("every planted near-duplicate found, nothing else; no copy of the corpus outside the library")
+
+    # ---- 3. the corpus grows in place: a few new vectors, each a near-duplicate of a stored one, and their rows of the graph
+    extra = min(4, corpus_size)
+    twins = np.arange(extra) * (corpus_size // extra)
+    vb.append(vb.rows(twins) + np.float32(1e-3))  # only these rows cross the bus; the handle and the old indices stay
+    assert vb.num_vectors() == corpus_size + extra
+    gi2, _ = B.batch_knn_graph(vb, k, first=corpus_size, count=extra)  # the graph rows of the new vectors ...
+    assert gi2[:, 0].tolist() == twins.tolist()
+    back, _ = B.batch_knn_rows(twins, vb, k)                           # ... and the grown corpus' rows of their twins
+    assert all(corpus_size + j in back[j] for j in range(extra))
+    print(f"appended {extra} vectors in place: the graph of the grown corpus ({vb.num_vectors()} vectors) includes them")
     vb.close()
 
 

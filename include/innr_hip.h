@@ -111,7 +111,8 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * switch of the sharded calls), filter_keep_selection (default 1; 0: innr_batch_knn_filtered_multi and innr_batch_knn_u8_filtered
  * free their selection at the end of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
  * innr_batch_set_copy_budget), scan_max_slots (default 0 = fill the chip: the most wave slots an exact scan is cut into, rounded
- * up to a multiple of 4, so that a wave owns several chunks of a small corpus) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
+ * up to a multiple of 4, so that a wave owns several chunks of a small corpus), mutate_round (default 0 = what fits 256 MiB: the
+ * most rows a staging round of innr_batch_append_rows / innr_batch_update_rows carries; a test switch) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
 const char* innr_last_error(void);
@@ -450,13 +451,62 @@ innr_status innr_batch_gather_rows_dev(innr_batch* b, const uint64_t* d_idx, siz
  * stats: engine = the last round's, queries_fallback and gemm_ms summed over the rounds, candidates_kept their maximum, total_ms
  * the whole call, gather and strip included.
  * Out of scope: u8 code batches (a code row is not an f32 query, and the reference defines no de-quantised search), document
- * corpora, a sharded variant, updating or appending rows, a fused range self-join (compose innr_batch_gather_rows_dev and
+ * corpora, a sharded variant, a fused range self-join (compose innr_batch_gather_rows_dev and
  * innr_batch_range_search_dev), excluding vectors EQUAL to the query. */
 innr_status innr_batch_knn_rows(innr_batch* b, int metric, const uint64_t* idx, size_t Q, size_t k, int exclude_self, int engine,
                                 uint64_t* out_idx, float* out_score, size_t* out_k, innr_knn_stats* stats);
 /* same, d_idx and the outputs resident on the device (innr_batch_knn_dev's conventions) */
 innr_status innr_batch_knn_rows_dev(innr_batch* b, int metric, const uint64_t* d_idx, size_t Q, size_t k, int exclude_self, int engine,
                                     uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats);
+
+/* ---- changing a resident f32 batch in place: append, overwrite and remove rows (an addition: the reference's VerticalBatch is
+ * immutable) ----
+ * The handle, the index base, the copy budget, alpha / offset and the matrix-pipe eligibility stay as they are;
+ * innr_batch_num_vectors reports the new N. `rows` is row-major [n*D], as innr_batch_upload_rowmajor takes it; every value is
+ * copied as a 32-bit word (a NaN's sign and payload, -0.0, denormals and +-inf arrive unchanged).
+ * One contract for the three: after a successful call every entry point of the library answers on this batch exactly as on a
+ * fresh batch uploaded with the final rows -- indices position for position, score bits, every engine. After a failed call the
+ * batch is exactly as before: store, derived state, answers.
+ * Derived state: a call that changes the batch drops EVERYTHING the batch derived from its store -- every INNR_COPY_* kind
+ * (remembered refusals included), the kept selection, the cached norms and their by-products, the dimension variances, the int8
+ * quantisation ranges and the engines' call history. Each is rebuilt by the next call that wants it, under the rules of that
+ * moment: an append followed by a search pays the norms pass and the copy builds again. This is deliberately the simple rule.
+ * Views: a batch must have no live prefix view when it is changed (append and keep move the store, update makes a view's
+ * copies and norms stale). The C ABI cannot see live views; as with "the parent must outlive the view", the caller keeps the
+ * rule. A view handle itself is refused.
+ * Order of the checks, all three: a null batch, a u8 code batch or a prefix view: INNR_E_BAD_ARG; D != the batch's:
+ * INNR_E_DIM_MISMATCH (an empty batch created with D = 0 takes only D = 0 rows; keep has no D); n == 0 (keep: N == 0):
+ * INNR_OK, nothing touched; null rows / idx / mask with work to do: INNR_E_BAD_ARG; the size limit; the index checks.
+ * Out of scope: u8 code batches and document corpora; reserved capacity and amortised growth (every append past the padding
+ * copies the store once); incremental maintenance of norms and filter copies; sharded corpora (a rank's shard may be changed,
+ * the index bases of the other shards and anything cached per communicator are the caller's business); changing a batch through
+ * a view; atomicity against searches issued concurrently from another thread, beyond the context's lock. */
+/* Append: the new rows get local indices N .. N+n-1, the old rows keep theirs. N + n <= the store's padded width (N rounded up
+ * to 256): the rows are transposed into the zero padding in place, nothing is allocated. Otherwise a new store of
+ * round_up(N + n, 256) columns is allocated and zeroed, the old block copied across on the device, the rows transposed in, and
+ * the old store freed after the stream is synchronised: the call needs the old and the new store at once, a failed hipMalloc is
+ * INNR_E_OOM. N + n beyond the u32 index limit of a batch: INNR_E_UNSUPPORTED. The host entry point stages the rows in the
+ * context's workspace, at most 256 MiB at a time. */
+innr_status innr_batch_append_rows(innr_batch* b, const float* rows, size_t n, size_t D);
+/* same, d_rows resident on the device; the call synchronises with the host (the allocation) */
+innr_status innr_batch_append_rows_dev(innr_batch* b, const float* d_rows, size_t n, size_t D);
+/* Update: row idx[j] becomes rows[j*D ..]. Indices are GLOBAL (index base + local index, as in innr_batch_gather_rows), in any
+ * order. Nothing is reallocated. Every index is checked on the device before anything is written -- against [base, base + N) and,
+ * through an N-bit bitmap in the context's workspace, against the other indices of the call: an index outside the range, or one
+ * that occurs twice in one call, is INNR_E_BAD_ARG with a message naming which of the two it was (duplicates are refused, not
+ * "last wins": the same inputs give the same bits). The host entry point stages indices and rows in rounds of at most 256 MiB;
+ * the bitmap spans all rounds, so nothing is written before every index has been checked. */
+innr_status innr_batch_update_rows(innr_batch* b, const uint64_t* idx, const float* rows, size_t n, size_t D);
+/* same, d_idx and d_rows resident on the device; the call synchronises with the host (the check's flag) */
+innr_status innr_batch_update_rows_dev(innr_batch* b, const uint64_t* d_idx, const float* d_rows, size_t n, size_t D);
+/* Keep (remove): the rows with mask[i] != 0 survive, in index order; row i's new local index is the number of kept rows below
+ * it. mask: N bytes. *out_n (may be null) receives the new N. The kept rows are compacted into a new store of round_up(N', 256)
+ * columns by the selection's count and gather kernels (old and new store exist at once; a failed hipMalloc is INNR_E_OOM); the
+ * memory of the removed rows is given back. A mask that keeps every row changes nothing and drops nothing; a mask that keeps
+ * none leaves an N = 0 batch of the same D. The host entry point stages the mask in the context's workspace. */
+innr_status innr_batch_keep_rows(innr_batch* b, const uint8_t* mask, size_t* out_n);
+/* same, d_mask resident on the device; the call synchronises with the host (the count, the allocation) */
+innr_status innr_batch_keep_rows_dev(innr_batch* b, const uint8_t* d_mask, size_t* out_n);
 
 /* ---- pairwise surface kept on the host: called per PAIR by graph indexes, so a kernel
  * launch cannot pay for itself. Plain host functions in the reference's portable arithmetic order. ------------ */

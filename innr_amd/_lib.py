@@ -149,6 +149,12 @@ SIGNATURES = {
     "innr_batch_gather_rows_dev": (C.c_int, [_vp, _vp, _sz, _vp]),
     "innr_batch_knn_rows": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
     "innr_batch_knn_rows_dev": (C.c_int, [_vp, C.c_int, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _szp, C.POINTER(KnnStats)]),
+    "innr_batch_append_rows": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "innr_batch_append_rows_dev": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "innr_batch_update_rows": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
+    "innr_batch_update_rows_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
+    "innr_batch_keep_rows": (C.c_int, [_vp, _vp, _szp]),
+    "innr_batch_keep_rows_dev": (C.c_int, [_vp, _vp, _szp]),
     "innr_merge_topk_dev":(C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "innr_dot_f32": (C.c_float, [_vp, _vp, _sz]),
     "innr_cosine_f32": (C.c_float, [_vp, _vp, _sz]),

@@ -9,7 +9,8 @@ Vec<f32> <-> numpy float32 arrays; `_into` variants refill a caller-owned Python
 
 Additions (the reference has no multi-query API; parity = "the reference called in a loop"):
   batch_knn_dot_multi / batch_knn_cosine_multi / batch_knn_multi / batch_knn_adaptive_multi;
-  search by stored vector: VerticalBatch.rows, batch_knn_rows, batch_knn_graph.
+  search by stored vector: VerticalBatch.rows, batch_knn_rows, batch_knn_graph;
+  changing a resident batch in place: VerticalBatch.append, update_rows, keep, remove.
 
 Every computation runs on the GPU through include/innr_hip.h; nothing here computes scores on the CPU.
 """
@@ -162,6 +163,98 @@ class VerticalBatch(_lib.BatchMemoryMixin):
         out = np.empty((ids.size, self._d), dtype=np.float32)
         check(load().innr_batch_gather_rows(self._h, _vp(ids) if ids.size else None, ids.size, _vp(out) if out.size else None))
         return out
+
+    # ---- changing the batch in place (innr_batch_append_rows / _update_rows / _keep_rows) --------------------
+    # After each of them the batch answers as a fresh batch of the final rows would; everything it had derived from its store
+    # (filter copies, norms, the kept selection) is dropped and rebuilt by the next call that wants it.
+    def _before_change(self, what: str) -> None:
+        if getattr(self, "_parent", None) is not None:
+            raise _lib.InnrError(_lib.E_BAD_ARG, f"{what}: a prefix view cannot be changed")
+        if any(getattr(v, "_h", None) for v in list(getattr(self, "_views", ()))):
+            raise _lib.InnrError(_lib.E_BAD_ARG, f"{what}: the batch has an open prefix view (close it first)")
+
+    def _changed(self) -> None:
+        self._n = int(load().innr_batch_num_vectors(self._h))
+        self._host = None
+
+    def _rows_arg(self, rows, what: str):
+        """(pointer or None, n, torch tensor or array kept alive) of row-major rows [n][dimension]"""
+        if hasattr(rows, "is_cuda") and rows.is_cuda:
+            import torch
+            t = rows.to(torch.float32).contiguous()
+            t = t.reshape(-1, self._d) if self._d else t.reshape(t.shape[0] if t.dim() else 0, 0)
+            return (C.c_void_p(t.data_ptr()) if t.numel() else None), int(t.shape[0]), t
+        a = _f32(rows)
+        if self._d:
+            if a.size % self._d:
+                raise InnrPanic(f"{what}: {a.size} values are no whole number of rows of dimension {self._d}")
+            a = a.reshape(-1, self._d)
+        elif a.ndim != 2 or a.shape[1] != 0:
+            raise InnrPanic(f"{what}: rows of a batch of dimension 0 must have shape (n, 0)")
+        return (_vp(a) if a.size else None), int(a.shape[0]), a
+
+    def append(self, rows) -> None:
+        """The rows (row-major (n, dimension): NumPy, or a CUDA tensor, which stays on the device) become vectors
+        num_vectors() .. num_vectors() + n - 1; the others keep their indices. In place while the store's padding has room,
+        else the store is copied once into a larger one."""
+        self._before_change("append")
+        dev = hasattr(rows, "is_cuda") and rows.is_cuda
+        p, n, keep = self._rows_arg(rows, "append")
+        if dev:
+            self._ctx.bind_torch_stream()
+        fn = load().innr_batch_append_rows_dev if dev else load().innr_batch_append_rows
+        check(fn(self._h, p, n, self._d))
+        self._changed()
+
+    def update_rows(self, indices, rows) -> None:
+        """Vector indices[j] (GLOBAL index, any order) becomes rows[j]. An index outside the batch, or one named twice in a call,
+        raises InnrError and nothing is written. NumPy arrays, or CUDA tensors (int64 indices), which stay on the device."""
+        self._before_change("update_rows")
+        dev = hasattr(rows, "is_cuda") and rows.is_cuda
+        p, n, keep = self._rows_arg(rows, "update_rows")
+        if dev:
+            import torch
+            ids = indices.to(device=rows.device, dtype=torch.int64).reshape(-1).contiguous()
+            if ids.numel() != n:
+                raise InnrPanic(f"update_rows: {ids.numel()} indices for {n} rows")
+            self._ctx.bind_torch_stream()
+            check(load().innr_batch_update_rows_dev(self._h, C.c_void_p(ids.data_ptr()) if n else None, p, n, self._d))
+        else:
+            ids = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+            if ids.size != n:
+                raise InnrPanic(f"update_rows: {ids.size} indices for {n} rows")
+            check(load().innr_batch_update_rows(self._h, _vp(ids) if n else None, p, n, self._d))
+        self._changed()
+
+    def keep(self, mask) -> int:
+        """Only the vectors with mask[i] != 0 stay (mask: num_vectors() bytes or bools, NumPy or a CUDA tensor), in index order:
+        vector i's new local index is the number of kept vectors below it. Returns the new num_vectors(); the memory of the
+        removed vectors is given back. A mask that keeps everything changes nothing."""
+        self._before_change("keep")
+        out_n = C.c_size_t(0)
+        if hasattr(mask, "is_cuda") and mask.is_cuda:
+            import torch
+            m = (mask != 0).to(torch.uint8).reshape(-1).contiguous()
+            if m.numel() != self._n:
+                raise InnrPanic(f"keep: a mask of {m.numel()} entries for {self._n} vectors")
+            self._ctx.bind_torch_stream()
+            check(load().innr_batch_keep_rows_dev(self._h, C.c_void_p(m.data_ptr()) if self._n else None, C.byref(out_n)))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+            if m.size != self._n:
+                raise InnrPanic(f"keep: a mask of {m.size} entries for {self._n} vectors")
+            check(load().innr_batch_keep_rows(self._h, _vp(m) if self._n else None, C.byref(out_n)))
+        self._changed()
+        return self._n
+
+    def remove(self, indices) -> int:
+        """keep() with a mask built on the host: the vectors named by GLOBAL index (duplicates allowed) go, the others stay."""
+        ids = np.asarray(indices, dtype=np.int64).reshape(-1) - self._base
+        if ids.size and (ids.min() < 0 or ids.max() >= self._n):
+            raise IndexError(f"remove: an index lies outside [{self._base}, {self._base + self._n})")
+        mask = np.ones(self._n, dtype=np.uint8)
+        mask[ids] = 0
+        return self.keep(mask)
 
     def _local_index(self, vec_idx: int) -> int:
         i = int(vec_idx)

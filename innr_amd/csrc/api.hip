@@ -45,6 +45,7 @@ static const TuneName kTuneNames[] = {
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
     {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"split_screen_worst_case", &innr_tuning::split_screen_worst_case}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
     {"copy_budget_mib", &innr_tuning::copy_budget_mib}, {"scan_max_slots", &innr_tuning::scan_max_slots},
+    {"mutate_round", &innr_tuning::mutate_round},
 };
 static void tuning_from_env(innr_tuning* t) {
     for (const TuneName& n : kTuneNames) {
@@ -67,7 +68,7 @@ static std::vector<DevBuf*> workspace_bufs(innr_ctx* c) {
             &c->redo[1].q, &c->redo[1].idx, &c->redo[1].sc, &c->redo[1].map, &c->redo[1].qn, &c->kmargin, &c->i8s_prog,
             &c->cmpl.q, &c->cmpl.idx, &c->cmpl.sc, &c->cmpl.map, &c->cmpl.qn, &c->flt_in, &c->flt_mask, &c->flt_scan,
             &c->rs_cnt, &c->rs_bits, &c->rs_tot, &c->rs_thr, &c->rs_off, &c->adp_scan, &c->adp_list,
-            &c->rows_q, &c->rows_stage, &c->rows_io, &c->rows_flag};
+            &c->rows_q, &c->rows_stage, &c->rows_io, &c->rows_flag, &c->rows_bits, &c->rows_map};
 }
 
 // kernel_of(Inst) of the recorded families whose kernels this file owns (api_internal.h: Inst, launch_kernel)
@@ -241,12 +242,12 @@ static uint64_t budget_from_option(const innr_ctx* ctx) {
     return (mib < 0 || mib >= (1L << 43)) ? UINT64_MAX : (uint64_t)mib << 20;
 }
 
-static innr_status alloc_batch(innr_ctx* ctx, size_t N, size_t D, innr_batch** out) {
+innr_status alloc_batch(innr_ctx* ctx, size_t N, size_t D, innr_batch** out) {
     if (!ctx || !out) {
         set_error("null ctx/out");
         return INNR_E_BAD_ARG;
     }
-    if (N >= 0xFFFFFFFFull - 256 || D > 0x7FFFFFFFull) {
+    if (N >= kMaxBatchN || D > 0x7FFFFFFFull) {
         set_error("corpus shard too large for u32 device indices (N=%zu, D=%zu)", N, D);
         return INNR_E_UNSUPPORTED;
     }
@@ -276,6 +277,13 @@ static innr_status alloc_batch(innr_ctx* ctx, size_t N, size_t D, innr_batch** o
     }
     *out = b;
     return INNR_OK;
+}
+
+hipError_t transpose_rows_into(innr_ctx* c, const float* d_rows, size_t n, size_t D, float* V, size_t ldN, size_t col0) {
+    if (n == 0 || D == 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 31) / 32), (unsigned)((D + 31) / 32));
+    transpose_rows_kernel<<<grid, 256, 0, c->stream>>>(d_rows, (uint32_t)n, (uint32_t)D, V, ldN, col0);
+    return hipGetLastError();
 }
 
 static innr_status ensure_norms(innr_batch* b) {
@@ -1886,9 +1894,7 @@ innr_status innr_batch_upload_rowmajor(innr_ctx* ctx, const float* rows, size_t 
             const size_t n = std::min(blk, N - i0);
             e = copy_in(ctx, stage, rows + i0 * D, n * D * sizeof(float));
             if (e != hipSuccess) break;
-            dim3 grid((unsigned)((n + 31) / 32), (unsigned)((D + 31) / 32));
-            transpose_rows_kernel<<<grid, 256, 0, ctx->stream>>>(stage, (uint32_t)n, (uint32_t)D, b->V, b->ldN, i0);
-            e = hipGetLastError();
+            e = transpose_rows_into(ctx, stage, n, D, b->V, b->ldN, i0);
             if (e == hipSuccess) e = ctx_sync(ctx);
         }
         (void)hipFree(stage);
@@ -3799,18 +3805,18 @@ static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
     }
     b->fsel_mask_bytes = mask_bytes;
     b->fsel_map_bytes = map_bytes;
-    const size_t nchunks = b->ldN / kSelChunk;
-    const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
-    const size_t D = b->D;
-    const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
-    const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
-    if (b->C8)
+    if (b->C8) {
+        const size_t nchunks = b->ldN / kSelChunk;
+        const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
+        const size_t D = b->D;
+        const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
+        const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
         select_gather_u8_kernel<<<grid, 256, 0, c->stream>>>(b->C8, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->C8,
                                                              s->ldN, b->fsel_map, slab);
-    else
-        select_gather_kernel<<<grid, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->V, s->ldN,
-                                                          b->fsel_map, slab);
-    INNR_HIP_CHECK(hipGetLastError());
+        INNR_HIP_CHECK(hipGetLastError());
+    } else {
+        INNR_TRY(gather_passing(b, s->V, s->ldN, b->fsel_map));
+    }
     INNR_HIP_CHECK(hipMemcpyAsync(b->fsel_mask, c->flt_mask.p, b->ldN, hipMemcpyDeviceToDevice, c->stream));
     ++b->fsel_builds;
     *built = true;
@@ -4104,14 +4110,9 @@ innr_status innr_batch_get_copy_budget(const innr_batch* b, uint64_t* bytes) {
     return INNR_OK;
 }
 
-innr_status innr_batch_release_copies(innr_batch* b, uint32_t mask) {
-    if (!b) {
-        set_error("batch is null");
-        return INNR_E_BAD_ARG;
-    }
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    INNR_HIP_CHECK(ctx_sync(c));  // nothing queued may still read what is freed below
+// the kinds of `mask` freed and their refusals forgotten (the stream is synchronised: nothing queued reads them);
+// innr_batch_release_copies, and invalidate_derived for every kind
+static void release_copy_kinds(innr_batch* b, uint32_t mask) {
     if (mask & INNR_COPY_BF16_DOT) mask |= INNR_COPY_BF16LO_DOT;  // the split filter needs the pair
     if (mask & INNR_COPY_BF16_COS) mask |= INNR_COPY_BF16LO_COS;
     for (int k = 0; k < kCopyKinds; ++k) {
@@ -4125,6 +4126,17 @@ innr_status innr_batch_release_copies(innr_batch* b, uint32_t mask) {
         cc.refused = false;  // "try again": the next call that wants the copy asks the memory rule anew (weak is about the data: kept)
     }
     if (mask & INNR_COPY_SELECTION) free_selection(b);
+}
+
+innr_status innr_batch_release_copies(innr_batch* b, uint32_t mask) {
+    if (!b) {
+        set_error("batch is null");
+        return INNR_E_BAD_ARG;
+    }
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(ctx_sync(c));  // nothing queued may still read what is freed below
+    release_copy_kinds(b, mask);
     return INNR_OK;
 }
 
@@ -4276,6 +4288,51 @@ innr_status innr_merge_topk_dev(innr_ctx* ctx, int metric, const uint64_t* d_idx
 }
 
 }  // extern "C"
+
+// ---- what the entry points that change a batch in place (mutate.hip) take from this unit ---------------------
+namespace innr {
+
+innr_status count_mask(innr_batch* b, const uint8_t* d_mask, size_t* npass) {
+    bool same = false;
+    return filter_mask(b, d_mask, npass, &same);
+}
+
+// (count_mask or filter_mask ran on this batch: c->flt_mask, and the chunk offsets behind the counts in c->flt_scan)
+innr_status gather_passing(innr_batch* b, float* S, size_t ldS, uint32_t* map) {
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kSelChunk;
+    const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
+    const size_t D = b->D;
+    const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
+    const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
+    select_gather_kernel<<<grid, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, S, ldS, map, slab);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
+void invalidate_derived(innr_batch* b) {
+    release_copy_kinds(b, INNR_COPY_ALL);  // every copy[] kind and the kept selection
+    for (CorpusCopy& cc : b->copy) cc.weak = false;  // (about the data that was: a release keeps it, new rows do not)
+    if (b->norms) (void)hipFree(b->norms);
+    if (b->invn) (void)hipFree(b->invn);
+    if (b->sqn) (void)hipFree(b->sqn);
+    if (b->max_norm_bits) (void)hipFree(b->max_norm_bits);
+    b->norms = b->invn = b->sqn = nullptr;
+    b->max_norm_bits = nullptr;
+    b->aux_bytes = 0;
+    b->norms_ready = false;
+    b->max_norm = 0.0f;
+    b->dimvar.clear();
+    b->i8_raw = b->i8_norm = innr_batch::I8Range();
+    b->i8l2_R = 0;
+    b->i8l2_nmax = 0.0f;
+    b->i8_weak_skips = 0;
+    b->screen_share[0] = b->screen_share[1] = 0.0f;
+    b->screen_skips[0] = b->screen_skips[1] = 0;
+    b->auto_small_calls = 0;
+}
+
+}  // namespace innr
 
 // =====================================================================================================================
 // Range search: every vector within a per-query threshold (innr_batch_range_search)

@@ -1,6 +1,6 @@
 // api_internal.h -- what more than one translation unit of the library shares: the context and its workspace, the launch record
 // and dispatch, the corpus handles, the entry guard, and the host functions that cross a unit boundary. The units: api.hip (the C
-// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), rows.hip (search by stored vector),
+// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), rows.hip (search by stored vector), mutate.hip (changing a batch in place),
 // comm.hip (the multi-GPU layer), sort_full.hip.
 // Nothing here may depend on INNR_TEST_HOOKS: every object but api.o is linked into the product library and the hook library
 // alike, so the struct layouts must be the same in every object.
@@ -75,6 +75,7 @@ struct innr_tuning {
     long split_screen_worst_case = 0;  // ... the screen's margin by the worst-case formula alone (every lo limb at half a last place), never from the limbs' measured norms (A/B, tests)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
+    long mutate_round = 0;       // innr_batch_append_rows, innr_batch_update_rows: at most this many rows per staging round (tests); 0 = what fits 256 MiB
     long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip
 };
 
@@ -190,6 +191,8 @@ struct innr_ctx {
     DevBuf rows_stage; // ... with exclude_self: the inner search's [round][k + 1] indices, then scores
     DevBuf rows_io;    // ... and innr_batch_gather_rows, host-memory entry points: indices in, results out
     DevBuf rows_flag;  // ... the gathers' own error word (an index outside the batch): every entry point clears c->flags
+    DevBuf rows_bits;  // innr_batch_update_rows (mutate.hip): one bit per vector of the batch, set by the index it was named by; zeroed per call
+    DevBuf rows_map;   // innr_batch_keep_rows: old column of every kept row (the selection gather writes it; not read)
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
     size_t screen_q = 0, screen_qpad = 0;  // queries of the last screen margins written to kmargin + Qpad (0: none yet; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
@@ -360,6 +363,22 @@ innr_status emit_results(innr_ctx* c, const uint64_t* sel, size_t KP, size_t Q, 
 // rows (out[0, ldN): the bits innr_batch_scores gives on a prefix view of W dimensions), and the single-workgroup exclusive scan
 innr_status l2_prefix_scores(innr_batch* b, const float* d_query, size_t W, float* out);
 innr_status exclusive_scan_u32(innr_ctx* c, const uint32_t* counts, uint32_t n, uint32_t* offsets, uint32_t* total);
+// api.hip, for the entry points that change a batch in place (mutate.hip):
+// a new f32 batch of N vectors with a zeroed store of round_up(N, 256) columns x round_up(D, 32) rows (N beyond kMaxBatchN:
+// INNR_E_UNSUPPORTED; a failed hipMalloc: INNR_E_OOM) -- a mutation takes its store and frees the rest
+constexpr size_t kMaxBatchN = 0xFFFFFFFFull - 256;  // a batch holds fewer vectors than this (u32 device indices)
+innr_status alloc_batch(innr_ctx* ctx, size_t N, size_t D, innr_batch** out);
+// rows[n][D] (device) into columns col0 .. col0 + n of a dimension-major store (transpose_rows_kernel, the upload's launch): only
+// d < D, i < n is written
+hipError_t transpose_rows_into(innr_ctx* c, const float* d_rows, size_t n, size_t D, float* V, size_t ldN, size_t col0);
+// the selection's count (select_mask_kernel + scan: d_mask normalised into c->flt_mask, offsets in c->flt_scan, *npass; one
+// synchronise) and its gather (select_gather_kernel) of the passing columns of b into S, in index order; map[npass] is written
+innr_status count_mask(innr_batch* b, const uint8_t* d_mask, size_t* npass);
+innr_status gather_passing(innr_batch* b, float* S, size_t ldS, uint32_t* map);
+// THE list of what a batch derives from its store, forgotten: every copy[] kind (as innr_batch_release_copies frees them, a
+// remembered refusal included), the kept selection, the norms and their by-products, the dimension variances, the int8 ranges
+// and the engines' call history. The caller has synchronised the stream. Each is rebuilt by the next call that wants it.
+void invalidate_derived(innr_batch* b);
 // sort_full.hip
 hipError_t full_sort_scratch_bytes(size_t n, size_t* bytes);
 size_t full_topk_out_capacity(size_t k);  // keys the `sorted` buffer must hold for the best k (the next power of two)

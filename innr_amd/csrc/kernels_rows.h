@@ -8,21 +8,9 @@
 // writes zeros (rows.hip reports it at the end of the call). Both give the same bits.
 #pragma once
 
-#include "common.h"
+#include "rows_dev.h"  // kRowsTile, kRowsNone, rows_local: shared with the scatter of kernels_mutate.h
 
 namespace innr {
-
-constexpr int kRowsTile = 32;               // indices and dimensions per LDS tile of the store gather
-constexpr uint32_t kRowsNone = 0xFFFFFFFFu;  // local index of a slot with nothing to load (N < 2^32 - 1: never a vector)
-
-// global index -> local, kRowsNone (and *bad) when it is not this batch's
-__device__ __forceinline__ uint32_t rows_local(uint64_t g, uint64_t base, uint32_t N, uint32_t* bad) {
-    if (g < base || g - base >= (uint64_t)N) {
-        *bad = 1u;
-        return kRowsNone;
-    }
-    return (uint32_t)(g - base);
-}
 
 // out[j*D + d] = V[d*ldN + idx[j] - base], j < n, d < D. A block of 32 x 8 threads owns tiles of 32 indices x 32 dimensions: for
 // the loads threadIdx.x runs along the indices (consecutive indices: whole cache lines of a dimension row), for the stores along

@@ -118,6 +118,12 @@ pub mod ffi {
         pub fn innr_batch_gather_rows_dev(b: *mut InnrBatch, d_idx: *const u64, n: usize, d_out: *mut f32) -> c_int;
         pub fn innr_batch_knn_rows(b: *mut InnrBatch, metric: c_int, idx: *const u64, q: usize, k: usize, exclude_self: c_int, engine: c_int, out_idx: *mut u64, out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
         pub fn innr_batch_knn_rows_dev(b: *mut InnrBatch, metric: c_int, d_idx: *const u64, q: usize, k: usize, exclude_self: c_int, engine: c_int, d_out_idx: *mut u64, d_out_score: *mut f32, out_k: *mut usize, stats: *mut InnrKnnStats) -> c_int;
+        pub fn innr_batch_append_rows(b: *mut InnrBatch, rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_append_rows_dev(b: *mut InnrBatch, d_rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_update_rows(b: *mut InnrBatch, idx: *const u64, rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_update_rows_dev(b: *mut InnrBatch, d_idx: *const u64, d_rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_keep_rows(b: *mut InnrBatch, mask: *const u8, out_n: *mut usize) -> c_int;
+        pub fn innr_batch_keep_rows_dev(b: *mut InnrBatch, d_mask: *const u8, out_n: *mut usize) -> c_int;
         pub fn innr_dot_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_cosine_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_l2sq_f32(a: *const f32, b: *const f32, n: usize) -> f32;
@@ -319,6 +325,33 @@ pub mod batch {
             let mut out = vec![0.0f32; indices.len() * self.dimension];
             check(unsafe { ffi::innr_batch_gather_rows(self.h, indices.as_ptr(), indices.len(), out.as_mut_ptr()) });
             out
+        }
+        // ---- changing the batch in place (innr_batch_append_rows / _update_rows / _keep_rows). `&mut self`: a PrefixBatch borrows
+        // the batch, so none is alive here -- the rule the C ABI leaves to its caller. Everything derived from the store is dropped.
+        fn changed(&mut self) {
+            self.num_vectors = unsafe { ffi::innr_batch_num_vectors(self.h) };
+            self.host = Default::default();
+        }
+        /// `rows` (row-major, a whole number of rows) become vectors `num_vectors() ..`; the others keep their indices
+        pub fn append(&mut self, rows: &[f32]) {
+            let n = if self.dimension == 0 { 0 } else { rows.len() / self.dimension };
+            assert_eq!(rows.len(), n * self.dimension, "rows.len() is no multiple of the dimension");
+            check(unsafe { ffi::innr_batch_append_rows(self.h, rows.as_ptr(), n, self.dimension) });
+            self.changed();
+        }
+        /// vector `indices[j]` (GLOBAL index, any order, no duplicates) becomes `rows[j * dimension ..]`
+        pub fn update_rows(&mut self, indices: &[u64], rows: &[f32]) {
+            assert_eq!(rows.len(), indices.len() * self.dimension);
+            check(unsafe { ffi::innr_batch_update_rows(self.h, indices.as_ptr(), rows.as_ptr(), indices.len(), self.dimension) });
+            self.changed();
+        }
+        /// only the vectors with `mask[i] != 0` stay, in index order; returns the new `num_vectors()`
+        pub fn keep(&mut self, mask: &[u8]) -> usize {
+            assert_eq!(mask.len(), self.num_vectors);
+            let mut n = 0usize;
+            check(unsafe { ffi::innr_batch_keep_rows(self.h, mask.as_ptr(), &mut n) });
+            self.changed();
+            n
         }
         /// k-NN of vectors the batch holds (innr_batch_knn_rows): query j = vector `indices[j]` (global). `exclude_self`: the best
         /// min(k, N - 1) of all vectors except `indices[j]` itself; otherwise what `batch_knn_multi` gives for the gathered rows.
