@@ -43,7 +43,7 @@ static const TuneName kTuneNames[] = {
     {"i8_slices_per_cu", &innr_tuning::i8_slices_per_cu}, {"i8_no_small", &innr_tuning::i8_no_small},
     {"i8_no_small4", &innr_tuning::i8_no_small4}, {"i8_small_max_q", &innr_tuning::i8_small_max_q},
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
-    {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"split_screen_worst_case", &innr_tuning::split_screen_worst_case}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
+    {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"split_screen_worst_case", &innr_tuning::split_screen_worst_case}, {"split_seed_rows", &innr_tuning::split_seed_rows}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
     {"copy_budget_mib", &innr_tuning::copy_budget_mib}, {"scan_max_slots", &innr_tuning::scan_max_slots},
     {"mutate_round", &innr_tuning::mutate_round},
 };
@@ -76,6 +76,7 @@ template <int KIND, int RR, int MODE, int WV> constexpr auto kernel_of(Inst<kLau
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmBf16, RR, MODE, 1>) { return &gemm_bf16_filter_kernel<RR, MODE, 1>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchGemmSplit, RR, MODE, 3>) { return &gemm_bf16_filter_kernel<RR, MODE, 3>; }
 // ... the same record's screened form (MODE 0: hi.hi K-loop, lo products where a wave can hit; launch_gemm_split chooses)
+template <int RR> constexpr auto kernel_of(Inst<kLaunchSplitSeed, RR, 3, 3>) { return &gemm_bf16_filter_kernel<RR, 3, 3>; }
 template <int RR> constexpr auto screened_kernel_of(Inst<kLaunchGemmSplit, RR, 0, 3>) { return &gemm_bf16_filter_kernel<RR, 0, 3, 1>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8One, RR, MODE>) { return &gemm_i8h_filter_kernel<RR, MODE>; }
 template <int RR, int MODE> constexpr auto kernel_of(Inst<kLaunchI8Two, RR, MODE>) { return &gemm_i8_filter_kernel<RR, MODE>; }
@@ -541,16 +542,23 @@ static innr_status make_kmargin(innr_ctx* c, ScoreSpace kind, float err_scale, c
 
 // ---- exact re-score + proof of the selected lists (c->sel [Q][KP], c->sel_cnt [Q]) ----
 // f32 corpus (rescore_kernel); qaux: C_j in the squared-L2 space, eq: per-query bounds instead of err_scale (int8 filter)
+// tight: the caller's filter is the split filter or the f32 kernel, whose E is a small fraction of the gaps between the best scores
+// (split filter at the C2 shape: E ~ 0.09 against a gap of ~1.0 between the 10th and the 17th best of 10M rows). A short answer
+// (k <= 12) is then nearly always proven by the best 16 candidates, and every candidate less is D sector reads of the
+// dimension-major store less: the progressive rounds begin with 16. The bf16 / int8 filters (E 1.5 .. 2.0 there) would only add
+// a serial round and keep 32. flag word kRescoreCountWord counts the candidates re-scored (read by a test hook).
+constexpr uint32_t kRescoreCountWord = 40;
 static innr_status launch_rescore(innr_batch* b, ScoreSpace space, const float* dQ, size_t Q, const float* qaux, uint32_t KP,
                                   size_t kout, float err_scale, uint64_t* d_out_idx, float* d_out_score, uint32_t* fallback,
-                                  const float* eq, bool early, const uint32_t* gthr) {
+                                  const float* eq, bool early, const uint32_t* gthr, bool tight = false) {
     innr_ctx* c = b->ctx;
+    const uint32_t r0 = (tight && kout <= 12) ? 16u : 32u;
     const auto launch = [&](auto met) {
         with_rk(KP, [&](auto rk) {
             rescore_kernel<decltype(met)::value, decltype(rk)::value><<<(unsigned)Q, 64, 0, c->stream>>>(
                 b->V, b->ldN, (uint32_t)b->D, dQ, b->norms, c->q_norm.as<float>(), qaux, c->sel.as<uint64_t>(),
                 c->sel_cnt.as<uint32_t>(), KP, (uint32_t)kout, err_scale, b->index_base, d_out_idx, d_out_score, fallback, eq, early,
-                gthr);
+                gthr, r0, c->flags.as<uint32_t>() + kRescoreCountWord);
         });
     };
     with_space(space, launch);
@@ -1474,6 +1482,52 @@ static innr_status launch_gemm_split(innr_batch* b, const GemmPlan& p, size_t nr
     return INNR_OK;
 }
 
+// ---- the split filter's own seeder: its first chip-wide bounds from a prefix pass on the matrix pipe ----
+// The exact seeder below costs exact-engine time per prefix row (the C2 shape: 0.30 ms for 2048 rows) and its bound has to be
+// exact only because the f32 scan makes it so: the k rule needs a VALID lower bound of the k-th best score, no more. The split
+// kernel in MODE 3 scores a prefix P of whole tiles with the filter's own arithmetic and keeps the best score of every group of 32
+// rows; the k-th largest of a query's P / 32 group maxima, less 2E, is such a bound (split_seed_kernel), and a prefix eight times
+// as long costs a fifth of the scan. A longer prefix also starts the bounds higher: a one-pass top-k admits about k ln(N / n0)
+// rows per query behind a seed from n0 rows, and every admission is a flagged wave tile of the screened kernel.
+// Rows: split_seed_rows (0: kSplitSeedRows), clamped to a multiple of 1024 within N / 32 (seeding_on's rule: the corpus is at least
+// 32 prefixes; P / 128 is then a multiple of 8, the kernel's block map) and to kSeedMaxGroups groups. 0 = the exact seeder: the
+// option says so (-1), gemm_seed_n or gemm_no_seed is set, the k rule is off, lists beyond 128, or fewer than k groups (with
+// exactly k the bound is the smallest group maximum: weak, and as valid as any; the default prefix has 512 groups for k <= 112).
+constexpr size_t kSplitSeedRows = 16384;
+static size_t split_seed_rows(const innr_batch* b, uint32_t KP, size_t kout) {
+    const innr_tuning& t = b->ctx->tune;
+    if (t.split_seed_rows < 0 || t.gemm_seed_n != 0 || t.gemm_no_seed || t.no_k_rule || KP > 128) return 0;
+    size_t P = t.split_seed_rows >= 1024 ? (size_t)t.split_seed_rows : kSplitSeedRows;
+    P = std::min(P, std::min(b->N / 32, (size_t)kSeedMaxGroups * 32)) / 1024 * 1024;
+    return P / 32 >= kout ? P : 0;
+}
+// seeds of the call's queries at *sd [p.Qpad] (c->seed_score), the group maxima as order keys at c->seed_idx [P / 32][p.Qpad].
+// The queries are packed (pack_queries_split) and their norms stand in c->q_norm.
+static innr_status seed_split(innr_batch* b, const GemmPlan& p, int metric, size_t Q, size_t kout, float err_scale, size_t P,
+                              uint32_t** sd) {
+    innr_ctx* c = b->ctx;
+    const CorpusCopy &hi = b->copy[bf16_kind(metric)], &lo = b->copy[bf16_kind(metric, true)];
+    const uint32_t ntiles = (uint32_t)(P / 128), ngroups = (uint32_t)(P / 32);
+    if (hi.nk % kBfLead != 0 || ntiles % 8 != 0 || P > b->N || ngroups > kSeedMaxGroups || kout > ngroups) {
+        set_error("internal: the split seeder's geometry (%zu rows, %u K-steps)", P, hi.nk);
+        return INNR_E_BAD_ARG;
+    }
+    INNR_TRY(c->seed_idx.ensure((size_t)ngroups * p.Qpad * sizeof(uint32_t)));
+    INNR_TRY(c->seed_score.ensure(p.Qpad * sizeof(uint32_t)));
+    // one tile per block, the kernel's own block -> (slice, query tile) map: slices = tiles, a multiple of 8
+    const Inst<kLaunchSplitSeed, 6, 3, 3> inst;
+    launch_kernel(c, inst, {p.nqt * ntiles, 64 * kBfWaves, 0, p.nqt}, hi.p, lo.p, c->q_bf16.as<char>(), ntiles, (uint32_t)P, hi.nk,
+                  p.Qpad, p.nqt, p.qtg, 1u, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.KP, 0u, c->flags.as<uint32_t>(),
+                  (uint32_t*)nullptr, (uint32_t*)nullptr, c->seed_idx.as<float>(), p.Qpad);
+    INNR_HIP_CHECK(hipGetLastError());
+    split_seed_kernel<<<(unsigned)p.Qpad, 64, 0, c->stream>>>(c->seed_idx.as<uint32_t>(), ngroups, (uint32_t)p.Qpad, (uint32_t)Q,
+                                                               (uint32_t)kout, metric == INNR_METRIC_COSINE, err_scale,
+                                                               c->q_norm.as<float>(), c->seed_score.as<uint32_t>());
+    INNR_HIP_CHECK(hipGetLastError());
+    *sd = c->seed_score.as<uint32_t>();
+    return INNR_OK;
+}
+
 // rows of the corpus prefix whose exact top-KP seeds the chip-wide thresholds (INNR_GEMM_SEED_N overrides: tools/seed_ab.py)
 // C2 shape, whole call (tools/seed_ab.py): int8 filter 13.50 / 12.80 / 12.38 / 12.12 / 12.59 ms at 512 / 1024 / 2048 / 4096 / 8192 rows
 // (without seeds 17.5), bf16 filter 16.14 -> 16.00 at 4096; the f32 kernel, whose visits are cheap next to its MFMAs, 107.37 / 107.42 /
@@ -1574,7 +1628,13 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     if (use_split) INNR_TRY(pack_queries_split(b, p, dQ, Q, cos ? c->misc.as<float>() : nullptr));
 
     const uint32_t* seed = nullptr;
-    if (seeding_on(b, use_bf16, Q, p.KP)) {
+    const size_t split_rows = use_split ? split_seed_rows(b, p.KP, kout) : 0;  // the split filter's own seeder, or 0: the exact one
+    if (level == 0) c->split_seed_served = split_rows;
+    if (split_rows) {
+        uint32_t* sd;
+        INNR_TRY(seed_split(b, p, metric, Q, kout, err_scale, split_rows, &sd));
+        seed = sd;
+    } else if (seeding_on(b, use_bf16, Q, p.KP)) {
         uint32_t kseed, *sd;
         INNR_TRY(seed_prefix(b, use_bf16, Q, p.Qpad, p.KP, kout, &kseed, &sd, [&](uint32_t ks, uint64_t* idx, float* sc, size_t rows) {
             return knn_exact_range(b, metric, dQ, b->D, c->q_norm.as<float>(), 0, Q, ks, idx, sc, ScanExt(), rows);
@@ -1636,7 +1696,7 @@ static innr_status knn_mfma(innr_batch* b, int metric, const float* dQ, size_t Q
     INNR_TRY(run_select(c, c->lists.as<uint64_t>(), c->counts.as<uint32_t>(), p.nslices, (uint32_t)p.Qpad, p.cap, p.KP,
                         (uint32_t)Q));
     INNR_TRY(launch_rescore(b, metric_space(metric), dQ, Q, Cj, p.KP, kout, err_scale, d_out_idx, d_out_score, fallback, nullptr,
-                            !c->tune.rescore_all, gthr_bounds(c, p.Qpad, p.KP)));
+                            !c->tune.rescore_all, gthr_bounds(c, p.Qpad, p.KP), /*tight=*/!use_bf16));
 
     std::vector<float> qn_host((use_bf16 || use_split) && !cos ? Q : 0);
     if (!qn_host.empty()) INNR_HIP_CHECK(copy_out(c, qn_host.data(), c->q_norm.p, Q * sizeof(float)));  // (the harvest synchronises)
@@ -2055,6 +2115,51 @@ innr_status innrdbg_split_screen_counts4(innr_batch* b, uint32_t* counts) {
 }
 // the pair path's capacity P (kPairCap) of this build
 int innrdbg_split_pair_cap(void) { return kPairCap; }
+
+// Test hook: the split filter's seeder on its own (seed_split, as knn_mfma calls it): the group maxima of the first `rows` corpus
+// rows as order keys, maxima[g * Q + j] (g < rows / 32: the best split score of rows 128 (g / 4) + 4 i + g % 4, i < 32), and the
+// bounds they seed for the best k, seeds[j]; info[0] = the filter's err_scale (E = err_scale |q| for dot, err_scale for cosine).
+// rows: a multiple of 1024 within N. INNR_E_UNSUPPORTED when the limb copies do not fit.
+innr_status innrdbg_split_seed(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, size_t k, size_t rows,
+                               uint32_t* maxima, uint32_t* seeds, float* info) {
+    if (b && !b->V) return INNR_E_BAD_ARG;
+    if (!b || !queries || !maxima || !seeds || !info || D != b->D || Q == 0 || k == 0 || rows == 0 || rows % 1024 != 0 || rows > b->N ||
+        rows / 32 > kSeedMaxGroups || k > rows / 32 || metric == INNR_METRIC_L2SQ || !metric_ok(metric))
+        return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    const bool cos = metric == INNR_METRIC_COSINE;
+    const GemmPlan p = plan_gemm(b, Q, k, /*waves=*/8);
+    INNR_TRY(ensure_norms(b));
+    if (cos) INNR_TRY(ensure_invnorms(b));
+    bool ok = false;
+    INNR_TRY(ensure_split_corpus(b, metric, &ok));
+    if (!ok) return INNR_E_UNSUPPORTED;
+    INNR_TRY(c->q_row.ensure(Q * D * sizeof(float)));
+    INNR_HIP_CHECK(copy_in(c, c->q_row.p, queries, Q * D * sizeof(float)));
+    INNR_TRY(prep_queries(b, p, c->q_row.as<float>(), Q, cos));
+    INNR_TRY(pack_queries_split(b, p, c->q_row.as<float>(), Q, cos ? c->misc.as<float>() : nullptr));
+    info[0] = split_filter_scale(b, metric);
+    uint32_t* sd = nullptr;
+    INNR_TRY(seed_split(b, p, metric, Q, k, info[0], rows, &sd));
+    INNR_HIP_CHECK(hipMemcpy2DAsync(maxima, Q * sizeof(uint32_t), c->seed_idx.p, p.Qpad * sizeof(uint32_t), Q * sizeof(uint32_t), rows / 32,
+                                    hipMemcpyDeviceToHost, c->stream));
+    INNR_HIP_CHECK(hipMemcpyAsync(seeds, sd, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    INNR_HIP_CHECK(ctx_sync(c));
+    return INNR_OK;
+}
+// ... and the prefix rows it served the context's last INNR_KNN_MFMA first pass with (0: the exact seeder, or none)
+size_t innrdbg_split_seed_served(const innr_batch* b) { return b && b->ctx ? b->ctx->split_seed_served : 0; }
+
+// Test hook: candidates the progressive re-score (rescore_kernel) has re-scored exactly, summed over the queries of every launch
+// since the call's entry cleared the flag words
+innr_status innrdbg_rescored(innr_batch* b, uint32_t* count) {
+    if (!b || !count) return INNR_E_BAD_ARG;
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(hipMemcpy(count, c->flags.as<uint32_t>() + kRescoreCountWord, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return INNR_OK;
+}
 
 // Test hook: what the screen margin was made of. maxima[0] / [1] = the largest hi / lo limb norm of the batch's split pair of
 // `metric` (CorpusCopy::limb_max; -1: not computed), info[0] = max_norm; margins[0 .. n) = the margins of the context's last

@@ -72,6 +72,7 @@ struct innr_tuning {
     long no_split_filter = 0;    // INNR_KNN_MFMA dot / cosine: filter on the f32 kernel, never the split-bf16 one (A/B, tests)
     long split_min_q = 0;        // ... smallest batch the split-bf16 filter takes; 0 = the measured crossover (kSplitMinQ)
     long no_split_screen = 0;    // ... 1: its full three-product K-loop, never the hi.hi loop with screened corrections; -1: always the screened loop; 0: by list length, batch size and the share of wave tiles the batch's last screened call corrected (A/B, tests); lists up to 64 beyond 2^20 padded queries always take the full loop (kPairMaxQpad)
+    long split_seed_rows = 0;    // ... rows of the corpus prefix whose split scores (the seeder, MODE 3 of the split kernel) seed its chip-wide bounds under the k rule; 0 = the default (kSplitSeedRows), -1 = never (the exact seeder of the other filters), >= 1024 = that many; always clamped to a multiple of 1024 within N / 32, and the exact seeder where fewer than k groups of 32 rows remain or gemm_seed_n is set
     long split_screen_worst_case = 0;  // ... the screen's margin by the worst-case formula alone (every lo limb at half a last place), never from the limbs' measured norms (A/B, tests)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
@@ -97,6 +98,11 @@ enum LaunchFamily {
     kLaunchScanU8Masked = 12,  // scan_u8_filter_kernel<QB, R, true> (the masked exact scan of a code batch): args QB, R; groups = query groups
     kLaunchRangeScanU8 = 13,   // range_scan_u8_kernel<QB, EMIT>: args QB, EMIT; groups = query groups
 };
+// ... and one family outside the closed set above, which the readers of launch_log decode (tests pin it to 1 .. 13): the split
+// filter's seeder over a corpus prefix, gemm_bf16_filter_kernel<6, 3, 3>: args RR, MODE, LIMBS. It runs in front of a gemm_split
+// launch wherever seed_split serves (api.hip); the calls whose records are decoded name their exact prefix (gemm_seed_n) and
+// never reach it.
+enum LaunchFamilySeed { kLaunchSplitSeed = 14 };
 struct LaunchRec {
     uint8_t family;    // LaunchFamily
     uint8_t lockstep;  // gemm_i8s_filter_kernel: the soft-lockstep `prog` buffer was passed
@@ -194,6 +200,7 @@ struct innr_ctx {
     DevBuf rows_bits;  // innr_batch_update_rows (mutate.hip): one bit per vector of the batch, set by the index it was named by; zeroed per call
     DevBuf rows_map;   // innr_batch_keep_rows: old column of every kept row (the selection gather writes it; not read)
     int last_filter = 0;  // filter kernel of the last knn_mfma first pass (LastFilter; read by a test hook)
+    size_t split_seed_served = 0;  // prefix rows of the split filter's seeder in the last knn_mfma first pass (0: it did not run; read by a test hook)
     size_t screen_q = 0, screen_qpad = 0;  // queries of the last screen margins written to kmargin + Qpad (0: none yet; read by a test hook)
     LaunchRec launch_log[kLaunchLogCap] = {};  // ring of the last templated launches (launch_kernel; read by a test hook)
     uint64_t launch_total = 0;                 // launches recorded so far: entry i lives at launch_log[i % kLaunchLogCap]

@@ -1,6 +1,7 @@
 // gemm_epilogue.inc -- the per-tile epilogue of the GEMM engine's kernels, textually included at the point where a
 // corpus tile's 128 x 64 accumulators of a wave are complete (gemm_filter_kernel in kernels_gemm.h, and
-// gemm_bf16_filter_kernel in kernels_gemm_bf16.h): MODE 1 dumps the scores; MODE 0 runs the fast reject against the
+// gemm_bf16_filter_kernel in kernels_gemm_bf16.h): MODE 1 dumps the scores; MODE 3 (the split filter's seeder) writes the best
+// score of every group of 32 rows; MODE 0 runs the fast reject against the
 // list / chip-wide thresholds and, on a hit, the append path (topk_dev.h). Expects in scope: acc[4][2] (f32x16), tile,
 // lane, w, wu, q0, N, KP, cap, R, MODE, the kind flags COS / U8 / L2K with invn, invq, iq_lane, scale, the LDS object s
 // (cnt, thr), my_lists, errflag, gslots, gthr, kk, kmargin (the k rule of topk_dev.h), tg_next[2], dump, ld_dump, kEpiPubEvery (one admission in so many re-derives the chip-wide bound), and kEpiTgWait = a vmcnt count no larger than the
@@ -23,6 +24,27 @@
                             if (U8) v = v * scale + invq[q];
                             dump[q * ld_dump + i] = v;
                         }
+                }
+            } else if (MODE == 3) {
+                // the split filter's seeder (kernels_gemm_bf16.h): no threshold is loaded, no list touched. Per query column and row
+                // tile rt the best of the 32 rows tb + 4 i + rt -- this lane's 16 values g and those of its half-lane partner
+                // (i = (g & 3) + 8 (g >> 2) + 4 half) -- as an order key, to row 4 tile + rt of the [rows / 32][ld_dump] key matrix
+                uint32_t* const gmax = reinterpret_cast<uint32_t*>(dump);
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const size_t q = q0 + 64 * w + 2 * C + ct;
+#pragma unroll
+                    for (int rt = 0; rt < 4; ++rt) {
+                        uint32_t best = 0;
+#pragma unroll
+                        for (int g = 0; g < 16; ++g) {
+                            const uint32_t o = f32_ord(acc[rt][ct][g]);
+                            best = best > o ? best : o;
+                        }
+                        const uint32_t other = (uint32_t)__shfl_xor((int)best, 32, 64);
+                        best = best > other ? best : other;
+                        if (half == 0) gmax[((size_t)tile * 4 + rt) * ld_dump + q] = best;
+                    }
                 }
             } else {
                 // Threshold of each of this lane's two queries: the better of the list's own (KP-th best it holds)
@@ -240,7 +262,7 @@
                 for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                     for (int g = 0; g < 16; ++g) acc[rt][ct][g] = 0.0f;
-            if (MODE != 1) {
+            if (MODE != 1 && MODE != 3) {
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) gload1_agent(tg_next[ct], gthr + q0 + 64 * wu + ct, 8u * (uint32_t)(lane & 31));
             }

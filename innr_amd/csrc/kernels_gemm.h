@@ -464,6 +464,9 @@ __global__ void inv_qnorms_kernel(const float* __restrict__ x, size_t n, size_t 
 // T = the approximate score of the best candidate NOT yet re-scored (every such candidate, and every outsider, has approx <= T).
 // The column gathers of the re-score are sector traffic (4 useful bytes per line fetched): at C2 the low-precision filters
 // kept 128 candidates per query and spent 2.0 ms re-scoring them, although the answer was usually proven by the first 32.
+// r0 (16 or 32; early only): the first round is [0, r0), the rest of the best 32 a round of its own. A filter whose bound E is small
+// against the gaps between the best scores (the split filter, the f32 kernel) proves a short answer after the best 16; the
+// low-precision filters would only gain a serial round. nresc (nullable): the test hooks' count of candidates re-scored.
 template <int MET, int RK>
 __global__ __launch_bounds__(64) void rescore_kernel(const float* __restrict__ V, size_t ldN, uint32_t D,
                                                      const float* __restrict__ Qm, const float* __restrict__ norms,
@@ -473,7 +476,8 @@ __global__ __launch_bounds__(64) void rescore_kernel(const float* __restrict__ V
                                                      float err_scale, uint64_t index_base,
                                                      uint64_t* __restrict__ out_idx, float* __restrict__ out_score,
                                                      uint32_t* __restrict__ fallback, const float* __restrict__ eq = nullptr,
-                                                     bool early = false, const uint32_t* __restrict__ gthr = nullptr) {
+                                                     bool early = false, const uint32_t* __restrict__ gthr = nullptr,
+                                                     uint32_t r0 = 32, uint32_t* __restrict__ nresc = nullptr) {
     constexpr bool COS = MET == 1, L2 = MET == 2;
     const uint32_t q = blockIdx.x;
     const int lane = threadIdx.x;
@@ -506,26 +510,12 @@ __global__ __launch_bounds__(64) void rescore_kernel(const float* __restrict__ V
         }
         return cand_make(score_pref<L2>(acc), i);
     };
-    // rounds [0,32) [32,64) [64,128) [128,256): candidate c lives in slot c / 64 of lane c % 64
-    constexpr int NR = RK == 1 ? 2 : (RK == 2 ? 3 : 4);
-#pragma unroll
-    for (int round = 0; round < NR; ++round) {
-        const uint32_t lo = round == 0 ? 0u : (32u << (round - 1)), hi = 32u << round;
-        if (lo >= cnt && round > 0) break;  // (wave-uniform)
-        if (round < 2) {
-            const uint32_t c = (uint32_t)lane;
-            if (c >= lo && c < hi && c < cnt) e[0] = exact(c);
-        } else {
-#pragma unroll
-            for (int r = (round == 2 ? 1 : 2); r < (round == 2 ? 2 : 4); ++r)
-                if (r < RK) {
-                    const uint32_t c = (uint32_t)(r * 64 + lane);
-                    if (c < cnt) e[r < RK ? r : 0] = exact(c);
-                }
-        }
-        const uint32_t done = hi < cnt ? hi : cnt;
+    // rounds [0,r0) [r0,32) [32,64) [64,128) [128,256): candidate c lives in slot c / 64 of lane c % 64
+    // decide(done): with the best `done` candidates re-scored, rank them and try the proof; true: the answer is written (proven, or
+    // the last round's flagged for the exact engine), false: the next round brings more candidates
+    const auto decide = [&](uint32_t done) -> bool {
         const bool last = done == cnt;
-        if (!last && (!early || done < kout)) continue;  // nothing to decide yet
+        if (!last && (!early || done < kout)) return false;  // nothing to decide yet
         uint32_t rank[RK];
         rescore_rank<RK>(e, done, rank);
         uint32_t kth_bits = 0;
@@ -564,7 +554,7 @@ __global__ __launch_bounds__(64) void rescore_kernel(const float* __restrict__ V
             }
         }
         const bool failed = __any(bad);
-        if (failed && !last) continue;  // not proven yet: the next round brings more candidates
+        if (failed && !last) return false;  // not proven yet
 #pragma unroll
         for (int r = 0; r < RK; ++r) {
             const uint32_t c = r * 64 + lane;
@@ -579,7 +569,32 @@ __global__ __launch_bounds__(64) void rescore_kernel(const float* __restrict__ V
             // with fewer than k candidates there is none
             if (done < kout) out_score[(size_t)q * kout + kout - 1] = __builtin_nanf("");
         }
-        return;
+        if (nresc && lane == 0) atomicAdd(nresc, done);
+        return true;
+    };
+    constexpr int NR = RK == 1 ? 2 : (RK == 2 ? 3 : 4);
+#pragma unroll
+    for (int round = 0; round < NR; ++round) {
+        const uint32_t lo = round == 0 ? 0u : (32u << (round - 1)), hi = 32u << round;
+        if (lo >= cnt && round > 0) break;  // (wave-uniform)
+        if (round < 2) {
+            const uint32_t c = (uint32_t)lane;
+            uint32_t from = lo;
+            if (round == 0 && early && r0 < hi && r0 < cnt) {  // (wave-uniform) the short first round
+                if (c < r0) e[0] = exact(c);
+                if (decide(r0)) return;
+                from = r0;
+            }
+            if (c >= from && c < hi && c < cnt) e[0] = exact(c);
+        } else {
+#pragma unroll
+            for (int r = (round == 2 ? 1 : 2); r < (round == 2 ? 2 : 4); ++r)
+                if (r < RK) {
+                    const uint32_t c = (uint32_t)(r * 64 + lane);
+                    if (c < cnt) e[r < RK ? r : 0] = exact(c);
+                }
+        }
+        if (decide(hi < cnt ? hi : cnt)) return;
     }
 }
 

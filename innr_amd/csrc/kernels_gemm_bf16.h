@@ -342,6 +342,10 @@ __global__ __launch_bounds__(64) void split_pair_scores_kernel(const char* __res
 // wave alone adds the two small products from global memory, and the shared epilogue runs on the full split scores. Lists up to 64
 // (R <= 8): a wave tile with at most kPairCap (row, query) pairs at thr - m corrects exactly those pairs, each by the whole wave in
 // one memory round trip (split_pair_delta); a wave tile with more keeps the MFMA correction of its flagged sub-tiles.
+// MODE 3 (LIMBS 3, SCREEN 0, R 6 only): the split filter's SEEDER over a corpus prefix of whole tiles, one tile per block
+// (tiles_per_slice = 1). The full three-product K-loop, no thresholds, no lists: the epilogue writes, per query column and row
+// tile rt, the best split score of the 32 rows 128 tile + 4 i + rt as an order key to dump[(4 tile + rt) ld_dump + query]
+// (uint32_t words); split_seed_kernel below turns a query's column of them into its first chip-wide bound.
 template <int R, int MODE, int LIMBS, int SCREEN = 0>
 __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     const char* __restrict__ Ab, const char* __restrict__ Abx, const char* __restrict__ Bb, uint32_t ntiles, uint32_t N, uint32_t nk, size_t Qpad, uint32_t nqt,
@@ -357,6 +361,7 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
     constexpr bool kScreen = SCREEN != 0;
     constexpr bool kPairPath = kScreen && R <= 8;  // lists up to 64: the longer lists' kernels have no room for it
     static_assert(!kScreen || (LIMBS == 3 && MODE == 0), "the screen belongs to the split filter's top-k mode");
+    static_assert(MODE != 3 || (LIMBS == 3 && !kScreen && R == 6), "the seeder is the split filter's full loop; its list geometry plays no part");
     constexpr int kLoop = kScreen ? 1 : LIMBS;  // limbs the K-loop multiplies
     using G = BfGeom<kLoop>;
     constexpr bool kSplit = kLoop == 3;
@@ -724,6 +729,52 @@ __global__ __launch_bounds__(64 * kBfWaves, 1) void gemm_bf16_filter_kernel(
             if (lane == j) mine = keep;
         }
         counts[(size_t)slice * Qpad + q0 + 64 * w + lane] = mine;
+    }
+}
+
+// The split filter's first chip-wide bounds from its seeder's group maxima (MODE 3 above): gmax[ngroups][Qpad] order keys, group g
+// of query j = the best split score of 32 prefix rows, the groups disjoint. One wave per query. t = the k-th largest of the
+// query's ngroups keys, by bisection on the key bits (as select in gthr_publish_select): the largest t that at least k keys reach.
+// At least k DISTINCT rows then have an approximate score >= t -- the certificate of the k rule (topk_dev.h): their exact scores
+// are >= t - E, so is the k-th best exact score of the corpus, and a row of the true top k has an approximate score >= t - 2E.
+// seed[j] = key(t - 2E) - 1 (one key lower, as seed_thresholds_kernel: the re-score's proof is strict), E = err_scale |q_j| 1.0001
+// (cosine: err_scale 1.0001); 0 ("no bound") where that is not finite and for the padding queries j >= Q. The host keeps
+// k <= ngroups <= kSeedMaxGroups.
+constexpr uint32_t kSeedMaxGroups = 2048;
+__global__ __launch_bounds__(64) void split_seed_kernel(const uint32_t* __restrict__ gmax, uint32_t ngroups, uint32_t Qpad, uint32_t Q,
+                                                        uint32_t k, int cosine, float err_scale, const float* __restrict__ qnorm,
+                                                        uint32_t* __restrict__ seed) {
+    __shared__ uint32_t keys[kSeedMaxGroups];
+    const uint32_t j = blockIdx.x, lane = threadIdx.x;
+    if (j >= Q) {
+        if (lane == 0) seed[j] = 0u;
+        return;
+    }
+    for (uint32_t g = lane; g < ngroups; g += 64) keys[g] = gmax[(size_t)g * Qpad + j];
+    __syncthreads();
+    uint32_t t = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t cand = t | (1u << bit);
+        uint32_t n = 0;  // wave-uniform
+        for (uint32_t g0 = 0; g0 < ngroups; g0 += 64) {
+            const uint32_t g = g0 + lane;
+            n += (uint32_t)__builtin_popcountll(__ballot(g < ngroups && keys[g] >= cand));
+        }
+#if defined(INNR_MUTATE_SPLIT_SEED) && INNR_MUTATE_SPLIT_SEED == 1  // mutation check, never the product: one rank too high
+        if (n + 1 >= k) t = cand;
+#else
+        if (n >= k) t = cand;
+#endif
+    }
+    if (lane == 0) {
+        const float qn = qnorm[j];
+#if defined(INNR_MUTATE_SPLIT_SEED) && INNR_MUTATE_SPLIT_SEED == 2  // ... the bound without its 2E
+        const float E = 0.0f * err_scale;
+#else
+        const float E = (cosine ? err_scale : err_scale * qn) * 1.0001f;
+#endif
+        const float s = ord_f32(t) - 2.0f * E;
+        seed[j] = (s - s == 0.0f && qn - qn == 0.0f) ? f32_ord(s) - 1u : 0u;  // (a non-finite query norm: no bound of any kind)
     }
 }
 
