@@ -112,7 +112,8 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * free their selection at the end of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
  * innr_batch_set_copy_budget), scan_max_slots (default 0 = fill the chip: the most wave slots an exact scan is cut into, rounded
  * up to a multiple of 4, so that a wave owns several chunks of a small corpus), mutate_round (default 0 = what fits 256 MiB: the
- * most rows a staging round of innr_batch_append_rows / innr_batch_update_rows carries; a test switch) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
+ * most rows a staging round of innr_batch_append_rows / innr_batch_update_rows carries; a test switch), range_u8_i8_min_n (default
+ * 65536: the fewest vectors of a code batch whose innr_batch_range_search_u8 calls the int8 collect pass serves) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
 const char* innr_last_error(void);
@@ -223,13 +224,28 @@ innr_status innr_batch_knn_u8_filtered_dev(innr_batch* b, const float* d_queries
  * Order of the checks: a null or f32 batch: INNR_E_BAD_ARG; D != the batch's: INNR_E_DIM_MISMATCH; a null out_offsets or
  * out_total: INNR_E_BAD_ARG; N == 0 or Q == 0: all-zero offsets; null thresholds, queries or outputs with work to do:
  * INNR_E_BAD_ARG.
- * Engine: the exact scan in the reference's arithmetic serves every `engine` value, up to eight queries per pass: one pass counts
- * the survivors per 1024-vector chunk, a second one -- which skips every chunk without survivors -- writes them. stats->engine =
- * INNR_KNN_EXACT, queries_fallback = 0, candidates_kept = 0, gemm_ms = device time of the scans, total_ms of the whole call. The
- * host-memory entry point stages results as innr_batch_range_search does (a count pass first where min(cap, Q*N) results would
- * need more than 256 MiB); the call works in rounds of at most 4096 queries whose workspace stays within 2 GiB (per query N/256
- * bytes of counts).
- * Out of scope: a collect mode on the integer matrix pipe (`engine` is kept so that it needs no new symbol), a sharded variant. */
+ * Engines: INNR_KNN_EXACT scans the corpus in the reference's arithmetic, up to eight queries per pass: one pass counts the
+ * survivors per 1024-vector chunk, a second one -- which skips every chunk without survivors -- writes them. The other known
+ * values (INNR_KNN_MFMA, _BF16, _I8, and INNR_KNN_AUTO from a measured batch size on) take the collect path: one pass of the int8
+ * matrix-pipe filter over the batch's int8 copy (INNR_COPY_I8_DOT, the one innr_batch_knn_u8 builds: reported, released and
+ * budgeted as there) collects every vector whose approximate score is within the filter's error bound of the query's threshold,
+ * those are re-scored exactly and the exact predicate decides. A query without a finite collect threshold (a NaN or infinite
+ * threshold, a NaN / inf query, a query with no usable scale) and a query with more than 65536 collected vectors are finished by
+ * the exact scan (stats->queries_fallback counts them). Results are bit-identical either way. The collect path serves a call only
+ * if innr_batch_knn_u8's rules for the int8 engine hold (alpha > 0, finite params, D <= 65535; a prefix view: a length that is a
+ * multiple of 32), the batch has at least range_u8_i8_min_n vectors (a context option, default 65536 -- it binds explicit
+ * requests too: below it a tile launch plus re-score costs more than the scans) and the int8 copy exists or can be built: on an
+ * explicit request whenever the copy budget admits it, under INNR_KNN_AUTO only with room to spare (free memory >= twice the copy
+ * + 8 GiB) and from kRangeU8AutoQ0 queries on (api.hip; a tuning constant, not part of this contract). Otherwise, and for unknown
+ * engine values, the exact scan serves the whole call and nothing counts as a fallback.
+ * stats->engine = INNR_KNN_MFMA_I8 if a collect pass ran, else INNR_KNN_EXACT; queries_fallback = queries the exact scan finished
+ * after a collect pass; candidates_kept = the longest collected list (at most 65536); gemm_ms = device time of the collect
+ * launches (exact scan: of the scans); total_ms of the whole call. The host-memory entry point stages results as
+ * innr_batch_range_search does (a count pass first where min(cap, Q*N) results would need more than 256 MiB).
+ * Memory: the call works in rounds of at most 4096 queries whose workspace stays within 2 GiB (per query N/256 bytes of counts; on
+ * the collect path N/8 bytes of bitmap and 768 KiB of lists and keys more).
+ * Out of scope: a sharded variant; the filtered / selection variant of range search; bf16 / int8 collect modes of the f32
+ * innr_batch_range_search. */
 innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
                                        uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
                                        innr_knn_stats* stats);
@@ -378,7 +394,8 @@ innr_status innr_batch_l2_squared_pruning(innr_batch* b, const float* q, size_t 
  * more search) and stages what the result needs, so a generous cap costs time, not memory; its stats describe the last search.
  * Memory: the call works in rounds of at most 4096 queries whose workspace stays within 2 GiB (per query N/64 bytes of counts;
  * on the collect path N/8 bytes of bitmap and 768 KiB of lists more).
- * Out of scope: the int8 / bf16 collect modes, a sharded variant. (u8 code batches: innr_batch_range_search_u8.) */
+ * Out of scope: the int8 / bf16 collect modes, a sharded variant. (u8 code batches: innr_batch_range_search_u8, whose collect
+ * path runs on the int8 matrix pipe.) */
 innr_status innr_batch_range_search(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const float* thresholds,
                                     int engine, uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap,
                                     size_t* out_total, innr_knn_stats* stats);

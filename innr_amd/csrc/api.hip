@@ -45,7 +45,7 @@ static const TuneName kTuneNames[] = {
     {"i8_small_free", &innr_tuning::i8_small_free}, {"no_split_filter", &innr_tuning::no_split_filter},
     {"split_min_q", &innr_tuning::split_min_q}, {"no_split_screen", &innr_tuning::no_split_screen}, {"split_screen_worst_case", &innr_tuning::split_screen_worst_case}, {"split_seed_rows", &innr_tuning::split_seed_rows}, {"filter_keep_selection", &innr_tuning::filter_keep_selection},
     {"copy_budget_mib", &innr_tuning::copy_budget_mib}, {"scan_max_slots", &innr_tuning::scan_max_slots},
-    {"mutate_round", &innr_tuning::mutate_round},
+    {"mutate_round", &innr_tuning::mutate_round}, {"range_u8_i8_min_n", &innr_tuning::range_u8_i8_min_n},
 };
 static void tuning_from_env(innr_tuning* t) {
     for (const TuneName& n : kTuneNames) {
@@ -4578,9 +4578,9 @@ static innr_status range_search_dev(innr_batch* b, int metric, const float* dQ, 
         if (cap == 0) continue;  // a count-only call
         if (a.nq) INNR_TRY(launch_range_scan<true>(b, metric, a));
         if (collect) {
-            range_scatter_kernel<<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, l2,
-                                                            c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx, d_sc,
-                                                            (uint64_t)cap);
+            range_scatter_kernel<256><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, l2,
+                                                                 c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx, d_sc,
+                                                                 (uint64_t)cap);
             INNR_HIP_CHECK(hipGetLastError());
         }
     }
@@ -4633,10 +4633,24 @@ static innr_status range_search_args(innr_batch* b, int metric, const float* que
     return INNR_OK;
 }
 
-// ---- range search on a u8 code batch (innr_batch_range_search_u8): the exact scan's two launches per round -----
+// ---- range search on a u8 code batch (innr_batch_range_search_u8) ---------------------------------------------
+// Smallest batch INNR_KNN_AUTO sends through the collect pass on the int8 matrix pipe (kRangeAutoQ0's rule: the smallest measured
+// batch from which the collect path beats the exact scan on both shapes by more than the spread of the repeats; tools/bench_range.py
+// u8, thresholds at the 100th best, the int8 copy in place; whole call, ms, exact / collect; profiles/range_search_u8_*.txt):
+//      Q      1M x 128      10M x 768       50M x 768
+//      8    0.23 / 0.22     4.89 /  1.60     16.6 /  6.44     (1M x 128: 0.23 .. 0.25 against 0.20 .. 0.22 -- within the spread)
+//     16    0.33 / 0.23     8.59 /  1.63     30.6 /  6.50
+//     32    0.54 / 0.25    16.46 /  1.73     58.4 /  6.76
+//     64    0.95 / 0.27    30.97 /  1.86    113.7 /  7.49
+//    128    1.71 / 0.40    59.63 /  2.22    224.5 /  9.94
+//   1024   12.83 / 1.00   459.91 / 11.64   1774.8 / 69.76
+constexpr size_t kRangeU8AutoQ0 = 16;
+
+// the exact scan's two launches per round; qmap: see range_scan_u8_kernel
 template <bool EMIT>
-static innr_status launch_range_scan_u8(innr_batch* b, const float* dQ, const float* qsum, const float* thr, uint32_t nq, uint32_t* cnt,
-                                        size_t ldc, const uint64_t* qoff, uint64_t* out_idx, float* out_score, uint64_t cap) {
+static innr_status launch_range_scan_u8(innr_batch* b, const float* dQ, const float* qsum, const float* thr, const uint32_t* qmap,
+                                        uint32_t nq, uint32_t* cnt, size_t ldc, const uint64_t* qoff, uint64_t* out_idx, float* out_score,
+                                        uint64_t cap) {
     innr_ctx* c = b->ctx;
     const size_t nchunks = b->ldN / kU8Chunk;
     const uint32_t qb = nq >= 8 ? 8 : (nq >= 4 ? 4 : 1);  // never more than there are queries: the last group ends on the last query
@@ -4644,42 +4658,150 @@ static innr_status launch_range_scan_u8(innr_batch* b, const float* dQ, const fl
     const dim3 grid((unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * 4), (nq + qb - 1) / qb);
     dispatch([&](auto QB) {
         launch_kernel(c, Inst<kLaunchRangeScanU8, QB, EMIT>(), {grid, 256, 0, grid.y}, b->C8, b->ldN, (uint32_t)b->N, (uint32_t)b->D, dQ,
-                      b->D, qsum, b->alpha / 255.0f, b->offset, thr, nq, cnt, ldc, qoff, b->index_base, out_idx, out_score, cap);
+                      b->D, qsum, b->alpha / 255.0f, b->offset, thr, nq, cnt, ldc, qoff, b->index_base, out_idx, out_score, cap, qmap);
     }, one_of<8, 4, 1>(qb));
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
 
-static innr_status range_search_u8_dev(innr_batch* b, const float* dQ, size_t Q, const float* dThr, uint64_t* d_off, uint64_t* d_idx,
-                                       float* d_sc, size_t cap, size_t* out_total, innr_knn_stats* stats) {
+// Whether the collect pass serves a call: a known engine value other than EXACT, innr_batch_knn_u8's rules for the
+// int8 engine, a corpus of at least range_u8_i8_min_n vectors, and the int8 copy -- there already, or built now: on an explicit
+// request whenever the copy budget admits it, under AUTO only from kRangeU8AutoQ0 queries on and with room to spare (copy_fits).
+// An allocation that fails leaves the call to the exact scan.
+static innr_status range_u8_wants_collect(innr_batch* b, size_t Q, int engine, bool* collect) {
     innr_ctx* c = b->ctx;
-    const size_t D = b->D, nchunks = b->ldN / kU8Chunk, ldc = nchunks + 1;
-    const size_t per_query = (ldc + 2) * sizeof(uint32_t) + 2 * sizeof(float);
+    *collect = false;
+    if (engine != INNR_KNN_AUTO && engine != INNR_KNN_MFMA && engine != INNR_KNN_MFMA_BF16 && engine != INNR_KNN_MFMA_I8) return INNR_OK;
+    if (!i8_eligible(b, Q) || !gemm_addressable(b, std::min(Q, kRangeMaxRound))) return INNR_OK;
+    if (c->tune.range_u8_i8_min_n > 0 && b->N < (size_t)c->tune.range_u8_i8_min_n) return INNR_OK;
+    if (engine == INNR_KNN_AUTO && (Q < kRangeU8AutoQ0 || c->tune.u8_no_i8)) return INNR_OK;
+    if (!b->copy[kCopyI8Dot].p) {
+        const size_t copy_b = u8_i8_copy_bytes(b);
+        if (!budget_admits(b, copy_b)) return INNR_OK;
+        if (engine == INNR_KNN_AUTO) {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !copy_fits(free_b, copy_b)) return INNR_OK;
+        }
+        if (ensure_i8_corpus(b) != INNR_OK) {  // no memory for the copy: the exact scan needs none
+            (void)hipGetLastError();
+            return INNR_OK;
+        }
+    }
+    *collect = true;
+    return INNR_OK;
+}
+
+// The collect path mirrors range_search_dev's for a code batch: one MODE 2 pass of the int8 filter per round with the fixed
+// thresholds ord(thr_j - E_j) (E_j: rescore_u8_kernel's whole bound), exact scores of everything collected from the K-packed copy,
+// the exact predicate on those bits, and the finish in index order. Queries without a finite collect threshold are closed before
+// the launch and, like those whose list ran past kCollectCap, finished by the exact scan through a query map.
+static innr_status range_search_u8_dev(innr_batch* b, const float* dQ, size_t Q, const float* dThr, int engine, uint64_t* d_off,
+                                       uint64_t* d_idx, float* d_sc, size_t cap, size_t* out_total, innr_knn_stats* stats) {
+    innr_ctx* c = b->ctx;
+    const size_t D = b->D, nchunks = b->ldN / kU8Chunk, ldc = nchunks + 1, ldb = b->ldN / 32;
+    bool collect = false;
+    INNR_TRY(range_u8_wants_collect(b, Q, engine, &collect));
+    uint32_t nfallback = 0, kept = 0;
+    float gemm_ms = 0.0f;
+    const size_t per_query = (ldc + 2) * sizeof(uint32_t) + 2 * sizeof(float) +
+                             (collect ? ldb * sizeof(uint32_t) + (size_t)kCollectCap * (sizeof(uint32_t) + sizeof(uint64_t)) : 0);
     const size_t round = std::min(Q, std::max<size_t>(1, std::min(kRangeMaxRound, kRangeWorkspace / per_query)));
     INNR_TRY(c->rs_cnt.ensure(round * ldc * sizeof(uint32_t)));
-    INNR_TRY(c->rs_tot.ensure(round * sizeof(uint32_t)));
+    INNR_TRY(c->rs_tot.ensure(2 * round * sizeof(uint32_t)));
     INNR_TRY(c->q_norm.ensure(2 * round * sizeof(float)));
+    if (collect) INNR_TRY(c->rs_bits.ensure(round * ldb * sizeof(uint32_t)));
     uint32_t* cnt = c->rs_cnt.as<uint32_t>();
     uint32_t* tot = c->rs_tot.as<uint32_t>();
+    uint32_t* bad = tot + round;
     float* qsum = c->q_norm.as<float>();
+    float* qnorm = qsum + round;
     INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
     INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
     INNR_HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), c->stream));  // the running base, carried in the offsets themselves
-    INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
     for (size_t q0 = 0; q0 < Q; q0 += round) {
         const uint32_t nq = (uint32_t)std::min(round, Q - q0);
         const float* Qp = dQ + q0 * D;
+        const float* thr = dThr + q0;
         uint64_t* off = d_off + q0;
-        query_sums_kernel<<<(nq + 63) / 64, 64, 0, c->stream>>>(Qp, nq, (uint32_t)D, D, qsum, qsum + round);
+        query_sums_kernel<<<(nq + 63) / 64, 64, 0, c->stream>>>(Qp, nq, (uint32_t)D, D, qsum, qnorm);
         INNR_HIP_CHECK(hipGetLastError());
-        INNR_TRY(launch_range_scan_u8<false>(b, Qp, qsum, dThr + q0, nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
+        // the queries the exact scan serves: all of them, or after a collect pass the bad ones (gathered, with a map to their rows)
+        const float *sQ = Qp, *sSum = qsum, *sThr = thr;
+        const uint32_t* smap = nullptr;
+        uint32_t snq = nq;
+        const dim3 lg(kCollectCap / 256, nq);  // (blocks beyond a query's list length return at once)
+        if (collect) {
+            I8Plan p = plan_i8(b, kCopyI8Dot, nq, 1, 32u, /*one_limb=*/true);
+            (void)plan_i8_small(b, &p, nq, false, /*collect=*/true);
+            INNR_TRY(prep_queries_i8(b, p, Qp, nq, qsum, b->alpha, b->offset));
+            const float* qc = c->misc.as<float>();
+            // fixed thresholds: thr - E (one key lower); 0 = "no bound" where that is not finite -> closed, the exact scan's
+            INNR_TRY(c->seed_score.ensure(p.Qpad * sizeof(uint32_t)));
+            uint32_t* seed = c->seed_score.as<uint32_t>();
+            seed_thresholds_u8_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(thr, nq, 1u, u8_filter_scale(b), qnorm, qsum, b->offset,
+                                                                                           qc + 3 * p.Qpad, seed, (uint32_t)p.Qpad, 0u);
+            range_close_unbounded_kernel<<<(nq + 255) / 256, 256, 0, c->stream>>>(seed, nq);
+            INNR_HIP_CHECK(hipGetLastError());
+            // global lists: [Qpad][kCollectCap] indices, [Qpad] lengths
+            INNR_TRY(c->lists.ensure(p.Qpad * (size_t)kCollectCap * sizeof(uint32_t)));
+            INNR_TRY(c->counts.ensure(p.Qpad * sizeof(uint32_t)));
+            INNR_TRY(c->sort_keys.ensure(nq * (size_t)kCollectCap * sizeof(uint64_t)));
+            INNR_HIP_CHECK(hipMemsetAsync(c->counts.p, 0, p.Qpad * sizeof(uint32_t), c->stream));
+            I8Plan pl = p;
+            pl.KP = kCollectCap;  // what the kernel takes as the list capacity
+            INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+            INNR_TRY(launch_gemm_i8<2>(b, pl, nq, qc, nullptr, 0, seed));
+            INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+            collect_scores_u8_kernel<<<lg, 256, 0, c->stream>>>(reinterpret_cast<const uint4*>(p.corpus), p.nk, (uint32_t)D, Qp, qsum,
+                                                                b->alpha / 255.0f, b->offset, c->lists.as<uint32_t>(), c->counts.as<uint32_t>(),
+                                                                kCollectCap, c->sort_keys.as<uint64_t>());
+            INNR_HIP_CHECK(hipMemsetAsync(c->rs_bits.p, 0, nq * ldb * sizeof(uint32_t), c->stream));
+            INNR_HIP_CHECK(hipMemsetAsync(cnt, 0, nq * ldc * sizeof(uint32_t), c->stream));
+            range_mark_kernel<false, (int)kU8Chunk, false><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr,
+                                                                                      seed, nullptr, c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
+            INNR_HIP_CHECK(hipGetLastError());
+            // which queries the exact scan finishes, and how long the lists got (one synchronisation per round)
+            std::vector<uint32_t> hb(2 * (size_t)nq);
+            INNR_HIP_CHECK(hipMemcpyAsync(hb.data(), bad, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            INNR_HIP_CHECK(hipMemcpyAsync(hb.data() + nq, c->counts.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            INNR_HIP_CHECK(hipStreamSynchronize(c->stream));
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms += ms;
+            std::vector<uint32_t> redo;
+            for (uint32_t j = 0; j < nq; ++j) {
+                if (hb[j]) redo.push_back(j);
+                kept = std::max(kept, std::min(hb[nq + j], kCollectCap));
+            }
+            nfallback += (uint32_t)redo.size();
+            snq = (uint32_t)redo.size();
+            if (snq) {  // gathered: their rows (rb.q), thresholds (rb.qn) and sums (rb.sc); rb.map = the rows of cnt / off
+                innr_ctx::RedoBufs& rb = c->cmpl;
+                INNR_TRY(upload_redo(c, rb, redo, D, 1));
+                smap = rb.map.as<uint32_t>();
+                gather_rows_kernel<<<(unsigned)(((size_t)snq * D + 255) / 256), 256, 0, c->stream>>>(Qp, smap, snq, (uint32_t)D, rb.q.as<float>());
+                gather_f32_kernel<<<(snq + 255) / 256, 256, 0, c->stream>>>(thr, smap, snq, rb.qn.as<float>());
+                gather_f32_kernel<<<(snq + 255) / 256, 256, 0, c->stream>>>(qsum, smap, snq, rb.sc.as<float>());
+                INNR_HIP_CHECK(hipGetLastError());
+                sQ = rb.q.as<float>();
+                sThr = rb.qn.as<float>();
+                sSum = rb.sc.as<float>();
+            }
+        }
+        if (snq) INNR_TRY(launch_range_scan_u8<false>(b, sQ, sSum, sThr, smap, snq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
         range_chunk_scan_kernel<<<nq, 1024, 0, c->stream>>>(cnt, ldc, (uint32_t)nchunks, tot);
         range_offsets_kernel<<<1, 1024, 0, c->stream>>>(tot, nq, off);
         INNR_HIP_CHECK(hipGetLastError());
         if (cap == 0) continue;  // a count-only call
-        INNR_TRY(launch_range_scan_u8<true>(b, Qp, qsum, dThr + q0, nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
+        if (snq) INNR_TRY(launch_range_scan_u8<true>(b, sQ, sSum, sThr, smap, snq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
+        if (collect) {
+            range_scatter_kernel<(int)kU8Chunk><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, false,
+                                                                           c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx,
+                                                                           d_sc, (uint64_t)cap);
+            INNR_HIP_CHECK(hipGetLastError());
+        }
     }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
     INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
     uint64_t total = 0;
     INNR_HIP_CHECK(copy_out(c, &total, d_off + Q, sizeof(total)));
@@ -4687,8 +4809,11 @@ static innr_status range_search_u8_dev(innr_batch* b, const float* dQ, size_t Q,
     *out_total = (size_t)total;
     if (stats) {
         float ms = 0.0f;
-        stats->engine = INNR_KNN_EXACT;
-        if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) stats->gemm_ms = ms;
+        if (!collect && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms = ms;
+        stats->engine = collect ? INNR_KNN_MFMA_I8 : INNR_KNN_EXACT;
+        stats->queries_fallback = nfallback;
+        stats->candidates_kept = kept;
+        stats->gemm_ms = gemm_ms;
         if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
     }
     return INNR_OK;
@@ -4780,11 +4905,9 @@ innr_status innr_batch_range_search(innr_batch* b, int metric, const float* quer
                                   });
 }
 
-// `engine` is accepted and ignored: the exact scan serves every value (a later matrix-pipe collect mode needs no new symbol)
 innr_status innr_batch_range_search_u8_dev(innr_batch* b, const float* d_queries, size_t Q, size_t D, const float* d_thresholds, int engine,
                                            uint64_t* d_out_offsets, uint64_t* d_out_idx, float* d_out_score, size_t cap, size_t* out_total,
                                            innr_knn_stats* stats) {
-    (void)engine;
     bool empty = false;
     INNR_TRY(range_search_u8_args(b, d_queries, Q, D, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats, &empty));
     innr_ctx* c = b->ctx;
@@ -4794,13 +4917,12 @@ innr_status innr_batch_range_search_u8_dev(innr_batch* b, const float* d_queries
         INNR_HIP_CHECK(ctx_sync(c));
         return INNR_OK;
     }
-    return range_search_u8_dev(b, d_queries, Q, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+    return range_search_u8_dev(b, d_queries, Q, d_thresholds, engine, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
 }
 
 innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
                                        uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
                                        innr_knn_stats* stats) {
-    (void)engine;
     bool empty = false;
     INNR_TRY(range_search_u8_args(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total, stats, &empty));
     if (empty) {
@@ -4809,7 +4931,7 @@ innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size
     }
     return range_search_from_host(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
                                   [&](const float* dQ, const float* dThr, uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t room) {
-                                      return range_search_u8_dev(b, dQ, Q, dThr, d_off, d_idx, d_sc, room, out_total, stats);
+                                      return range_search_u8_dev(b, dQ, Q, dThr, engine, d_off, d_idx, d_sc, room, out_total, stats);
                                   });
 }
 

@@ -77,6 +77,7 @@ struct innr_tuning {
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
     long mutate_round = 0;       // innr_batch_append_rows, innr_batch_update_rows: at most this many rows per staging round (tests); 0 = what fits 256 MiB
+    long range_u8_i8_min_n = 65536;  // innr_batch_range_search_u8: fewest vectors of a code batch whose calls the collect pass on the int8 matrix pipe serves, for every engine value (below it a tile launch plus re-score costs more than the scans; tests of small shapes set 0)
     long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip
 };
 

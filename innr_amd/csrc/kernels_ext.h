@@ -170,16 +170,27 @@ __global__ __launch_bounds__(1024) void range_offsets_kernel(const uint32_t* __r
 // bound held for the query: bad[q] = 1 otherwise (list past `cap`; no finite collect threshold, seed[q] == 0; a query norm outside
 // {0} + [1e-12, 1e18], where the approximate scores may overflow or lose products to flushing) and the exact scan finishes it.
 // For the others the exact predicate marks each survivor in the query's bitmap over the corpus (bit i % 32 of word i / 32) and
-// counts it in its 256-vector chunk. A corpus index occurs once per list, and OR / ADD do not depend on the order of arrival.
-template <bool L2>
+// counts it in its CHUNK-vector chunk. A corpus index occurs once per list, and OR / ADD do not depend on the order of arrival.
+// CHUNK: the vectors per count of the exact scan that shares cnt (256: range_scan_kernel, 1024: range_scan_u8_kernel).
+// QNORM = false (a code corpus on the int8 filter): no norm window -- a constant that overflows already makes the query's bound
+// non-finite, hence its seed 0 -- and qnorm is not read; a query without a finite collect threshold was closed before the launch
+// (seed[q] = 0xFFFFFFFF, range_close_unbounded_kernel) and is bad like one whose seed is still 0.
+template <bool L2, int CHUNK = 256, bool QNORM = true>
 __global__ __launch_bounds__(256) void range_mark_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ccnt, uint32_t cap,
                                                           const float* __restrict__ thr, const uint32_t* __restrict__ seed,
                                                           const float* __restrict__ qnorm, uint32_t* __restrict__ bitmap, size_t ldb,
                                                           uint32_t* __restrict__ cnt, size_t ldc, uint32_t* __restrict__ bad) {
+    static_assert(CHUNK == 256 || CHUNK == 1024, "the chunk of the f32 scans or of the u8 scans");
+    constexpr int SH = CHUNK == 256 ? 8 : 10;
     const uint32_t q = blockIdx.y;
     const uint32_t n = ccnt[q];
-    const float qn = qnorm[q];
-    const bool fb = n > cap || seed[q] == 0u || !(qn == 0.0f || (qn >= 1e-12f && qn <= 1e18f));
+    bool fb;
+    if constexpr (QNORM) {
+        const float qn = qnorm[q];
+        fb = n > cap || seed[q] == 0u || !(qn == 0.0f || (qn >= 1e-12f && qn <= 1e18f));
+    } else {
+        fb = n > cap || seed[q] == 0u || seed[q] == 0xFFFFFFFFu;
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0) bad[q] = fb ? 1u : 0u;
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     if (fb || slot >= n) return;
@@ -188,27 +199,40 @@ __global__ __launch_bounds__(256) void range_mark_kernel(const uint64_t* __restr
     if (L2 ? (s > t) : (s < t)) return;
     const uint32_t i = cand_idx(key), bit = 1u << (i & 31);
     const uint32_t old = atomicOr(bitmap + (size_t)q * ldb + (i >> 5), bit);
-    if (!(old & bit)) atomicAdd(cnt + (size_t)q * ldc + (i >> 8), 1u);
+    if (!(old & bit)) atomicAdd(cnt + (size_t)q * ldc + (i >> SH), 1u);
+}
+
+// The collect thresholds of a code corpus (seed_thresholds_u8_kernel) before the launch: a query without a finite one (seed 0: a
+// NaN or infinite threshold, a NaN / inf query, an unusable query scale) would collect the whole corpus through the survivors'
+// path only to be discarded. It is closed the way padding queries are -- the largest key, nothing is ever admitted -- and
+// range_mark_kernel<.., false> hands it to the exact scan.
+__global__ void range_close_unbounded_kernel(uint32_t* __restrict__ seed, uint32_t nq) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < nq && seed[j] == 0u) seed[j] = 0xFFFFFFFFu;
 }
 
 // ... and after the scans each marked candidate goes to its place in index order: the query's offset, its chunk's prefix, the
 // marked vectors of the chunk below it (popcounts of the bitmap). Only positions < outcap are written.
+template <int CHUNK = 256>
 __global__ __launch_bounds__(256) void range_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ccnt, uint32_t cap,
                                                              bool l2, const uint32_t* __restrict__ bitmap, size_t ldb,
                                                              const uint32_t* __restrict__ pref, size_t ldc, const uint32_t* __restrict__ bad,
                                                              const uint64_t* __restrict__ qoff, uint64_t index_base,
                                                              uint64_t* __restrict__ out_idx, float* __restrict__ out_score, uint64_t outcap) {
+    static_assert(CHUNK == 256 || CHUNK == 1024, "the chunk of the f32 scans or of the u8 scans");
+    constexpr int SH = CHUNK == 256 ? 8 : 10;
+    constexpr uint32_t W = CHUNK / 32;  // bitmap words per chunk
     const uint32_t q = blockIdx.y;
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     if (bad[q] || slot >= ccnt[q]) return;
     const uint64_t key = keys[(size_t)q * cap + slot];
     const uint32_t i = cand_idx(key), bit = 1u << (i & 31);
-    const uint32_t* words = bitmap + (size_t)q * ldb + ((i >> 8) << 3);  // the chunk's eight words
-    const uint32_t w = (i >> 5) & 7;
+    const uint32_t* words = bitmap + (size_t)q * ldb + ((i >> SH) * W);  // the chunk's words
+    const uint32_t w = (i >> 5) & (W - 1);
     if (!(words[w] & bit)) return;
     uint32_t rank = (uint32_t)__popc(words[w] & (bit - 1u));
     for (uint32_t u = 0; u < w; ++u) rank += (uint32_t)__popc(words[u]);
-    const uint64_t pos = qoff[q] + pref[(size_t)q * ldc + (i >> 8)] + rank;
+    const uint64_t pos = qoff[q] + pref[(size_t)q * ldc + (i >> SH)] + rank;
     if (pos < outcap) {
         out_idx[pos] = index_base + i;
         out_score[pos] = pref_score(cand_pref(key), l2);

@@ -498,16 +498,21 @@ __global__ __launch_bounds__(256) void scan_u8_filter_kernel(const uint8_t* __re
 //     lane's earlier codes. Only positions < cap are written.
 // Query groups of QB on blockIdx.y; the ragged last group is moved back to end on the last query (nq >= QB) and writes only the
 // queries the group before does not, as in range_scan_kernel.
+// qmap: cnt / qoff row of local query q (null: q itself) -- the queries of a batch that the exact scan finishes after a collect pass.
 template <int QB, bool EMIT>
 __global__ __launch_bounds__(256) void range_scan_u8_kernel(const uint8_t* __restrict__ C, size_t ldN, uint32_t N, uint32_t D,
                                                             const float* __restrict__ Qm, size_t ldq, const float* __restrict__ qsum,
                                                             float a255, float offset, const float* __restrict__ thr, uint32_t nq,
                                                             uint32_t* __restrict__ cnt, size_t ldc, const uint64_t* __restrict__ qoff,
                                                             uint64_t index_base, uint64_t* __restrict__ out_idx,
-                                                            float* __restrict__ out_score, uint64_t cap) {
+                                                            float* __restrict__ out_score, uint64_t cap,
+                                                            const uint32_t* __restrict__ qmap = nullptr) {
     const uint32_t g0 = blockIdx.y * QB;                // first query this group writes
     const uint32_t qb0 = g0 + QB <= nq ? g0 : nq - QB;  // first query it scores
     Qm += (size_t)qb0 * ldq;
+    size_t row[QB];
+#pragma unroll
+    for (int j = 0; j < QB; ++j) row[j] = qmap ? qmap[qb0 + j] : qb0 + j;
     const size_t nchunks = ldN / kU8Chunk;
     const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * 256) >> 6;
     const int lane = threadIdx.x & 63;
@@ -516,7 +521,7 @@ __global__ __launch_bounds__(256) void range_scan_u8_kernel(const uint8_t* __res
             bool any = false;
 #pragma unroll
             for (int j = 0; j < QB; ++j)
-                if (qb0 + j >= g0) any |= cnt[(size_t)(qb0 + j) * ldc + ch + 1] != cnt[(size_t)(qb0 + j) * ldc + ch];
+                if (qb0 + j >= g0) any |= cnt[row[j] * ldc + ch + 1] != cnt[row[j] * ldc + ch];
             if (!any) continue;  // wave-uniform
         }
         const size_t col = ch * kU8Chunk + (size_t)lane * 16;
@@ -537,7 +542,7 @@ __global__ __launch_bounds__(256) void range_scan_u8_kernel(const uint8_t* __res
                 uint32_t total = mine;
 #pragma unroll
                 for (int off = 32; off >= 1; off >>= 1) total += (uint32_t)__shfl_xor((int)total, off, 64);
-                if (lane == 0) cnt[(size_t)(qb0 + j) * ldc + ch] = total;
+                if (lane == 0) cnt[row[j] * ldc + ch] = total;
             } else {
                 uint32_t incl = mine;  // inclusive prefix sum over the lanes
 #pragma unroll
@@ -546,7 +551,7 @@ __global__ __launch_bounds__(256) void range_scan_u8_kernel(const uint8_t* __res
                     if (lane >= off) incl += up;
                 }
                 if (keep) {
-                    uint64_t pos = qoff[qb0 + j] + cnt[(size_t)(qb0 + j) * ldc + ch] + (incl - mine);
+                    uint64_t pos = qoff[row[j]] + cnt[row[j] * ldc + ch] + (incl - mine);
 #pragma unroll
                     for (int c = 0; c < 16; ++c) {
                         if (keep & (1u << c)) {
@@ -561,6 +566,45 @@ __global__ __launch_bounds__(256) void range_scan_u8_kernel(const uint8_t* __res
             }
         }
     }
+}
+
+// ---- the collect path of innr_batch_range_search_u8: exact scores of the code rows a MODE 2 pass of the int8 filter collected ----
+// The code-corpus counterpart of collect_scores_rows_kernel: one lane per (query, slot), grid (cap / 256, queries); blocks past the
+// list length return at once. The codes come ROW-WISE from the int8 filter's K-packed copy (rescore_u8_kernel's address
+// arithmetic: 16 consecutive dimensions per 16-byte unit, c - 128 as i8, hence the ^ 0x80) -- never by column gathers from the
+// dimension-major store, which cost one 32-byte sector per dimension and candidate. The sum is the reference's chain: d ascending
+// from -0.0f, fl(acc + fl(q_d * c_d)), then u8_score. keys[q][slot] = cand_make(f32_ord(score), i) for the first min(ccnt[q], cap)
+// slots. The query is uniform over the block (blockIdx.y): its elements come through scalar loads.
+__global__ __launch_bounds__(256) void collect_scores_u8_kernel(const uint4* __restrict__ Ai8, uint32_t nk, uint32_t D,
+                                                                const float* __restrict__ Qm, const float* __restrict__ qsum, float a255,
+                                                                float offset, const uint32_t* __restrict__ clist,
+                                                                const uint32_t* __restrict__ ccnt, uint32_t cap,
+                                                                uint64_t* __restrict__ keys) {
+    const uint32_t q = blockIdx.y;
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t n = ccnt[q] < cap ? ccnt[q] : cap;
+    if (slot >= n) return;  // (the finish reads only the first n keys)
+    const uint32_t i = clist[(size_t)q * cap + slot];
+    const float* qv = Qm + (size_t)q * D;
+    const uint4* rowp = Ai8 + ((size_t)(i >> 7) * nk * 4) * 128 + (i & 3u) * 32 + ((i & 127u) >> 2);
+    float acc = -0.0f;
+    const uint32_t nfull = D / 16;
+    for (uint32_t ch = 0; ch < nfull; ++ch) {
+        const uint4 v = rowp[(size_t)ch * 128];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc = ex::mad2(acc, qv[ch * 16 + e], (float)(((w[e >> 2] >> (8 * (e & 3))) & 0xffu) ^ 0x80u));
+    }
+    if (nfull * 16 < D) {  // the ragged last unit (a row of the copy is whole K-steps long: the load stays inside it)
+        const uint4 v = rowp[(size_t)nfull * 128];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const uint32_t d = nfull * 16 + e;
+            if (d < D) acc = ex::mad2(acc, qv[d], (float)(((w[e >> 2] >> (8 * (e & 3))) & 0xffu) ^ 0x80u));
+        }
+    }
+    keys[(size_t)q * cap + slot] = cand_make(f32_ord(u8_score(a255, acc, offset, qsum[q])), i);
 }
 
 }  // namespace innr

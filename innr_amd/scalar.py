@@ -278,6 +278,11 @@ class QuantizedCorpus(_lib.BatchMemoryMixin):
         float32 [total]); query j owns [offsets[j], offsets[j + 1]). A scalar threshold is broadcast to all queries. cap: room for
         that many results -- the offsets are the full ones, indices / scores hold the first min(total, cap) entries, 0 only
         counts; None: one call with a guessed capacity and, only if that was exceeded, a second one with room for everything.
+        engine: KNN_EXACT scans the codes, eight queries a pass; KNN_MFMA / _BF16 / _I8 (and KNN_AUTO from a measured batch size
+        on) collect every document within the int8 filter's error bound of its query's threshold in one matrix-pipe pass over the
+        corpus' int8 copy (COPY_I8_DOT, built on first use like knn_multi's), re-score those exactly and decide on the exact bits;
+        corpora below the context option range_u8_i8_min_n (65536) always take the scan. Same results either way; stats.engine
+        says which ran, stats.queries_fallback how many queries the scan finished after a collect pass.
         Torch device tensors (queries on the corpus' GPU) take the device entry point: thresholds go to the device, offsets
         (int64), indices (int64) and scores stay there."""
         n = self._n

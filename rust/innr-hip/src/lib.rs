@@ -668,7 +668,9 @@ pub mod scalar {
             (0..q).map(|j| (j * out_k..(j + 1) * out_k).map(|i| (idx[i] as usize, sc[i])).collect()).collect()
         }
         /// every document with `!(score < thresholds[j])` for query j, in index order (innr_batch_range_search_u8): a count-only
-        /// call sizes the buffers, a second one fills them
+        /// call sizes the buffers, a second one fills them. `engine`: INNR_KNN_EXACT scans; the other values (AUTO from a measured
+        /// batch size on) collect on the int8 matrix pipe over the corpus' int8 copy and re-score exactly, on corpora of at least
+        /// `range_u8_i8_min_n` vectors -- the same bits either way
         #[must_use] pub fn range_search(&self, engine: i32, queries: &[f32], thresholds: &[f32]) -> Vec<Vec<(usize, f32)>> {
             let q = thresholds.len();
             assert_eq!(queries.len(), q * self.dim);
