@@ -2260,6 +2260,42 @@ extern "C" void innrdbg_scan_log_reset(innr_ctx* c) {
     c->scan_total = 0;
 }
 
+// Test hook: the context's workspace overwritten with one byte value, so that the next call meets residue no earlier call of a
+// test would have left (tests/test_gpu_workspace_residue.py): every buffer of workspace_bufs() but `flags` (the documented
+// exception: the kernels' error words live there between the calls' own memsets) over its full size, and the whole pinned
+// staging area (nothing is pending after the synchronise). *bytes_filled = the device bytes written (innr_ctx_memory less flags).
+extern "C" innr_status innrdbg_workspace_fill(innr_ctx* c, int byte, uint64_t* bytes_filled) {
+    if (!c) return INNR_E_BAD_ARG;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(ctx_sync(c));
+    uint64_t sum = 0;
+    for (DevBuf* buf : workspace_bufs(c)) {
+        if (buf == &c->flags || !buf->p || !buf->bytes) continue;
+        INNR_HIP_CHECK(hipMemsetAsync(buf->p, byte, buf->bytes, c->stream));
+        sum += buf->bytes;
+    }
+    if (c->pin) memset(c->pin, byte, kPinIn + kPinOut);
+    INNR_HIP_CHECK(ctx_sync(c));
+    if (bytes_filled) *bytes_filled = sum;
+    return INNR_OK;
+}
+// ... and the size of every workspace buffer, in the order of workspace_bufs(): up to `cap` sizes into `sizes`, the number of
+// buffers returned; innrdbg_workspace_names() = their names in the same order, comma-separated
+extern "C" size_t innrdbg_workspace_sizes(innr_ctx* c, uint64_t* sizes, size_t cap) {
+    if (!c) return 0;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    const std::vector<DevBuf*> bufs = workspace_bufs(c);
+    for (size_t i = 0; i < bufs.size() && i < cap && sizes; ++i) sizes[i] = bufs[i]->bytes;
+    return bufs.size();
+}
+extern "C" const char* innrdbg_workspace_names(void) {
+    return "gthr,sel_tmp0,sel_tmp1,selcnt_tmp0,selcnt_tmp1,q_row,q_kmajor,q_norm,lists,counts,sel,sel_cnt,scores,tmp_norms,flags,"
+           "out_idx,out_score,misc,seed_idx,seed_score,q_one,sort_keys,sort_tmp,q_bf16,q_pad,q_hat,redo0.q,redo0.idx,redo0.sc,"
+           "redo0.map,redo0.qn,redo1.q,redo1.idx,redo1.sc,redo1.map,redo1.qn,kmargin,i8s_prog,cmpl.q,cmpl.idx,cmpl.sc,cmpl.map,"
+           "cmpl.qn,flt_in,flt_mask,flt_scan,rs_cnt,rs_bits,rs_tot,rs_thr,rs_off,adp_scan,adp_list,rows_q,rows_stage,rows_io,"
+           "rows_flag,rows_bits,rows_map";
+}
+
 // Test hook: sort_full.hip's full_topk_keys on caller-given composites -- the radix select, the gather and the bitonic network with
 // nothing in front of them. host_keys[0..n) -> host_sorted[0..min(k, n)), best (largest) first. Buffers as knn_full_sort lays them
 // out: c->sort_keys = [n keys][full_topk_out_capacity(min(k, n)) sorted], c->sort_tmp = the selection state.
