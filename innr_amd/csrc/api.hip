@@ -413,12 +413,66 @@ static innr_status select_and_emit(innr_batch* b, uint32_t nslots, uint32_t nql,
     return emit_results(c, c->sel.as<uint64_t>(), KP, nreal, kout, l2, b->index_base, d_out_idx, d_out_score);
 }
 
+// How an exact scan lays a corpus out over the chip
+struct ScanGeom {
+    size_t cols;          // columns that are scanned
+    size_t chunk;         // ... in chunks of this many
+    size_t waves_per_cu;  // wave slots: never more than this per CU, nor than there are chunks
+    size_t block_waves;   // ... a whole number of blocks of this many waves
+    size_t bytes;         // what one pass reads: a corpus within the Infinity Cache takes all its groups in one launch
+    bool l2;              // smaller is better
+};
+
+// The rounds of an exact scan, f32 or code corpus, for queries [q0, q0+nq) (row-major on device, stride ldq; aux: the per-query value,
+// nullable): results to d_out_* at row q0. launch(qb, q, aux, nblocks, nql, KP, cap, cps, groups, nreal) scans for `groups` groups
+// of qb queries -- nql slots, the first nreal of them real -- into c->lists / c->counts.
+template <class Launch>
+static innr_status exact_scan_rounds(innr_batch* b, const ScanGeom& g, const float* dQ, size_t ldq, const float* aux, size_t q0,
+                                     size_t nq, size_t kout, uint64_t* d_out_idx, float* d_out_score, Launch&& launch) {
+    innr_ctx* c = b->ctx;
+    const uint32_t KP = pick_kp(kout, 0);
+    const uint32_t cap = exact_cap(KP);
+    const size_t nchunks = g.cols / g.chunk;
+    size_t nslots = cap_scan_slots(c, std::min<size_t>(nchunks, (size_t)c->num_cus * g.waves_per_cu));
+    nslots = round_up(nslots, g.block_waves);
+    const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
+    const uint32_t nblocks = (uint32_t)(nslots / g.block_waves);
+    constexpr uint32_t QBMAX = 8;
+    // A corpus that stays in the Infinity Cache (<= 128 MB) is cheap to re-read and too small to fill the chip with
+    // one group of 8 queries: all the 8-query groups go into ONE launch (blockIdx.y), within 256 MB of list space.
+    // Large corpora keep one group per launch (each launch streams HBM once and fills the chip by itself).
+    size_t max_groups = 1;
+    if (g.bytes <= (size_t)128 << 20) max_groups = std::max<size_t>(1, ((size_t)256 << 20) / (nslots * QBMAX * cap * sizeof(uint64_t)));
+    max_groups = std::min<size_t>(max_groups, 65535);
+    size_t done = 0;
+    while (done < nq) {
+        const size_t rem = nq - done;
+        // One corpus pass serves 8, 4 or 1 queries. A ragged tail of 5-7 (2-3) queries takes ONE 8- (4-) query pass with
+        // zero rows as padding instead of several smaller passes (2 queries: 5.5 ms instead of 2 x 5.2 at 10M x 768; on a code
+        // corpus the 8-query pass costs less than two of 4: one corpus stream, one widening of each code).
+        const uint32_t qb = rem >= 5 ? 8 : (rem >= 2 ? 4 : 1);
+        // (only 8-query passes come in several groups: with qb == 4, rem <= 4, so "qb > 1 && rem >= qb ? rem / qb" gives 1 as well)
+        const uint32_t groups = (qb == 8 && rem >= 8) ? (uint32_t)std::min<size_t>(rem / 8, max_groups) : 1u;
+        const uint32_t nql = qb * groups;                               // query slots of this launch
+        const uint32_t nreal = (uint32_t)std::min<size_t>(nql, rem);    // ... of which real queries
+        INNR_TRY(c->lists.ensure(nslots * nql * cap * sizeof(uint64_t)));
+        INNR_TRY(c->counts.ensure(nslots * nql * sizeof(uint32_t)));
+        const float* q = dQ + (q0 + done) * ldq;
+        const float* qa = aux ? aux + q0 + done : nullptr;
+        if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qa));
+        INNR_TRY(launch(qb, q, qa, nblocks, nql, KP, cap, cps, groups, nreal));
+        INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, g.l2, d_out_idx + (q0 + done) * kout,
+                                 d_out_score + (q0 + done) * kout));
+        done += nreal;
+    }
+    return INNR_OK;
+}
+
 // Exact kNN for queries [q0, q0+nq) (row-major on device, stride ldq): results to d_out_* at row q0.
 // limit_n != 0: only the first limit_n vectors of the batch take part (the GEMM engine's threshold seeding).
 static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* dQ, size_t ldq, const float* dQn,
                                    size_t q0, size_t nq, size_t kout, uint64_t* d_out_idx, float* d_out_score,
                                    const ScanExt& ext = ScanExt(), size_t limit_n = 0) {
-    innr_ctx* c = b_full->ctx;
     innr_batch view;  // same device buffers, shorter N (masks) -- never freed, it owns nothing
     innr_batch* b = b_full;
     if (limit_n && limit_n < b_full->N) {
@@ -432,48 +486,17 @@ static innr_status knn_exact_range(innr_batch* b_full, int metric, const float* 
         view.index_base = b_full->index_base;
         b = &view;
     }
-    const uint32_t KP = pick_kp(kout, 0);
-    const uint32_t cap = exact_cap(KP);
-    const size_t cols = (b == &view) ? round_up(limit_n, kScanChunk) : b->ldN;  // columns that are scanned
-    const size_t nchunks = cols / kScanChunk;
-    // wave slots: fill the chip to the occupancy the register budget allows (HBM latency needs the waves: the
-    // single-query kernel holds 72 VGPRs = 7 waves/SIMD) but never more than there are chunks
-    const size_t waves_per_cu = nq >= 8 ? 16 : 24;
-    size_t nslots = cap_scan_slots(c, std::min<size_t>(nchunks, (size_t)c->num_cus * waves_per_cu));
-    nslots = round_up(nslots, kScanThreads / 64);
-    const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
-    const uint32_t nblocks = (uint32_t)(nslots / (kScanThreads / 64));
-    constexpr uint32_t QBMAX = 8;
-    // A corpus that stays in the Infinity Cache (<= 128 MB) is cheap to re-read and too small to fill the chip with
-    // one group of 8 queries: all the 8-query groups go into ONE launch (blockIdx.y), within 256 MB of list space.
-    // Large corpora keep one group per launch (each launch streams HBM once and fills the chip by itself).
-    size_t max_groups = 1;
-    if (cols * b->D * sizeof(float) <= (size_t)128 << 20)
-        max_groups = std::max<size_t>(1, ((size_t)256 << 20) / (nslots * QBMAX * cap * sizeof(uint64_t)));
-    max_groups = std::min<size_t>(max_groups, 65535);
-    const bool l2 = metric == INNR_METRIC_L2SQ;
-    size_t done = 0;
-    while (done < nq) {
-        const size_t rem = nq - done;
-        // One corpus pass serves 8, 4 or 1 queries. A ragged tail of 5-7 (2-3) queries takes ONE 8- (4-) query pass with
-        // zero rows as padding instead of several smaller passes (2 queries: 5.5 ms instead of 2 x 5.2 at 10M x 768).
-        const uint32_t qb = rem >= 5 ? 8 : (rem >= 2 ? 4 : 1);
-        const uint32_t groups = (qb == 8 && rem >= 8) ? (uint32_t)std::min<size_t>(rem / 8, max_groups) : 1u;
-        const uint32_t nql = qb * groups;                               // query slots of this launch
-        const uint32_t nreal = (uint32_t)std::min<size_t>(nql, rem);    // ... of which real queries
-        INNR_TRY(c->lists.ensure(nslots * nql * cap * sizeof(uint64_t)));
-        INNR_TRY(c->counts.ensure(nslots * nql * sizeof(uint32_t)));
-        const float* q = dQ + (q0 + done) * ldq;
-        const float* qn = dQn ? dQn + q0 + done : nullptr;
-        if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qn));
-        ScanExt ext2 = ext;
-        if (nreal < nql) ext2.nvalid = nreal;
-        INNR_TRY(launch_scan_filter(b, metric, qb, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2, groups));
-        INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, l2, d_out_idx + (q0 + done) * kout,
-                                 d_out_score + (q0 + done) * kout));
-        done += nreal;
-    }
-    return INNR_OK;
+    const size_t cols = (b == &view) ? round_up(limit_n, kScanChunk) : b->ldN;
+    // waves: fill the chip to the occupancy the register budget allows (HBM latency needs the waves: the single-query kernel holds
+    // 72 VGPRs = 7 waves/SIMD)
+    const ScanGeom g = {cols, kScanChunk, nq >= 8 ? 16u : 24u, kScanThreads / 64, cols * b->D * sizeof(float), metric == INNR_METRIC_L2SQ};
+    return exact_scan_rounds(b, g, dQ, ldq, dQn, q0, nq, kout, d_out_idx, d_out_score,
+                             [&](uint32_t qb, const float* q, const float* qn, uint32_t nblocks, uint32_t nql, uint32_t KP, uint32_t cap,
+                                 uint32_t cps, uint32_t groups, uint32_t nreal) {
+                                 ScanExt ext2 = ext;
+                                 if (nreal < nql) ext2.nvalid = nreal;
+                                 return launch_scan_filter(b, metric, qb, q, ldq, qn, nblocks, nql, KP, cap, cps, ext2, groups);
+                             });
 }
 
 // ---- GEMM engine -------------------------------------------------------------------------------------
@@ -3101,40 +3124,14 @@ static innr_status launch_scan_u8(innr_batch* b, uint32_t qb, const float* dQ, s
 static innr_status knn_u8_exact_range(innr_batch* b, const float* dQ, size_t ldq, const float* qsum, size_t q0, size_t nq,
                                       size_t kout, uint64_t* d_out_idx, float* d_out_score, size_t limit_n = 0,
                                       const uint8_t* mask = nullptr) {
-    innr_ctx* c = b->ctx;
-    const uint32_t KP = pick_kp(kout, 0);
-    const uint32_t cap = exact_cap(KP);
-    const size_t cols = (limit_n && limit_n < b->N) ? round_up(limit_n, kU8Chunk) : b->ldN;  // columns that are scanned
-    const size_t nchunks = cols / kU8Chunk;
-    size_t nslots = cap_scan_slots(c, std::min<size_t>(nchunks, (size_t)c->num_cus * 16));
-    nslots = round_up(nslots, 4);
-    const uint32_t cps = (uint32_t)((nchunks + nslots - 1) / nslots);
-    const uint32_t nblocks = (uint32_t)(nslots / 4);
-    // a code corpus that stays in the Infinity Cache: all 4-query groups in one launch (see knn_exact_range)
-    size_t max_groups = 1;
-    if (cols * b->D <= (size_t)128 << 20)
-        max_groups = std::max<size_t>(1, ((size_t)256 << 20) / (nslots * 8 * cap * sizeof(uint64_t)));
-    max_groups = std::min<size_t>(max_groups, 65535);
-    size_t done = 0;
-    while (done < nq) {
-        const size_t rem = nq - done;
-        // 2-3 queries: one 4-query pass padded with zero rows, 5-7: one 8-query pass (cf. knn_exact_range); the 8-query pass
-        // costs less than two of 4 (one corpus stream, one widening of each code)
-        const uint32_t qb = rem >= 5 ? 8 : (rem >= 2 ? 4 : 1);
-        const uint32_t groups = (qb > 1 && rem >= qb) ? (uint32_t)std::min<size_t>(rem / qb, max_groups) : 1u;
-        const uint32_t nql = qb * groups;
-        const uint32_t nreal = (uint32_t)std::min<size_t>(nql, rem);
-        INNR_TRY(c->lists.ensure(nslots * nql * cap * sizeof(uint64_t)));
-        INNR_TRY(c->counts.ensure(nslots * nql * sizeof(uint32_t)));
-        const float* q = dQ + (q0 + done) * ldq;
-        const float* qs = qsum + q0 + done;
-        if (nreal < nql) INNR_TRY(pad_queries(c, ldq, b->D, nql, nreal, &q, &qs));
-        INNR_TRY(launch_scan_u8(b, qb, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n, nreal < nql ? nreal : 0xFFFFFFFFu, mask));
-        INNR_TRY(select_and_emit(b, (uint32_t)nslots, nql, cap, KP, nreal, kout, false, d_out_idx + (q0 + done) * kout,
-                                 d_out_score + (q0 + done) * kout));
-        done += nreal;
-    }
-    return INNR_OK;
+    const size_t cols = (limit_n && limit_n < b->N) ? round_up(limit_n, kU8Chunk) : b->ldN;
+    const ScanGeom g = {cols, kU8Chunk, 16, 4, cols * b->D, false};
+    return exact_scan_rounds(b, g, dQ, ldq, qsum, q0, nq, kout, d_out_idx, d_out_score,
+                             [&](uint32_t qb, const float* q, const float* qs, uint32_t nblocks, uint32_t nql, uint32_t KP, uint32_t cap,
+                                 uint32_t cps, uint32_t groups, uint32_t nreal) {
+                                 return launch_scan_u8(b, qb, q, ldq, qs, nblocks, KP, cap, cps, groups, limit_n,
+                                                       nreal < nql ? nreal : 0xFFFFFFFFu, mask);
+                             });
 }
 
 // unproven queries of the u8 GEMM / int8 engines: gathered and redone together on the exact engine (4 per corpus pass)
@@ -3966,33 +3963,94 @@ static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
 
 // The masked exact scan on the batch itself (INNR_KNN_EXACT, or no room for a selection): scan_filter_kernel<..., EXT> with the
 // normalised mask for every query, or beyond INNR_MAX_K all N scores of one query at a time and a full sort with the failing
-// vectors keyed last (as knn_l2_ext does it). kout <= npass.
+// vectors keyed last (as knn_l2_ext does it). metric -1: a code batch -- scan_u8_filter_kernel<..., MASK>, or the masked full sort.
+// kout <= npass.
 static innr_status knn_masked_exact(innr_batch* b, int metric, const float* dQ, size_t Q, size_t D, size_t kout, size_t npass,
                                     uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats) {
     innr_ctx* c = b->ctx;
     const uint8_t* nm = c->flt_mask.as<uint8_t>();
     INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
     INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
-    const float* dQn = nullptr;
-    if (metric == INNR_METRIC_COSINE) {
+    const float* aux = nullptr;  // the per-query value: the norms for cosine, the sums for a code batch
+    if (metric < 0) {
+        INNR_TRY(c->q_norm.ensure(2 * round_up(Q, kBQmax) * sizeof(float)));
+        float* qsum = c->q_norm.as<float>();
+        query_sums_kernel<<<(unsigned)((Q + 63) / 64), 64, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)D, D, qsum, qsum + round_up(Q, kBQmax));
+        INNR_HIP_CHECK(hipGetLastError());
+        aux = qsum;
+    } else if (metric == INNR_METRIC_COSINE) {
         INNR_TRY(ensure_norms(b));
         INNR_TRY(c->q_norm.ensure(Q * sizeof(float)));
         query_norms_kernel<<<(unsigned)Q, 64, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)D, D, c->q_norm.as<float>());
         INNR_HIP_CHECK(hipGetLastError());
-        dQn = c->q_norm.as<float>();
+        aux = c->q_norm.as<float>();
     }
     uint32_t kept;
     if (kout > INNR_MAX_K) {
-        INNR_TRY(knn_full_sort(b, metric, dQ, D, dQn, Q, kout, d_out_idx, d_out_score, nm));
+        INNR_TRY(knn_full_sort(b, metric, dQ, D, aux, Q, kout, d_out_idx, d_out_score, nm));
         kept = (uint32_t)npass;
     } else {
-        ScanExt ext;
-        ext.mask = nm;
-        INNR_TRY(knn_exact_range(b, metric, dQ, D, dQn, 0, Q, kout, d_out_idx, d_out_score, ext));
+        if (metric < 0) {
+            INNR_TRY(knn_u8_exact_range(b, dQ, D, aux, 0, Q, kout, d_out_idx, d_out_score, 0, nm));
+        } else {
+            ScanExt ext;
+            ext.mask = nm;
+            INNR_TRY(knn_exact_range(b, metric, dQ, D, aux, 0, Q, kout, d_out_idx, d_out_score, ext));
+        }
         kept = pick_kp(kout, 0);
     }
     return finish_knn(c, INNR_KNN_EXACT, kout, 0, kept, 0.0f, out_k, stats);
 }
+
+}  // extern "C"  (a template follows; the entry points get C linkage from the header)
+
+// What innr_batch_knn_filtered_multi_dev and innr_batch_knn_u8_filtered_dev do once their arguments are checked: the mask, the
+// selection, the search, the remap. knn(batch): the caller's engine on a batch (b itself, or its selection);
+// masked(kout, npass): the masked exact scan on b.
+template <class Knn, class Masked>
+static innr_status knn_filtered_dev(innr_batch* b, size_t Q, size_t k, const uint8_t* d_mask, int engine, uint64_t* d_out_idx,
+                                    size_t* out_k, innr_knn_stats* stats, Knn&& knn, Masked&& masked) {
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    INNR_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
+    size_t npass = 0;
+    bool same = false;
+    INNR_TRY(filter_mask(b, d_mask, &npass, &same));
+    if (npass == 0) return INNR_OK;  // batch.rs:841-847
+    const size_t kout = std::min(k, npass);  // batch.rs:849
+    if (npass == b->N) {
+        // every vector passes: the batch itself, no selection
+        INNR_TRY(knn(b));
+    } else {
+        bool have = same;
+        if (engine != INNR_KNN_EXACT && !same) INNR_TRY(build_selection(b, npass, &have));
+        if (engine != INNR_KNN_EXACT && have) {
+            // the selection's copies count against this batch's budget: it gets what this batch's copies and its own store leave
+            const size_t used = corpus_copy_bytes(b) + selection_base_bytes(b);
+            b->fsel->copy_budget = b->copy_budget == UINT64_MAX ? UINT64_MAX : (b->copy_budget > used ? b->copy_budget - used : 0);
+            // the caller's engine on the selection (its own index_base is 0), then selection indices -> this batch's
+            INNR_TRY(knn(b->fsel));
+            const size_t n = Q * *out_k;
+            if (n) {
+                select_remap_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d_out_idx, n, b->fsel_map, (uint32_t)npass,
+                                                                                     b->index_base);
+                INNR_HIP_CHECK(hipGetLastError());
+            }
+        } else {
+            INNR_TRY(masked(kout, npass));
+        }
+    }
+    INNR_HIP_CHECK(hipEventRecord(c->ev[5], c->stream));
+    if (!c->tune.filter_keep_selection) free_selection(b);  // (synchronises)
+    if (stats) {  // the whole call: mask, selection build, search, remap
+        float ms = 0.0f;
+        INNR_HIP_CHECK(hipEventSynchronize(c->ev[5]));
+        if (hipEventElapsedTime(&ms, c->ev[4], c->ev[5]) == hipSuccess) stats->total_ms = ms;
+    }
+    return INNR_OK;
+}
+
+extern "C" {
 
 innr_status innr_batch_knn_filtered_multi_dev(innr_batch* b, int metric, const float* d_queries, size_t Q, size_t D, size_t k,
                                               const uint8_t* d_mask, int engine, uint64_t* d_out_idx, float* d_out_score, size_t* out_k,
@@ -4017,44 +4075,12 @@ innr_status innr_batch_knn_filtered_multi_dev(innr_batch* b, int metric, const f
         return INNR_E_BAD_ARG;
     }
     if (!d_queries || !d_out_idx || !d_out_score) return INNR_E_BAD_ARG;
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    INNR_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
-    size_t npass = 0;
-    bool same = false;
-    INNR_TRY(filter_mask(b, d_mask, &npass, &same));
-    if (npass == 0) return INNR_OK;  // batch.rs:841-847
-    const size_t kout = std::min(k, npass);  // batch.rs:849
-    if (npass == b->N) {
-        // every vector passes: the batch itself, no selection
-        INNR_TRY(innr_batch_knn_dev(b, metric, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
-    } else {
-        bool have = same;
-        if (engine != INNR_KNN_EXACT && !same) INNR_TRY(build_selection(b, npass, &have));
-        if (engine != INNR_KNN_EXACT && have) {
-            // the selection's copies count against this batch's budget: it gets what this batch's copies and its own store leave
-            const size_t used = corpus_copy_bytes(b) + selection_base_bytes(b);
-            b->fsel->copy_budget = b->copy_budget == UINT64_MAX ? UINT64_MAX : (b->copy_budget > used ? b->copy_budget - used : 0);
-            // the caller's engine on the selection (its own index_base is 0), then selection indices -> this batch's
-            INNR_TRY(innr_batch_knn_dev(b->fsel, metric, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
-            const size_t n = Q * *out_k;
-            if (n) {
-                select_remap_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d_out_idx, n, b->fsel_map, (uint32_t)npass,
-                                                                                     b->index_base);
-                INNR_HIP_CHECK(hipGetLastError());
-            }
-        } else {
-            INNR_TRY(knn_masked_exact(b, metric, d_queries, Q, D, kout, npass, d_out_idx, d_out_score, out_k, stats));
-        }
-    }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[5], c->stream));
-    if (!c->tune.filter_keep_selection) free_selection(b);  // (synchronises)
-    if (stats) {  // the whole call: mask, selection build, search, remap
-        float ms = 0.0f;
-        INNR_HIP_CHECK(hipEventSynchronize(c->ev[5]));
-        if (hipEventElapsedTime(&ms, c->ev[4], c->ev[5]) == hipSuccess) stats->total_ms = ms;
-    }
-    return INNR_OK;
+    return knn_filtered_dev(
+        b, Q, k, d_mask, engine, d_out_idx, out_k, stats,
+        [&](innr_batch* on) { return innr_batch_knn_dev(on, metric, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats); },
+        [&](size_t kout, size_t npass) {
+            return knn_masked_exact(b, metric, d_queries, Q, D, kout, npass, d_out_idx, d_out_score, out_k, stats);
+        });
 }
 
 innr_status innr_batch_knn_filtered_multi(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, size_t k,
@@ -4090,29 +4116,6 @@ innr_status innr_batch_knn_filtered_multi(innr_batch* b, int metric, const float
 }
 
 // ---- batch_knn_u8 over the vectors that pass a mask: innr_batch_knn_filtered_multi's scheme on a code batch ----
-// The masked exact scan on the code batch itself: scan_u8_filter_kernel<..., MASK> with the normalised mask for every query, or
-// beyond INNR_MAX_K the masked full sort. kout <= npass.
-static innr_status knn_u8_masked_exact(innr_batch* b, const float* dQ, size_t Q, size_t D, size_t kout, size_t npass,
-                                       uint64_t* d_out_idx, float* d_out_score, size_t* out_k, innr_knn_stats* stats) {
-    innr_ctx* c = b->ctx;
-    const uint8_t* nm = c->flt_mask.as<uint8_t>();
-    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
-    INNR_TRY(c->q_norm.ensure(2 * round_up(Q, kBQmax) * sizeof(float)));
-    float* qsum = c->q_norm.as<float>();
-    query_sums_kernel<<<(unsigned)((Q + 63) / 64), 64, 0, c->stream>>>(dQ, (uint32_t)Q, (uint32_t)D, D, qsum, qsum + round_up(Q, kBQmax));
-    INNR_HIP_CHECK(hipGetLastError());
-    uint32_t kept;
-    if (kout > INNR_MAX_K) {
-        INNR_TRY(knn_full_sort(b, -1, dQ, D, qsum, Q, kout, d_out_idx, d_out_score, nm));
-        kept = (uint32_t)npass;
-    } else {
-        INNR_TRY(knn_u8_exact_range(b, dQ, D, qsum, 0, Q, kout, d_out_idx, d_out_score, 0, nm));
-        kept = pick_kp(kout, 0);
-    }
-    return finish_knn(c, INNR_KNN_EXACT, kout, 0, kept, 0.0f, out_k, stats);
-}
-
 // the checks the two entry points share, in the reference's order (scalar.rs:376-378: an empty corpus or k == 0 before any dimension
 // assert); *empty: nothing to search, *out_k stays 0
 static innr_status knn_u8_filtered_args(innr_batch* b, size_t Q, size_t D, size_t k, const uint8_t* mask, size_t* out_k,
@@ -4144,44 +4147,10 @@ innr_status innr_batch_knn_u8_filtered_dev(innr_batch* b, const float* d_queries
         set_error("queries / output buffers are null");
         return INNR_E_BAD_ARG;
     }
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    INNR_HIP_CHECK(hipEventRecord(c->ev[4], c->stream));
-    size_t npass = 0;
-    bool same = false;
-    INNR_TRY(filter_mask(b, d_mask, &npass, &same));
-    if (npass == 0) return INNR_OK;
-    const size_t kout = std::min(k, npass);
-    if (npass == b->N) {
-        // every vector passes: the batch itself, no selection
-        INNR_TRY(innr_batch_knn_u8_dev(b, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
-    } else {
-        bool have = same;
-        if (engine != INNR_KNN_EXACT && !same) INNR_TRY(build_selection(b, npass, &have));
-        if (engine != INNR_KNN_EXACT && have) {
-            // the selection's int8 copy counts against this batch's budget: it gets what this batch's copies and its own store leave
-            const size_t used = corpus_copy_bytes(b) + selection_base_bytes(b);
-            b->fsel->copy_budget = b->copy_budget == UINT64_MAX ? UINT64_MAX : (b->copy_budget > used ? b->copy_budget - used : 0);
-            // the caller's engine on the selection (its own index_base is 0), then selection indices -> this batch's
-            INNR_TRY(innr_batch_knn_u8_dev(b->fsel, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats));
-            const size_t n = Q * *out_k;
-            if (n) {
-                select_remap_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(d_out_idx, n, b->fsel_map, (uint32_t)npass,
-                                                                                     b->index_base);
-                INNR_HIP_CHECK(hipGetLastError());
-            }
-        } else {
-            INNR_TRY(knn_u8_masked_exact(b, d_queries, Q, D, kout, npass, d_out_idx, d_out_score, out_k, stats));
-        }
-    }
-    INNR_HIP_CHECK(hipEventRecord(c->ev[5], c->stream));
-    if (!c->tune.filter_keep_selection) free_selection(b);  // (synchronises)
-    if (stats) {  // the whole call: mask, selection build, search, remap
-        float ms = 0.0f;
-        INNR_HIP_CHECK(hipEventSynchronize(c->ev[5]));
-        if (hipEventElapsedTime(&ms, c->ev[4], c->ev[5]) == hipSuccess) stats->total_ms = ms;
-    }
-    return INNR_OK;
+    return knn_filtered_dev(
+        b, Q, k, d_mask, engine, d_out_idx, out_k, stats,
+        [&](innr_batch* on) { return innr_batch_knn_u8_dev(on, d_queries, Q, D, k, engine, d_out_idx, d_out_score, out_k, stats); },
+        [&](size_t kout, size_t npass) { return knn_masked_exact(b, -1, d_queries, Q, D, kout, npass, d_out_idx, d_out_score, out_k, stats); });
 }
 
 innr_status innr_batch_knn_u8_filtered(innr_batch* b, const float* queries, size_t Q, size_t D, size_t k, const uint8_t* mask, int engine,
@@ -4510,6 +4479,111 @@ struct RangeScan {  // one launch of range_scan_kernel: nq queries (row-major, s
     uint64_t cap;
 };
 
+// A range search on device memory, f32 or code corpus: rounds of at most kRangeMaxRound queries -- the collect path where it serves
+// the call (one filter launch, exact scores of what it collected, the predicate on those bits; queries it cannot prove are redone by
+// the exact scan through a query map), else the exact scan for every query: a count launch, offsets, an emit launch. The policy P
+// (RangeF32, RangeU8) has what depends on the kind of corpus:
+//   kChunk, kRoundExtra, kEngine   vectors per count, bytes of per-query values per round, the engine the collect path reports
+//   l2                             smaller is better
+//   wants_collect(Q, engine, &collect, &nfallback)   whether the collect path serves the call (and what that needs: norms, a copy)
+//   carve(round)                   its per-query values in c->q_norm, for a round of that many queries
+//   prepare(collect, Qp, nq, &a)   those values for a round's queries; a.qnorm where the exact scan serves them all
+//   collect(Qp, thr, nq, lg, ldb, cnt, ldc, bad)     the collect step up to and including range_mark_kernel
+//   scan<EMIT>(a)                  one launch of the exact scan
+template <class P>
+static innr_status range_search_rounds(P& p, innr_batch* b, const float* dQ, size_t Q, const float* dThr, int engine, uint64_t* d_off,
+                                       uint64_t* d_idx, float* d_sc, size_t cap, size_t* out_total, innr_knn_stats* stats) {
+    innr_ctx* c = b->ctx;
+    const size_t D = b->D, nchunks = b->ldN / P::kChunk, ldc = nchunks + 1, ldb = b->ldN / 32;
+    uint32_t nfallback = 0, kept = 0;
+    float gemm_ms = 0.0f;
+    bool collect = false;
+    INNR_TRY(p.wants_collect(Q, engine, &collect, &nfallback));
+    const size_t per_query = (ldc + 2) * sizeof(uint32_t) + P::kRoundExtra +
+                             (collect ? ldb * sizeof(uint32_t) + (size_t)kCollectCap * (sizeof(uint32_t) + sizeof(uint64_t)) : 0);
+    const size_t round = std::min(Q, std::max<size_t>(1, std::min(kRangeMaxRound, kRangeWorkspace / per_query)));
+    INNR_TRY(c->rs_cnt.ensure(round * ldc * sizeof(uint32_t)));
+    INNR_TRY(c->rs_tot.ensure(2 * round * sizeof(uint32_t)));
+    INNR_TRY(p.carve(round));
+    if (collect) INNR_TRY(c->rs_bits.ensure(round * ldb * sizeof(uint32_t)));
+    uint32_t* cnt = c->rs_cnt.as<uint32_t>();
+    uint32_t* tot = c->rs_tot.as<uint32_t>();
+    uint32_t* bad = tot + round;
+    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
+    INNR_HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), c->stream));  // the running base, carried in the offsets themselves
+    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+    for (size_t q0 = 0; q0 < Q; q0 += round) {
+        const size_t nq = std::min(round, Q - q0);
+        const float* Qp = dQ + q0 * D;
+        const float* thr = dThr + q0;
+        uint64_t* off = d_off + q0;
+        // the queries the exact scan serves: all of them, or after a collect pass the bad ones (gathered, with a map to their rows)
+        RangeScan a = {Qp, nullptr, thr, nullptr, (uint32_t)nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap};
+        INNR_TRY(p.prepare(collect, Qp, nq, &a));
+        const dim3 lg(kCollectCap / 256, (unsigned)nq);  // (blocks beyond a query's list length return at once)
+        if (collect) {
+            INNR_TRY(p.collect(Qp, thr, nq, lg, ldb, cnt, ldc, bad));
+            // which queries the exact scan finishes, and how long the lists got (one synchronisation per round)
+            std::vector<uint32_t> hb(2 * nq);
+            INNR_HIP_CHECK(hipMemcpyAsync(hb.data(), bad, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            INNR_HIP_CHECK(hipMemcpyAsync(hb.data() + nq, c->counts.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            INNR_HIP_CHECK(hipStreamSynchronize(c->stream));
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms += ms;
+            std::vector<uint32_t> redo;
+            for (size_t j = 0; j < nq; ++j) {
+                if (hb[j]) redo.push_back((uint32_t)j);
+                kept = std::max(kept, std::min(hb[nq + j], kCollectCap));
+            }
+            nfallback += (uint32_t)redo.size();
+            a.nq = (uint32_t)redo.size();
+            if (a.nq) {  // gathered: their rows (rb.q), thresholds (rb.qn) and per-query values (rb.sc); rb.map = the rows of cnt / off
+                innr_ctx::RedoBufs& rb = c->cmpl;
+                INNR_TRY(upload_redo(c, rb, redo, D, 1));
+                const uint32_t* map = rb.map.as<uint32_t>();
+                gather_rows_kernel<<<(unsigned)(((size_t)a.nq * D + 255) / 256), 256, 0, c->stream>>>(Qp, map, a.nq, (uint32_t)D, rb.q.as<float>());
+                gather_f32_kernel<<<(a.nq + 255) / 256, 256, 0, c->stream>>>(thr, map, a.nq, rb.qn.as<float>());
+                // (the exact norms the collect pass left, or the sums: either way the round's first values of q_norm)
+                gather_f32_kernel<<<(a.nq + 255) / 256, 256, 0, c->stream>>>(c->q_norm.as<float>(), map, a.nq, rb.sc.as<float>());
+                INNR_HIP_CHECK(hipGetLastError());
+                a.Q = rb.q.as<float>();
+                a.thr = rb.qn.as<float>();
+                a.qnorm = rb.sc.as<float>();
+                a.qmap = map;
+            }
+        }
+        if (a.nq) INNR_TRY(p.template scan<false>(a));
+        range_chunk_scan_kernel<<<(unsigned)nq, 1024, 0, c->stream>>>(cnt, ldc, (uint32_t)nchunks, tot);
+        range_offsets_kernel<<<1, 1024, 0, c->stream>>>(tot, (uint32_t)nq, off);
+        INNR_HIP_CHECK(hipGetLastError());
+        if (cap == 0) continue;  // a count-only call
+        if (a.nq) INNR_TRY(p.template scan<true>(a));
+        if (collect) {
+            range_scatter_kernel<P::kChunk><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, p.l2,
+                                                                       c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx,
+                                                                       d_sc, (uint64_t)cap);
+            INNR_HIP_CHECK(hipGetLastError());
+        }
+    }
+    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
+    uint64_t total = 0;
+    INNR_HIP_CHECK(copy_out(c, &total, d_off + Q, sizeof(total)));
+    INNR_TRY(check_errflag(c));  // (synchronises)
+    *out_total = (size_t)total;
+    if (stats) {
+        float ms = 0.0f;
+        if (!collect && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms = ms;
+        stats->engine = collect ? P::kEngine : INNR_KNN_EXACT;
+        stats->queries_fallback = nfallback;
+        stats->candidates_kept = kept;
+        stats->gemm_ms = gemm_ms;
+        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
+    }
+    return INNR_OK;
+}
+
 // eight, four or one query per corpus pass, never more than there are queries (the kernel's last group ends on the last query)
 template <bool EMIT>
 static innr_status launch_range_scan(innr_batch* b, int metric, const RangeScan& a) {
@@ -4528,114 +4602,57 @@ static innr_status launch_range_scan(innr_batch* b, int metric, const RangeScan&
     return INNR_OK;
 }
 
+struct RangeF32 {  // range_search_rounds on an f32 batch: the f32 collect pass (it serves the bf16 / int8 requests too)
+    static constexpr int kChunk = kScanChunk;
+    static constexpr size_t kRoundExtra = 0;
+    static constexpr int kEngine = INNR_KNN_MFMA;
+    innr_batch* b;
+    int metric;
+    bool cos, l2;
+
+    innr_status wants_collect(size_t Q, int engine, bool* collect, uint32_t* nfallback) {
+        *collect = engine != INNR_KNN_EXACT;
+        if (engine == INNR_KNN_AUTO) *collect = Q >= kRangeAutoQ0;
+        if (!gemm_addressable(b, std::min(Q, kRangeMaxRound)) || b->D == 0) *collect = false;
+        if (*collect || cos) INNR_TRY(ensure_norms(b));
+        if (*collect && !(b->max_norm >= 1e-12f && b->max_norm <= 1e18f)) {
+            // the corpus' largest norm outside the range the filter's error bound is good for (non-finite values included)
+            *collect = false;
+            *nfallback = (uint32_t)Q;
+        }
+        return INNR_OK;
+    }
+    innr_status carve(size_t) { return INNR_OK; }  // (the collect pass sizes q_norm itself, prepare() for the exact scan)
+    innr_status prepare(bool collect, const float* Qp, size_t nq, RangeScan* a) {
+        if (collect || !cos) return INNR_OK;
+        innr_ctx* c = b->ctx;
+        INNR_TRY(c->q_norm.ensure(nq * sizeof(float)));
+        query_norms_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(Qp, (uint32_t)nq, (uint32_t)b->D, b->D, c->q_norm.as<float>());
+        INNR_HIP_CHECK(hipGetLastError());
+        a->qnorm = c->q_norm.as<float>();
+        return INNR_OK;
+    }
+    innr_status collect(const float* Qp, const float* thr, size_t nq, dim3 lg, size_t ldb, uint32_t* cnt, size_t ldc, uint32_t* bad) {
+        innr_ctx* c = b->ctx;
+        INNR_TRY(collect_pass(b, metric, Qp, nq, 1, thr));
+        bool rows = false;
+        INNR_TRY(collect_rescore(b, metric, Qp, c->q_norm.as<float>(), nq, &rows));
+        INNR_HIP_CHECK(hipMemsetAsync(c->rs_bits.p, 0, nq * ldb * sizeof(uint32_t), c->stream));
+        INNR_HIP_CHECK(hipMemsetAsync(cnt, 0, nq * ldc * sizeof(uint32_t), c->stream));
+        if (l2) range_mark_kernel<true><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr, c->seed_score.as<uint32_t>(), c->q_norm.as<float>(), c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
+        else range_mark_kernel<false><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr, c->seed_score.as<uint32_t>(), c->q_norm.as<float>(), c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
+        INNR_HIP_CHECK(hipGetLastError());
+        return INNR_OK;
+    }
+    template <bool EMIT>
+    innr_status scan(const RangeScan& a) { return launch_range_scan<EMIT>(b, metric, a); }
+};
+
 static innr_status range_search_dev(innr_batch* b, int metric, const float* dQ, size_t Q, const float* dThr, int engine,
                                     uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t cap, size_t* out_total,
                                     innr_knn_stats* stats) {
-    innr_ctx* c = b->ctx;
-    const bool cos = metric == INNR_METRIC_COSINE, l2 = metric == INNR_METRIC_L2SQ;
-    const size_t D = b->D, nchunks = b->ldN / kScanChunk, ldc = nchunks + 1, ldb = b->ldN / 32;
-    bool collect = engine != INNR_KNN_EXACT;  // (the bf16 / int8 requests: the f32 collect pass serves them)
-    if (engine == INNR_KNN_AUTO) collect = Q >= kRangeAutoQ0;
-    if (!gemm_addressable(b, std::min(Q, kRangeMaxRound)) || D == 0) collect = false;
-    uint32_t nfallback = 0, kept = 0;
-    float gemm_ms = 0.0f;
-    if (collect || cos) INNR_TRY(ensure_norms(b));
-    if (collect && !(b->max_norm >= 1e-12f && b->max_norm <= 1e18f)) {
-        // the corpus' largest norm outside the range the filter's error bound is good for (non-finite values included)
-        collect = false;
-        nfallback = (uint32_t)Q;
-    }
-    const size_t per_query = (ldc + 2) * sizeof(uint32_t) +
-                             (collect ? ldb * sizeof(uint32_t) + (size_t)kCollectCap * (sizeof(uint32_t) + sizeof(uint64_t)) : 0);
-    const size_t round = std::min(Q, std::max<size_t>(1, std::min(kRangeMaxRound, kRangeWorkspace / per_query)));
-    INNR_TRY(c->rs_cnt.ensure(round * ldc * sizeof(uint32_t)));
-    INNR_TRY(c->rs_tot.ensure(2 * round * sizeof(uint32_t)));
-    if (collect) INNR_TRY(c->rs_bits.ensure(round * ldb * sizeof(uint32_t)));
-    uint32_t* cnt = c->rs_cnt.as<uint32_t>();
-    uint32_t* tot = c->rs_tot.as<uint32_t>();
-    uint32_t* bad = tot + round;
-    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
-    INNR_HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), c->stream));  // the running base, carried in the offsets themselves
-    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-    for (size_t q0 = 0; q0 < Q; q0 += round) {
-        const size_t nq = std::min(round, Q - q0);
-        const float* Qp = dQ + q0 * D;
-        const float* thr = dThr + q0;
-        uint64_t* off = d_off + q0;
-        RangeScan a = {Qp, nullptr, thr, nullptr, (uint32_t)nq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap};
-        const dim3 lg(kCollectCap / 256, (unsigned)nq);  // (blocks beyond a query's list length return at once)
-        if (collect) {
-            INNR_TRY(collect_pass(b, metric, Qp, nq, 1, thr));
-            bool rows = false;
-            INNR_TRY(collect_rescore(b, metric, Qp, c->q_norm.as<float>(), nq, &rows));
-            INNR_HIP_CHECK(hipMemsetAsync(c->rs_bits.p, 0, nq * ldb * sizeof(uint32_t), c->stream));
-            INNR_HIP_CHECK(hipMemsetAsync(cnt, 0, nq * ldc * sizeof(uint32_t), c->stream));
-            if (l2) range_mark_kernel<true><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr, c->seed_score.as<uint32_t>(), c->q_norm.as<float>(), c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
-            else range_mark_kernel<false><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr, c->seed_score.as<uint32_t>(), c->q_norm.as<float>(), c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
-            INNR_HIP_CHECK(hipGetLastError());
-            // which queries the exact scan finishes, and how long the lists got (one synchronisation per round)
-            std::vector<uint32_t> hb(2 * nq);
-            INNR_HIP_CHECK(hipMemcpyAsync(hb.data(), bad, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            INNR_HIP_CHECK(hipMemcpyAsync(hb.data() + nq, c->counts.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            INNR_HIP_CHECK(hipStreamSynchronize(c->stream));
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms += ms;
-            std::vector<uint32_t> redo;
-            for (size_t j = 0; j < nq; ++j) {
-                if (hb[j]) redo.push_back((uint32_t)j);
-                kept = std::max(kept, std::min(hb[nq + j], kCollectCap));
-            }
-            nfallback += (uint32_t)redo.size();
-            a.nq = (uint32_t)redo.size();
-            if (a.nq) {  // gathered: their rows (rb.q), thresholds (rb.qn) and exact norms (rb.sc); rb.map = the rows of cnt / off
-                innr_ctx::RedoBufs& rb = c->cmpl;
-                INNR_TRY(upload_redo(c, rb, redo, D, 1));
-                const uint32_t* map = rb.map.as<uint32_t>();
-                gather_rows_kernel<<<(unsigned)(((size_t)a.nq * D + 255) / 256), 256, 0, c->stream>>>(Qp, map, a.nq, (uint32_t)D, rb.q.as<float>());
-                gather_f32_kernel<<<(a.nq + 255) / 256, 256, 0, c->stream>>>(thr, map, a.nq, rb.qn.as<float>());
-                gather_f32_kernel<<<(a.nq + 255) / 256, 256, 0, c->stream>>>(c->q_norm.as<float>(), map, a.nq, rb.sc.as<float>());
-                INNR_HIP_CHECK(hipGetLastError());
-                a.Q = rb.q.as<float>();
-                a.thr = rb.qn.as<float>();
-                a.qnorm = rb.sc.as<float>();
-                a.qmap = map;
-            }
-        } else if (cos) {
-            INNR_TRY(c->q_norm.ensure(nq * sizeof(float)));
-            query_norms_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(Qp, (uint32_t)nq, (uint32_t)D, D, c->q_norm.as<float>());
-            INNR_HIP_CHECK(hipGetLastError());
-            a.qnorm = c->q_norm.as<float>();
-        }
-        if (a.nq) INNR_TRY(launch_range_scan<false>(b, metric, a));
-        range_chunk_scan_kernel<<<(unsigned)nq, 1024, 0, c->stream>>>(cnt, ldc, (uint32_t)nchunks, tot);
-        range_offsets_kernel<<<1, 1024, 0, c->stream>>>(tot, (uint32_t)nq, off);
-        INNR_HIP_CHECK(hipGetLastError());
-        if (cap == 0) continue;  // a count-only call
-        if (a.nq) INNR_TRY(launch_range_scan<true>(b, metric, a));
-        if (collect) {
-            range_scatter_kernel<256><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, l2,
-                                                                 c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx, d_sc,
-                                                                 (uint64_t)cap);
-            INNR_HIP_CHECK(hipGetLastError());
-        }
-    }
-    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
-    uint64_t total = 0;
-    INNR_HIP_CHECK(copy_out(c, &total, d_off + Q, sizeof(total)));
-    INNR_TRY(check_errflag(c));  // (synchronises)
-    *out_total = (size_t)total;
-    if (stats) {
-        float ms = 0.0f;
-        if (!collect && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms = ms;
-        stats->engine = collect ? INNR_KNN_MFMA : INNR_KNN_EXACT;
-        stats->queries_fallback = nfallback;
-        stats->candidates_kept = kept;
-        stats->gemm_ms = gemm_ms;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
-    }
-    return INNR_OK;
+    RangeF32 p = {b, metric, metric == INNR_METRIC_COSINE, metric == INNR_METRIC_L2SQ};
+    return range_search_rounds(p, b, dQ, Q, dThr, engine, d_off, d_idx, d_sc, cap, out_total, stats);
 }
 
 // the argument checks both entry points share; *empty: nothing to search, the offsets are all zero
@@ -4682,19 +4699,18 @@ static innr_status range_search_args(innr_batch* b, int metric, const float* que
 //   1024   12.83 / 1.00   459.91 / 11.64   1774.8 / 69.76
 constexpr size_t kRangeU8AutoQ0 = 16;
 
-// the exact scan's two launches per round; qmap: see range_scan_u8_kernel
+// the exact scan's two launches per round (a.qnorm: the queries' sums); qmap: see range_scan_u8_kernel
 template <bool EMIT>
-static innr_status launch_range_scan_u8(innr_batch* b, const float* dQ, const float* qsum, const float* thr, const uint32_t* qmap,
-                                        uint32_t nq, uint32_t* cnt, size_t ldc, const uint64_t* qoff, uint64_t* out_idx, float* out_score,
-                                        uint64_t cap) {
+static innr_status launch_range_scan_u8(innr_batch* b, const RangeScan& a) {
     innr_ctx* c = b->ctx;
     const size_t nchunks = b->ldN / kU8Chunk;
-    const uint32_t qb = nq >= 8 ? 8 : (nq >= 4 ? 4 : 1);  // never more than there are queries: the last group ends on the last query
+    const uint32_t qb = a.nq >= 8 ? 8 : (a.nq >= 4 ? 4 : 1);  // never more than there are queries: the last group ends on the last query
     // waves per CU as the exact u8 kNN scan (knn_u8_exact_range): 16
-    const dim3 grid((unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * 4), (nq + qb - 1) / qb);
+    const dim3 grid((unsigned)std::min<size_t>((nchunks + 3) / 4, (size_t)c->num_cus * 4), (a.nq + qb - 1) / qb);
     dispatch([&](auto QB) {
-        launch_kernel(c, Inst<kLaunchRangeScanU8, QB, EMIT>(), {grid, 256, 0, grid.y}, b->C8, b->ldN, (uint32_t)b->N, (uint32_t)b->D, dQ,
-                      b->D, qsum, b->alpha / 255.0f, b->offset, thr, nq, cnt, ldc, qoff, b->index_base, out_idx, out_score, cap, qmap);
+        launch_kernel(c, Inst<kLaunchRangeScanU8, QB, EMIT>(), {grid, 256, 0, grid.y}, b->C8, b->ldN, (uint32_t)b->N, (uint32_t)b->D, a.Q,
+                      b->D, a.qnorm, b->alpha / 255.0f, b->offset, a.thr, a.nq, a.cnt, a.ldc, a.qoff, b->index_base, a.out_idx, a.out_score,
+                      a.cap, a.qmap);
     }, one_of<8, 4, 1>(qb));
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
@@ -4727,132 +4743,72 @@ static innr_status range_u8_wants_collect(innr_batch* b, size_t Q, int engine, b
     return INNR_OK;
 }
 
-// The collect path mirrors range_search_dev's for a code batch: one MODE 2 pass of the int8 filter per round with the fixed
-// thresholds ord(thr_j - E_j) (E_j: rescore_u8_kernel's whole bound), exact scores of everything collected from the K-packed copy,
-// the exact predicate on those bits, and the finish in index order. Queries without a finite collect threshold are closed before
-// the launch and, like those whose list ran past kCollectCap, finished by the exact scan through a query map.
+// range_search_rounds on a code batch. The collect path: one MODE 2 pass of the int8 filter per round with the fixed thresholds
+// ord(thr_j - E_j) (E_j: rescore_u8_kernel's whole bound), exact scores of everything collected from the K-packed copy, the exact
+// predicate on those bits, and the finish in index order. Queries without a finite collect threshold are closed before the launch
+// and, like those whose list ran past kCollectCap, finished by the exact scan through a query map.
+struct RangeU8 {
+    static constexpr int kChunk = kU8Chunk;
+    static constexpr size_t kRoundExtra = 2 * sizeof(float);
+    static constexpr int kEngine = INNR_KNN_MFMA_I8;
+    static constexpr bool l2 = false;
+    innr_batch* b;
+    float *qsum, *qnorm;  // the round's sums and norms: q_norm, [round] each
+
+    innr_status wants_collect(size_t Q, int engine, bool* collect, uint32_t*) { return range_u8_wants_collect(b, Q, engine, collect); }
+    innr_status carve(size_t round) {
+        INNR_TRY(b->ctx->q_norm.ensure(2 * round * sizeof(float)));
+        qsum = b->ctx->q_norm.as<float>();
+        qnorm = qsum + round;
+        return INNR_OK;
+    }
+    innr_status prepare(bool, const float* Qp, size_t nq, RangeScan* a) {
+        query_sums_kernel<<<((uint32_t)nq + 63) / 64, 64, 0, b->ctx->stream>>>(Qp, (uint32_t)nq, (uint32_t)b->D, b->D, qsum, qnorm);
+        INNR_HIP_CHECK(hipGetLastError());
+        a->qnorm = qsum;
+        return INNR_OK;
+    }
+    innr_status collect(const float* Qp, const float* thr, size_t nq, dim3 lg, size_t ldb, uint32_t* cnt, size_t ldc, uint32_t* bad) {
+        innr_ctx* c = b->ctx;
+        I8Plan p = plan_i8(b, kCopyI8Dot, nq, 1, 32u, /*one_limb=*/true);
+        (void)plan_i8_small(b, &p, nq, false, /*collect=*/true);
+        INNR_TRY(prep_queries_i8(b, p, Qp, nq, qsum, b->alpha, b->offset));
+        const float* qc = c->misc.as<float>();
+        // fixed thresholds: thr - E (one key lower); 0 = "no bound" where that is not finite -> closed, the exact scan's
+        INNR_TRY(c->seed_score.ensure(p.Qpad * sizeof(uint32_t)));
+        uint32_t* seed = c->seed_score.as<uint32_t>();
+        seed_thresholds_u8_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(thr, (uint32_t)nq, 1u, u8_filter_scale(b), qnorm, qsum, b->offset,
+                                                                                       qc + 3 * p.Qpad, seed, (uint32_t)p.Qpad, 0u);
+        range_close_unbounded_kernel<<<((uint32_t)nq + 255) / 256, 256, 0, c->stream>>>(seed, (uint32_t)nq);
+        INNR_HIP_CHECK(hipGetLastError());
+        // global lists: [Qpad][kCollectCap] indices, [Qpad] lengths
+        INNR_TRY(c->lists.ensure(p.Qpad * (size_t)kCollectCap * sizeof(uint32_t)));
+        INNR_TRY(c->counts.ensure(p.Qpad * sizeof(uint32_t)));
+        INNR_TRY(c->sort_keys.ensure(nq * (size_t)kCollectCap * sizeof(uint64_t)));
+        INNR_HIP_CHECK(hipMemsetAsync(c->counts.p, 0, p.Qpad * sizeof(uint32_t), c->stream));
+        I8Plan pl = p;
+        pl.KP = kCollectCap;  // what the kernel takes as the list capacity
+        INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
+        INNR_TRY(launch_gemm_i8<2>(b, pl, nq, qc, nullptr, 0, seed));
+        INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
+        collect_scores_u8_kernel<<<lg, 256, 0, c->stream>>>(reinterpret_cast<const uint4*>(p.corpus), p.nk, (uint32_t)b->D, Qp, qsum,
+                                                            b->alpha / 255.0f, b->offset, c->lists.as<uint32_t>(), c->counts.as<uint32_t>(),
+                                                            kCollectCap, c->sort_keys.as<uint64_t>());
+        INNR_HIP_CHECK(hipMemsetAsync(c->rs_bits.p, 0, nq * ldb * sizeof(uint32_t), c->stream));
+        INNR_HIP_CHECK(hipMemsetAsync(cnt, 0, nq * ldc * sizeof(uint32_t), c->stream));
+        range_mark_kernel<false, (int)kU8Chunk, false><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr,
+                                                                                  seed, nullptr, c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
+        INNR_HIP_CHECK(hipGetLastError());
+        return INNR_OK;
+    }
+    template <bool EMIT>
+    innr_status scan(const RangeScan& a) { return launch_range_scan_u8<EMIT>(b, a); }
+};
+
 static innr_status range_search_u8_dev(innr_batch* b, const float* dQ, size_t Q, const float* dThr, int engine, uint64_t* d_off,
                                        uint64_t* d_idx, float* d_sc, size_t cap, size_t* out_total, innr_knn_stats* stats) {
-    innr_ctx* c = b->ctx;
-    const size_t D = b->D, nchunks = b->ldN / kU8Chunk, ldc = nchunks + 1, ldb = b->ldN / 32;
-    bool collect = false;
-    INNR_TRY(range_u8_wants_collect(b, Q, engine, &collect));
-    uint32_t nfallback = 0, kept = 0;
-    float gemm_ms = 0.0f;
-    const size_t per_query = (ldc + 2) * sizeof(uint32_t) + 2 * sizeof(float) +
-                             (collect ? ldb * sizeof(uint32_t) + (size_t)kCollectCap * (sizeof(uint32_t) + sizeof(uint64_t)) : 0);
-    const size_t round = std::min(Q, std::max<size_t>(1, std::min(kRangeMaxRound, kRangeWorkspace / per_query)));
-    INNR_TRY(c->rs_cnt.ensure(round * ldc * sizeof(uint32_t)));
-    INNR_TRY(c->rs_tot.ensure(2 * round * sizeof(uint32_t)));
-    INNR_TRY(c->q_norm.ensure(2 * round * sizeof(float)));
-    if (collect) INNR_TRY(c->rs_bits.ensure(round * ldb * sizeof(uint32_t)));
-    uint32_t* cnt = c->rs_cnt.as<uint32_t>();
-    uint32_t* tot = c->rs_tot.as<uint32_t>();
-    uint32_t* bad = tot + round;
-    float* qsum = c->q_norm.as<float>();
-    float* qnorm = qsum + round;
-    INNR_HIP_CHECK(hipMemsetAsync(c->flags.p, 0, 4096, c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[0], c->stream));
-    INNR_HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), c->stream));  // the running base, carried in the offsets themselves
-    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-    for (size_t q0 = 0; q0 < Q; q0 += round) {
-        const uint32_t nq = (uint32_t)std::min(round, Q - q0);
-        const float* Qp = dQ + q0 * D;
-        const float* thr = dThr + q0;
-        uint64_t* off = d_off + q0;
-        query_sums_kernel<<<(nq + 63) / 64, 64, 0, c->stream>>>(Qp, nq, (uint32_t)D, D, qsum, qnorm);
-        INNR_HIP_CHECK(hipGetLastError());
-        // the queries the exact scan serves: all of them, or after a collect pass the bad ones (gathered, with a map to their rows)
-        const float *sQ = Qp, *sSum = qsum, *sThr = thr;
-        const uint32_t* smap = nullptr;
-        uint32_t snq = nq;
-        const dim3 lg(kCollectCap / 256, nq);  // (blocks beyond a query's list length return at once)
-        if (collect) {
-            I8Plan p = plan_i8(b, kCopyI8Dot, nq, 1, 32u, /*one_limb=*/true);
-            (void)plan_i8_small(b, &p, nq, false, /*collect=*/true);
-            INNR_TRY(prep_queries_i8(b, p, Qp, nq, qsum, b->alpha, b->offset));
-            const float* qc = c->misc.as<float>();
-            // fixed thresholds: thr - E (one key lower); 0 = "no bound" where that is not finite -> closed, the exact scan's
-            INNR_TRY(c->seed_score.ensure(p.Qpad * sizeof(uint32_t)));
-            uint32_t* seed = c->seed_score.as<uint32_t>();
-            seed_thresholds_u8_kernel<<<(unsigned)((p.Qpad + 255) / 256), 256, 0, c->stream>>>(thr, nq, 1u, u8_filter_scale(b), qnorm, qsum, b->offset,
-                                                                                           qc + 3 * p.Qpad, seed, (uint32_t)p.Qpad, 0u);
-            range_close_unbounded_kernel<<<(nq + 255) / 256, 256, 0, c->stream>>>(seed, nq);
-            INNR_HIP_CHECK(hipGetLastError());
-            // global lists: [Qpad][kCollectCap] indices, [Qpad] lengths
-            INNR_TRY(c->lists.ensure(p.Qpad * (size_t)kCollectCap * sizeof(uint32_t)));
-            INNR_TRY(c->counts.ensure(p.Qpad * sizeof(uint32_t)));
-            INNR_TRY(c->sort_keys.ensure(nq * (size_t)kCollectCap * sizeof(uint64_t)));
-            INNR_HIP_CHECK(hipMemsetAsync(c->counts.p, 0, p.Qpad * sizeof(uint32_t), c->stream));
-            I8Plan pl = p;
-            pl.KP = kCollectCap;  // what the kernel takes as the list capacity
-            INNR_HIP_CHECK(hipEventRecord(c->ev[2], c->stream));
-            INNR_TRY(launch_gemm_i8<2>(b, pl, nq, qc, nullptr, 0, seed));
-            INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-            collect_scores_u8_kernel<<<lg, 256, 0, c->stream>>>(reinterpret_cast<const uint4*>(p.corpus), p.nk, (uint32_t)D, Qp, qsum,
-                                                                b->alpha / 255.0f, b->offset, c->lists.as<uint32_t>(), c->counts.as<uint32_t>(),
-                                                                kCollectCap, c->sort_keys.as<uint64_t>());
-            INNR_HIP_CHECK(hipMemsetAsync(c->rs_bits.p, 0, nq * ldb * sizeof(uint32_t), c->stream));
-            INNR_HIP_CHECK(hipMemsetAsync(cnt, 0, nq * ldc * sizeof(uint32_t), c->stream));
-            range_mark_kernel<false, (int)kU8Chunk, false><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, thr,
-                                                                                      seed, nullptr, c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad);
-            INNR_HIP_CHECK(hipGetLastError());
-            // which queries the exact scan finishes, and how long the lists got (one synchronisation per round)
-            std::vector<uint32_t> hb(2 * (size_t)nq);
-            INNR_HIP_CHECK(hipMemcpyAsync(hb.data(), bad, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            INNR_HIP_CHECK(hipMemcpyAsync(hb.data() + nq, c->counts.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            INNR_HIP_CHECK(hipStreamSynchronize(c->stream));
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms += ms;
-            std::vector<uint32_t> redo;
-            for (uint32_t j = 0; j < nq; ++j) {
-                if (hb[j]) redo.push_back(j);
-                kept = std::max(kept, std::min(hb[nq + j], kCollectCap));
-            }
-            nfallback += (uint32_t)redo.size();
-            snq = (uint32_t)redo.size();
-            if (snq) {  // gathered: their rows (rb.q), thresholds (rb.qn) and sums (rb.sc); rb.map = the rows of cnt / off
-                innr_ctx::RedoBufs& rb = c->cmpl;
-                INNR_TRY(upload_redo(c, rb, redo, D, 1));
-                smap = rb.map.as<uint32_t>();
-                gather_rows_kernel<<<(unsigned)(((size_t)snq * D + 255) / 256), 256, 0, c->stream>>>(Qp, smap, snq, (uint32_t)D, rb.q.as<float>());
-                gather_f32_kernel<<<(snq + 255) / 256, 256, 0, c->stream>>>(thr, smap, snq, rb.qn.as<float>());
-                gather_f32_kernel<<<(snq + 255) / 256, 256, 0, c->stream>>>(qsum, smap, snq, rb.sc.as<float>());
-                INNR_HIP_CHECK(hipGetLastError());
-                sQ = rb.q.as<float>();
-                sThr = rb.qn.as<float>();
-                sSum = rb.sc.as<float>();
-            }
-        }
-        if (snq) INNR_TRY(launch_range_scan_u8<false>(b, sQ, sSum, sThr, smap, snq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
-        range_chunk_scan_kernel<<<nq, 1024, 0, c->stream>>>(cnt, ldc, (uint32_t)nchunks, tot);
-        range_offsets_kernel<<<1, 1024, 0, c->stream>>>(tot, nq, off);
-        INNR_HIP_CHECK(hipGetLastError());
-        if (cap == 0) continue;  // a count-only call
-        if (snq) INNR_TRY(launch_range_scan_u8<true>(b, sQ, sSum, sThr, smap, snq, cnt, ldc, off, d_idx, d_sc, (uint64_t)cap));
-        if (collect) {
-            range_scatter_kernel<(int)kU8Chunk><<<lg, 256, 0, c->stream>>>(c->sort_keys.as<uint64_t>(), c->counts.as<uint32_t>(), kCollectCap, false,
-                                                                           c->rs_bits.as<uint32_t>(), ldb, cnt, ldc, bad, off, b->index_base, d_idx,
-                                                                           d_sc, (uint64_t)cap);
-            INNR_HIP_CHECK(hipGetLastError());
-        }
-    }
-    if (!collect) INNR_HIP_CHECK(hipEventRecord(c->ev[3], c->stream));
-    INNR_HIP_CHECK(hipEventRecord(c->ev[1], c->stream));
-    uint64_t total = 0;
-    INNR_HIP_CHECK(copy_out(c, &total, d_off + Q, sizeof(total)));
-    INNR_TRY(check_errflag(c));  // (synchronises)
-    *out_total = (size_t)total;
-    if (stats) {
-        float ms = 0.0f;
-        if (!collect && hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) gemm_ms = ms;
-        stats->engine = collect ? INNR_KNN_MFMA_I8 : INNR_KNN_EXACT;
-        stats->queries_fallback = nfallback;
-        stats->candidates_kept = kept;
-        stats->gemm_ms = gemm_ms;
-        if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) stats->total_ms = ms;
-    }
-    return INNR_OK;
+    RangeU8 p = {b, nullptr, nullptr};
+    return range_search_rounds(p, b, dQ, Q, dThr, engine, d_off, d_idx, d_sc, cap, out_total, stats);
 }
 
 // the argument checks both u8 entry points share: range_search_args' order with the batch test inverted
@@ -4878,10 +4834,15 @@ static innr_status range_search_u8_args(innr_batch* b, const float* queries, siz
 // A range search on host memory: queries, thresholds and offsets staged on the device, and room for min(cap, Q * N) results. Where
 // that room is large (beyond kRangeStageDirect bytes) a count-only pass comes first and the room shrinks to what the result needs: a
 // generous cap costs a second search, not memory for results that do not exist. dev(dQ, dThr, d_off, d_idx, d_sc, room) searches.
+// empty (the argument checks found nothing to search): the offsets are all zero.
 template <class Dev>
-static innr_status range_search_from_host(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds,
+static innr_status range_search_from_host(innr_batch* b, bool empty, const float* queries, size_t Q, size_t D, const float* thresholds,
                                           uint64_t* out_offsets, uint64_t* out_idx, float* out_score, size_t cap, size_t* out_total,
                                           Dev&& dev) {
+    if (empty) {
+        memset(out_offsets, 0, (Q + 1) * sizeof(uint64_t));
+        return INNR_OK;
+    }
     innr_ctx* c = b->ctx;
     INNR_ENTER(c);
     size_t room = std::min(cap, Q * b->N);
@@ -4907,6 +4868,19 @@ static innr_status range_search_from_host(innr_batch* b, const float* queries, s
     return INNR_OK;
 }
 
+// ... and on device memory: all-zero offsets where the argument checks found nothing to search, else dev() searches
+template <class Dev>
+static innr_status range_search_on_device(innr_batch* b, bool empty, size_t Q, uint64_t* d_out_offsets, Dev&& dev) {
+    innr_ctx* c = b->ctx;
+    INNR_ENTER(c);
+    if (empty) {
+        INNR_HIP_CHECK(hipMemsetAsync(d_out_offsets, 0, (Q + 1) * sizeof(uint64_t), c->stream));
+        INNR_HIP_CHECK(ctx_sync(c));
+        return INNR_OK;
+    }
+    return dev();
+}
+
 }  // namespace innr
 
 extern "C" {
@@ -4916,14 +4890,9 @@ innr_status innr_batch_range_search_dev(innr_batch* b, int metric, const float* 
                                         size_t* out_total, innr_knn_stats* stats) {
     bool empty = false;
     INNR_TRY(range_search_args(b, metric, d_queries, Q, D, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats, &empty));
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    if (empty) {
-        INNR_HIP_CHECK(hipMemsetAsync(d_out_offsets, 0, (Q + 1) * sizeof(uint64_t), c->stream));
-        INNR_HIP_CHECK(ctx_sync(c));
-        return INNR_OK;
-    }
-    return range_search_dev(b, metric, d_queries, Q, d_thresholds, engine, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+    return range_search_on_device(b, empty, Q, d_out_offsets, [&] {
+        return range_search_dev(b, metric, d_queries, Q, d_thresholds, engine, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+    });
 }
 
 innr_status innr_batch_range_search(innr_batch* b, int metric, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
@@ -4931,11 +4900,7 @@ innr_status innr_batch_range_search(innr_batch* b, int metric, const float* quer
                                     innr_knn_stats* stats) {
     bool empty = false;
     INNR_TRY(range_search_args(b, metric, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total, stats, &empty));
-    if (empty) {
-        memset(out_offsets, 0, (Q + 1) * sizeof(uint64_t));
-        return INNR_OK;
-    }
-    return range_search_from_host(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
+    return range_search_from_host(b, empty, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
                                   [&](const float* dQ, const float* dThr, uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t room) {
                                       return range_search_dev(b, metric, dQ, Q, dThr, engine, d_off, d_idx, d_sc, room, out_total, stats);
                                   });
@@ -4946,14 +4911,9 @@ innr_status innr_batch_range_search_u8_dev(innr_batch* b, const float* d_queries
                                            innr_knn_stats* stats) {
     bool empty = false;
     INNR_TRY(range_search_u8_args(b, d_queries, Q, D, d_thresholds, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats, &empty));
-    innr_ctx* c = b->ctx;
-    INNR_ENTER(c);
-    if (empty) {
-        INNR_HIP_CHECK(hipMemsetAsync(d_out_offsets, 0, (Q + 1) * sizeof(uint64_t), c->stream));
-        INNR_HIP_CHECK(ctx_sync(c));
-        return INNR_OK;
-    }
-    return range_search_u8_dev(b, d_queries, Q, d_thresholds, engine, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+    return range_search_on_device(b, empty, Q, d_out_offsets, [&] {
+        return range_search_u8_dev(b, d_queries, Q, d_thresholds, engine, d_out_offsets, d_out_idx, d_out_score, cap, out_total, stats);
+    });
 }
 
 innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size_t Q, size_t D, const float* thresholds, int engine,
@@ -4961,11 +4921,7 @@ innr_status innr_batch_range_search_u8(innr_batch* b, const float* queries, size
                                        innr_knn_stats* stats) {
     bool empty = false;
     INNR_TRY(range_search_u8_args(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total, stats, &empty));
-    if (empty) {
-        memset(out_offsets, 0, (Q + 1) * sizeof(uint64_t));
-        return INNR_OK;
-    }
-    return range_search_from_host(b, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
+    return range_search_from_host(b, empty, queries, Q, D, thresholds, out_offsets, out_idx, out_score, cap, out_total,
                                   [&](const float* dQ, const float* dThr, uint64_t* d_off, uint64_t* d_idx, float* d_sc, size_t room) {
                                       return range_search_u8_dev(b, dQ, Q, dThr, engine, d_off, d_idx, d_sc, room, out_total, stats);
                                   });

@@ -78,7 +78,7 @@ def _thresholds(scores):
         elif kind == 5:
             thr[j] = np.sort(s)[-1]           # above all scores but the best
         elif kind == 6:
-            last0 = (n - 1) // 1024 * 1024
+            last0 = (n - 1) // 1024 * 1024 or n - 256                   # (a corpus of one chunk: its last 256 vectors)
             thr[j] = np.nextafter(s[:last0].max(), np.float32(np.inf))  # nothing below the last chunk survives
         else:
             mid = s[1024:2048].max() if n > 2048 else s[n // 3:2 * n // 3].max()
@@ -307,7 +307,39 @@ def test_launch_records(S, small):
         qc.close()
 
 
-# ------------------------------------------------------------------------------------------------ 6. the checks, in their order
+# ------------------------------------------------------------------------------------------------ 6. several rounds
+@pytest.fixture(scope="module")
+def many():
+    """4100 queries on 1000 codes of 8 dimensions, built once and read-only: the case and its CPU expectation"""
+    case = _case(1000, 8, 4100, 601)
+    exp = _expected(case[3], case[4])
+    for a in (case[0], case[2], case[3], case[4]) + exp:
+        a.setflags(write=False)
+    return case, exp
+
+
+@pytest.mark.parametrize("engine", (EXACT, I8))
+def test_more_queries_than_one_round(S, many, ctx_option, engine):
+    """more than 4096 queries: the batch is worked off in rounds -- the running 64-bit base carried in the offsets, each round's
+    queries, thresholds and offsets against round-local counts, sums, norms, seeds, flags and lists (the collect path, which a
+    corpus this small takes only with range_u8_i8_min_n = 0, finishes the queries without a finite collect bound by the exact scan)"""
+    from test_gpu_u8_range_collect import _no_bound
+    (codes, p, qs, scores, thr), exp = many
+    if engine == I8:
+        ctx_option("range_u8_i8_min_n", 0)
+    qc = _corpus(S, codes, p)
+    try:
+        got = _run(qc, qs, thr, engine)
+        _assert_same(got, exp, f"{len(qs)} queries engine={engine}")
+        st = got[3]
+        assert st.engine == engine
+        if engine == I8:
+            assert st.queries_fallback == _no_bound(thr), (st.queries_fallback, _no_bound(thr))
+    finally:
+        qc.close()
+
+
+# ------------------------------------------------------------------------------------------------ 7. the checks, in their order
 def test_checks_in_order(S, small):
     from innr_amd import _lib
     from innr_amd import batch as B
