@@ -112,7 +112,7 @@ innr_status innr_ctx_synchronize(innr_ctx* ctx);
  * free their selection at the end of every call), copy_budget_mib (default -1 = unlimited: the copy budget, in MiB, of every batch created from now on, see
  * innr_batch_set_copy_budget), scan_max_slots (default 0 = fill the chip: the most wave slots an exact scan is cut into, rounded
  * up to a multiple of 4, so that a wave owns several chunks of a small corpus), mutate_round (default 0 = what fits 256 MiB: the
- * most rows a staging round of innr_batch_append_rows / innr_batch_update_rows carries; a test switch), range_u8_i8_min_n (default
+ * most rows a staging round of innr_batch_append_rows / innr_batch_update_rows and their u8 twins carries; a test switch), range_u8_i8_min_n (default
  * 65536: the fewest vectors of a code batch whose innr_batch_range_search_u8 calls the int8 collect pass serves) -- DESIGN.md lists what each one does. None of them changes a result. Unknown name: INNR_E_BAD_ARG. */
 innr_status innr_ctx_set_option(innr_ctx* ctx, const char* name, long value);
 innr_status innr_ctx_get_option(innr_ctx* ctx, const char* name, long* value);
@@ -494,7 +494,8 @@ innr_status innr_batch_knn_rows_dev(innr_batch* b, int metric, const uint64_t* d
  * Order of the checks, all three: a null batch, a u8 code batch or a prefix view: INNR_E_BAD_ARG; D != the batch's:
  * INNR_E_DIM_MISMATCH (an empty batch created with D = 0 takes only D = 0 rows; keep has no D); n == 0 (keep: N == 0):
  * INNR_OK, nothing touched; null rows / idx / mask with work to do: INNR_E_BAD_ARG; the size limit; the index checks.
- * Out of scope: u8 code batches and document corpora; reserved capacity and amortised growth (every append past the padding
+ * Out of scope: u8 code batches (refused here: the next section's innr_batch_append_codes / _update_codes / _keep_codes change
+ * one) and document corpora; reserved capacity and amortised growth (every append past the padding
  * copies the store once); incremental maintenance of norms and filter copies; sharded corpora (a rank's shard may be changed,
  * the index bases of the other shards and anything cached per communicator are the caller's business); changing a batch through
  * a view; atomicity against searches issued concurrently from another thread, beyond the context's lock. */
@@ -524,6 +525,68 @@ innr_status innr_batch_update_rows_dev(innr_batch* b, const uint64_t* d_idx, con
 innr_status innr_batch_keep_rows(innr_batch* b, const uint8_t* mask, size_t* out_n);
 /* same, d_mask resident on the device; the call synchronises with the host (the count, the allocation) */
 innr_status innr_batch_keep_rows_dev(innr_batch* b, const uint8_t* d_mask, size_t* out_n);
+
+/* ---- changing a resident u8 code batch in place: append, overwrite and remove rows, as codes or as f32 rows quantised on the
+ * device (an addition: the reference's quantised corpus is a list of immutable QuantizedU8) ----
+ * The byte twins of the f32 section above, for the batches of innr_batch_upload_u8 / _generate_u8 / _quantize_u8. The handle, the
+ * index base, the copy budget and alpha / offset stay as they are; innr_batch_num_vectors reports the new N. `codes` is row-major
+ * u8 [n*D], as innr_batch_upload_u8 takes it. The _quantized variants take row-major f32 [n*D] and store, for every value v,
+ * quantize_u8(v) under the BATCH's alpha / offset: clamp(round((v - offset) * (255.0f / alpha))) with 255.0f / alpha computed
+ * once in f32 on the host, no contraction, round half away from zero, NaN -> 0 -- the arithmetic of innr_quantize_u8,
+ * innr_batch_quantize_u8 and innr_batch_generate_u8, and like them without a check on alpha. After quantising, a _quantized call
+ * IS the _codes call on those codes.
+ * One contract for the five: after a successful call every entry point that accepts a code batch answers on this batch exactly
+ * as on a fresh code batch uploaded with the final codes -- indices position for position, score bits, every engine. After a
+ * failed call the batch is exactly as before: store, derived state, answers.
+ * Derived state: a successful call that changes the batch drops EVERYTHING the batch derived from its store, through the one
+ * list the f32 calls use -- for a code batch the int8 copy (INNR_COPY_I8_DOT, with its `weak` mark and a remembered refusal), the
+ * kept selection and the engines' call history. Each is rebuilt by the next call that wants it.
+ * Views: a batch must have no live prefix view when it is changed; a view handle itself is refused (see the f32 section).
+ * Order of the checks, all five: a null batch, an f32 batch or a prefix view: INNR_E_BAD_ARG (the message says which: "null",
+ * "f32", "view"); D != the batch's: INNR_E_DIM_MISMATCH (keep has no D); n == 0 (keep: N == 0): INNR_OK, nothing touched, nothing
+ * dropped; null codes / rows / idx / mask with work to do: INNR_E_BAD_ARG; the size limit -- N + n must stay below 2^32 - 1 - 1024,
+ * the bound of every code batch: INNR_E_UNSUPPORTED, before anything is read or allocated; the index checks.
+ * Memory: a code store has round_up(N, 1024) columns x round_up(D, 32) rows of bytes. The host entry points stage in the
+ * context's workspace in rounds of at most 256 MiB (indices, codes and, for the _quantized variants, the f32 rows and their codes
+ * together; the option mutate_round bounds the rows of a round); a _quantized_dev call quantises into that workspace, n*D bytes in
+ * rounds of at most 256 MiB. An append past the padding and a keep need the old and the new store at once.
+ * Out of scope: reserved capacity and amortised growth (every append past the padding copies the store once); incremental
+ * maintenance of the int8 copy; re-fitting alpha / offset when appended values fall outside the range (they clamp, as quantize_u8
+ * does); document corpora; sharded corpora; changing a batch through a view; atomicity against searches issued concurrently from
+ * another thread, beyond the context's lock. */
+/* Append: the new rows get local indices N .. N+n-1, the old rows keep theirs. N + n <= the store's padded width (N rounded up
+ * to 1024): the rows are transposed into the zero padding in place, byte by byte (column N need be no multiple of 4), nothing is
+ * allocated; a failure after a partial write zeroes the touched padding again. Otherwise a new store of round_up(N + n, 1024)
+ * columns is allocated and zeroed, the old D x N block copied across on the device (a pitched copy), the rows transposed in, and
+ * the old store freed after the stream is synchronised; a failed hipMalloc is INNR_E_OOM and leaves the batch untouched. */
+innr_status innr_batch_append_codes(innr_batch* b, const uint8_t* codes, size_t n, size_t D);
+/* same, d_codes resident on the device; the call synchronises with the host (the allocation) */
+innr_status innr_batch_append_codes_dev(innr_batch* b, const uint8_t* d_codes, size_t n, size_t D);
+/* Update: row idx[j] becomes codes[j*D ..]. Indices are GLOBAL (index base + local index), in any order. Nothing is reallocated.
+ * Two passes, as innr_batch_update_rows: every index is checked on the device before anything is written -- against
+ * [base, base + N) and, through an N-bit bitmap in the context's workspace that spans all staging rounds, against the other
+ * indices of the call. An index outside the range, or one that occurs twice in one call, is INNR_E_BAD_ARG with a message naming
+ * it (duplicates are refused, not "last wins"). The writes are single-byte stores: four neighbouring vectors share a dword of a
+ * dimension row, and the three a call does not name are never read or rewritten. */
+innr_status innr_batch_update_codes(innr_batch* b, const uint64_t* idx, const uint8_t* codes, size_t n, size_t D);
+/* same, d_idx and d_codes resident on the device; the call synchronises with the host (the check's flag) */
+innr_status innr_batch_update_codes_dev(innr_batch* b, const uint64_t* d_idx, const uint8_t* d_codes, size_t n, size_t D);
+/* Keep (remove): the rows with mask[i] != 0 survive, in index order; row i's new local index is the number of kept rows below
+ * it. mask: N bytes. *out_n (may be null) receives the new N. The kept rows are compacted into a new store of round_up(N', 1024)
+ * columns by the selection's count and gather kernels (a failed hipMalloc is INNR_E_OOM); the memory of the removed rows is
+ * given back. A mask that keeps every row changes nothing and drops nothing; a mask that keeps none leaves an N = 0 batch of the
+ * same D, which append fills again. The host entry point stages the mask in the context's workspace. */
+innr_status innr_batch_keep_codes(innr_batch* b, const uint8_t* mask, size_t* out_n);
+/* same, d_mask resident on the device; the call synchronises with the host (the count, the allocation) */
+innr_status innr_batch_keep_codes_dev(innr_batch* b, const uint8_t* d_mask, size_t* out_n);
+/* innr_batch_append_codes of quantize_u8(rows) under the batch's alpha / offset, quantised on the device */
+innr_status innr_batch_append_quantized(innr_batch* b, const float* rows, size_t n, size_t D);
+/* same, d_rows resident on the device (fresh embeddings never visit the host) */
+innr_status innr_batch_append_quantized_dev(innr_batch* b, const float* d_rows, size_t n, size_t D);
+/* innr_batch_update_codes of quantize_u8(rows) under the batch's alpha / offset, quantised on the device */
+innr_status innr_batch_update_quantized(innr_batch* b, const uint64_t* idx, const float* rows, size_t n, size_t D);
+/* same, d_idx and d_rows resident on the device */
+innr_status innr_batch_update_quantized_dev(innr_batch* b, const uint64_t* d_idx, const float* d_rows, size_t n, size_t D);
 
 /* ---- pairwise surface kept on the host: called per PAIR by graph indexes, so a kernel
  * launch cannot pay for itself. Plain host functions in the reference's portable arithmetic order. ------------ */

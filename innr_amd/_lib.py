@@ -155,6 +155,16 @@ SIGNATURES = {
     "innr_batch_update_rows_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
     "innr_batch_keep_rows": (C.c_int, [_vp, _vp, _szp]),
     "innr_batch_keep_rows_dev": (C.c_int, [_vp, _vp, _szp]),
+    "innr_batch_append_codes": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "innr_batch_append_codes_dev": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "innr_batch_update_codes": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
+    "innr_batch_update_codes_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
+    "innr_batch_keep_codes": (C.c_int, [_vp, _vp, _szp]),
+    "innr_batch_keep_codes_dev": (C.c_int, [_vp, _vp, _szp]),
+    "innr_batch_append_quantized": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "innr_batch_append_quantized_dev": (C.c_int, [_vp, _vp, _sz, _sz]),
+    "innr_batch_update_quantized": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
+    "innr_batch_update_quantized_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz]),
     "innr_merge_topk_dev":(C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "innr_dot_f32": (C.c_float, [_vp, _vp, _sz]),
     "innr_cosine_f32": (C.c_float, [_vp, _vp, _sz]),

@@ -2802,9 +2802,9 @@ innr_status innr_batch_knn(innr_batch* b, int metric, const float* queries, size
 }  // extern "C"  (the u8 section has templates and static helpers; its entry points get C linkage from the header)
 
 // ---- scalar-quantised corpus (scalar.rs) -----------------------------------------------------------------
-static innr_status alloc_batch_u8(innr_ctx* ctx, size_t N, size_t D, float alpha, float offset, innr_batch** out) {
+innr_status innr::alloc_batch_u8(innr_ctx* ctx, size_t N, size_t D, float alpha, float offset, innr_batch** out) {
     if (!ctx || !out) return INNR_E_BAD_ARG;
-    if (N >= 0xFFFFFFFFull - 1024 || D > 65535) {
+    if (N >= kMaxBatchNU8 || D > 65535) {
         set_error("u8 corpus shard too large (N=%zu, D=%zu)", N, D);
         return INNR_E_UNSUPPORTED;
     }
@@ -3944,14 +3944,7 @@ static innr_status build_selection(innr_batch* b, size_t npass, bool* built) {
     b->fsel_mask_bytes = mask_bytes;
     b->fsel_map_bytes = map_bytes;
     if (b->C8) {
-        const size_t nchunks = b->ldN / kSelChunk;
-        const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
-        const size_t D = b->D;
-        const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
-        const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
-        select_gather_u8_kernel<<<grid, 256, 0, c->stream>>>(b->C8, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, s->C8,
-                                                             s->ldN, b->fsel_map, slab);
-        INNR_HIP_CHECK(hipGetLastError());
+        INNR_TRY(gather_passing_u8(b, s->C8, s->ldN, b->fsel_map));
     } else {
         INNR_TRY(gather_passing(b, s->V, s->ldN, b->fsel_map));
     }
@@ -4418,6 +4411,29 @@ innr_status gather_passing(innr_batch* b, float* S, size_t ldS, uint32_t* map) {
     select_gather_kernel<<<grid, 256, 0, c->stream>>>(b->V, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, S, ldS, map, slab);
     INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
+}
+
+// ... and for a code batch (mutate_u8.hip): the same chunks, counts and offsets, select_gather_u8_kernel
+innr_status gather_passing_u8(innr_batch* b, uint8_t* S, size_t ldS, uint32_t* map) {
+    innr_ctx* c = b->ctx;
+    const size_t nchunks = b->ldN / kSelChunk;
+    const uint32_t* off = c->flt_scan.as<uint32_t>() + nchunks;
+    const size_t D = b->D;
+    const uint32_t slab = (uint32_t)std::max<size_t>(kSelSlab, (D + 65534) / 65535);
+    const dim3 grid((unsigned)((nchunks + 3) / 4), (unsigned)std::max<size_t>(1, (D + slab - 1) / slab));
+    select_gather_u8_kernel<<<grid, 256, 0, c->stream>>>(b->C8, b->ldN, (uint32_t)D, c->flt_mask.as<uint8_t>(), off, nchunks, S, ldS, map,
+                                                         slab);
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
+
+// codes[n][D] (device, row-major) into columns col0 .. col0 + n of a code store (transpose_rows_u8_kernel, the upload's launch):
+// only d < D, i < n is written, byte by byte
+hipError_t transpose_codes_into(innr_ctx* c, const uint8_t* d_codes, size_t n, size_t D, uint8_t* C8, size_t ldN, size_t col0) {
+    if (n == 0 || D == 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 31) / 32), (unsigned)((D + 31) / 32));
+    transpose_rows_u8_kernel<<<grid, 256, 0, c->stream>>>(d_codes, (uint32_t)n, (uint32_t)D, C8, ldN, col0);
+    return hipGetLastError();
 }
 
 void invalidate_derived(innr_batch* b) {

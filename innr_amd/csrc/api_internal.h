@@ -1,7 +1,7 @@
 // api_internal.h -- what more than one translation unit of the library shares: the context and its workspace, the launch record
 // and dispatch, the corpus handles, the entry guard, and the host functions that cross a unit boundary. The units: api.hip (the C
-// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), rows.hip (search by stored vector), mutate.hip (changing a batch in place),
-// comm.hip (the multi-GPU layer), sort_full.hip.
+// ABI, the kNN engines, range search, memory), maxsim.hip, adaptive.hip (batch_knn_adaptive), rows.hip (search by stored vector), mutate.hip and
+// mutate_u8.hip (changing an f32 / a u8 code batch in place), comm.hip (the multi-GPU layer), sort_full.hip.
 // Nothing here may depend on INNR_TEST_HOOKS: every object but api.o is linked into the product library and the hook library
 // alike, so the struct layouts must be the same in every object.
 #pragma once
@@ -76,7 +76,7 @@ struct innr_tuning {
     long split_screen_worst_case = 0;  // ... the screen's margin by the worst-case formula alone (every lo limb at half a last place), never from the limbs' measured norms (A/B, tests)
     long filter_keep_selection = 1;  // innr_batch_knn_filtered_multi, innr_batch_knn_u8_filtered: keep the selection of the last mask for the next call (0: free it at the end of each call)
     long copy_budget_mib = -1;   // the copy budget (MiB) a batch gets when it is created; < 0 = unlimited (innr_batch_set_copy_budget)
-    long mutate_round = 0;       // innr_batch_append_rows, innr_batch_update_rows: at most this many rows per staging round (tests); 0 = what fits 256 MiB
+    long mutate_round = 0;       // innr_batch_append_rows, innr_batch_update_rows and their u8 twins (mutate_u8.hip): at most this many rows per staging round (tests); 0 = what fits 256 MiB
     long range_u8_i8_min_n = 65536;  // innr_batch_range_search_u8: fewest vectors of a code batch whose calls the collect pass on the int8 matrix pipe serves, for every engine value (below it a tile launch plus re-score costs more than the scans; tests of small shapes set 0)
     long scan_max_slots = 0;     // exact scans (f32, u8, maxsim's document filter): at most this many wave slots, so that a wave owns several chunks on a small corpus (tests); 0 = fill the chip
 };
@@ -383,6 +383,21 @@ hipError_t transpose_rows_into(innr_ctx* c, const float* d_rows, size_t n, size_
 // synchronise) and its gather (select_gather_kernel) of the passing columns of b into S, in index order; map[npass] is written
 innr_status count_mask(innr_batch* b, const uint8_t* d_mask, size_t* npass);
 innr_status gather_passing(innr_batch* b, float* S, size_t ldS, uint32_t* map);
+// ... and for the entry points that change a code batch in place (mutate_u8.hip) their byte twins: a new code
+// batch of N vectors with a zeroed store of round_up(N, 1024) columns x round_up(D, 32) rows of bytes (N from kMaxBatchNU8 on:
+// INNR_E_UNSUPPORTED; a failed hipMalloc: INNR_E_OOM), the upload's transpose at a column offset (byte stores: col0 need be no
+// multiple of 4), and the selection's gather of a code batch (select_gather_u8_kernel, after count_mask)
+constexpr size_t kMaxBatchNU8 = 0xFFFFFFFFull - 1024;
+innr_status alloc_batch_u8(innr_ctx* ctx, size_t N, size_t D, float alpha, float offset, innr_batch** out);
+hipError_t transpose_codes_into(innr_ctx* c, const uint8_t* d_codes, size_t n, size_t D, uint8_t* C8, size_t ldN, size_t col0);
+innr_status gather_passing_u8(innr_batch* b, uint8_t* S, size_t ldS, uint32_t* map);
+// mutate.hip: update_check_kernel over n device indices of one staging round (the caller zeroed c->rows_bits and the head of
+// c->rows_flag once per call), and that head as the kernel writes it
+struct UpdateFlag {
+    uint32_t outside, twice;
+    uint64_t outside_idx, twice_idx;
+};
+innr_status launch_update_check(innr_batch* b, const uint64_t* d_idx, size_t n);
 // THE list of what a batch derives from its store, forgotten: every copy[] kind (as innr_batch_release_copies frees them, a
 // remembered refusal included), the kept selection, the norms and their by-products, the dimension variances, the int8 ranges
 // and the engines' call history. The caller has synchronised the stream. Each is rebuilt by the next call that wants it.

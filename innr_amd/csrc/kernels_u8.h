@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "kernels_prep.h"
+#include "quantize_dev.h"
 #include "topk_dev.h"
 
 namespace innr {
@@ -26,12 +27,7 @@ constexpr int kU8Unroll = INNR_U8_UNROLL;
 #endif
 constexpr int kU8Chunk = 64 * 16;  // vectors per wave step (64 lanes x 16 codes)
 
-// quantize_u8 (scalar.rs:212-225): clamp(round((v - offset) * (255/alpha)), 0, 255); round = half away from zero
-__device__ __forceinline__ uint8_t quantize_one(float v, float offset, float inv_alpha) {
-    const float r = __builtin_roundf(ex::mul(ex::sub(v, offset), inv_alpha));
-    if (r != r) return 0;  // NaN `as u8` == 0
-    return (uint8_t)(r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r));
-}
+// (quantize_one, the arithmetic of quantize_u8: quantize_dev.h)
 
 // codes[(i0+i)*D + d] (row-major packed, what a &[QuantizedU8] holds) -> C[d*ldN + i0 + i]
 __global__ __launch_bounds__(256) void transpose_rows_u8_kernel(const uint8_t* __restrict__ rows, uint32_t nrows,

@@ -3,6 +3,7 @@
 // api.hip owns (transpose_rows_kernel, the selection's count and gather) are reached through its launchers (api_internal.h).
 // Each call either leaves the batch exactly as it was or ends in invalidate_derived (api.hip), the one list of what a batch
 // derives from its store: the store is the only thing these functions write themselves.
+// u8 code batches are refused here and changed by mutate_u8.hip, which shares this unit's index validation (launch_update_check).
 // Workspace: the context's rows_io (staged rows and indices), rows_flag, rows_bits, rows_map; keep: flt_in / flt_mask / flt_scan.
 #include "api_internal.h"
 #include "kernels_mutate.h"
@@ -123,20 +124,6 @@ innr_status append_rows(innr_batch* b, const float* rows, size_t n, size_t D, bo
     }
     take_store(b, nb);
     invalidate_derived(b);
-    return INNR_OK;
-}
-
-struct UpdateFlag {  // the head of rows_flag as update_check_kernel writes it
-    uint32_t outside, twice;
-    uint64_t outside_idx, twice_idx;
-};
-
-innr_status launch_update_check(innr_batch* b, const uint64_t* d_idx, size_t n) {
-    innr_ctx* c = b->ctx;
-    const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->num_cus * 8);
-    update_check_kernel<<<nb, 256, 0, c->stream>>>(d_idx, n, b->index_base, (uint32_t)b->N, c->rows_bits.as<uint32_t>(),
-                                                   c->rows_flag.as<uint32_t>());
-    INNR_HIP_CHECK(hipGetLastError());
     return INNR_OK;
 }
 
@@ -266,6 +253,16 @@ innr_status keep_rows(innr_batch* b, const uint8_t* mask, size_t* out_n, bool ho
 }
 
 }  // namespace
+
+// (declared in api_internal.h: the code batches' update shares the validation kernel, mutate_u8.hip)
+innr_status innr::launch_update_check(innr_batch* b, const uint64_t* d_idx, size_t n) {
+    innr_ctx* c = b->ctx;
+    const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)c->num_cus * 8);
+    update_check_kernel<<<nb, 256, 0, c->stream>>>(d_idx, n, b->index_base, (uint32_t)b->N, c->rows_bits.as<uint32_t>(),
+                                                   c->rows_flag.as<uint32_t>());
+    INNR_HIP_CHECK(hipGetLastError());
+    return INNR_OK;
+}
 
 innr_status innr_batch_append_rows(innr_batch* b, const float* rows, size_t n, size_t D) { return append_rows(b, rows, n, D, true); }
 innr_status innr_batch_append_rows_dev(innr_batch* b, const float* d_rows, size_t n, size_t D) {

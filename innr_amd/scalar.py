@@ -5,7 +5,8 @@ asymmetric_dot_u8[_precomputed] (:261-300), mixed_dot_u8_f32 (:314-358) and batc
 Fitting and quantising are one-time ingest steps and stay on the host; the pairwise dots are
 host functions of libinnr_hip.so in the portable order; the corpus scan `batch_knn_u8` runs on the GPU.
 Addition: `QuantizedCorpus` keeps the packed codes resident on the device across calls (the reference re-walks
-N separate Vec<u8> allocations per call).
+N separate Vec<u8> allocations per call), and changes them in place: append_codes / append, update_codes / update_rows,
+keep, remove -- from codes, or from f32 rows quantised on the device with the corpus' own params.
 """
 from __future__ import annotations
 
@@ -145,6 +146,7 @@ class QuantizedCorpus(_lib.BatchMemoryMixin):
 
     def __init__(self, handle, n: int, dim: int, params: QuantizationParams, ctx: _lib.Context):
         self._h, self._n, self._d, self.params, self._ctx = handle, int(n), int(dim), params, ctx
+        self._base = 0  # the index base, remembered for remove()
         ctx._children.add(self)
 
     @classmethod
@@ -188,7 +190,9 @@ class QuantizedCorpus(_lib.BatchMemoryMixin):
         host round trip); inherits the batch's index base."""
         h = C.c_void_p()
         check(load().innr_batch_quantize_u8(batch._h, C.c_float(params.alpha), C.c_float(params.offset), C.byref(h)))
-        return cls(h, batch.num_vectors(), batch.dimension(), params, batch._ctx)
+        qc = cls(h, batch.num_vectors(), batch.dimension(), params, batch._ctx)
+        qc._base = int(getattr(batch, "_base", 0))
+        return qc
 
     def __len__(self) -> int: return self._n
     def dimension(self) -> int: return self._d
@@ -196,6 +200,108 @@ class QuantizedCorpus(_lib.BatchMemoryMixin):
     def set_index_base(self, base: int) -> None:
         """Global index of this shard's first document (multi-GPU range partition)."""
         check(load().innr_batch_set_index_base(self._h, C.c_uint64(int(base))))
+        self._base = int(base)
+
+    # ---- changing the corpus in place (innr_batch_append_codes / _update_codes / _keep_codes and the _quantized variants;
+    # DESIGN.md 4.5h). After each of them the corpus answers as a fresh corpus of the final codes would; what it had derived from
+    # its store (the int8 copy, the kept selection) is dropped and rebuilt by the next call that wants it.
+    def _before_change(self, what: str) -> None:
+        if getattr(self, "_parent", None) is not None:
+            raise _lib.InnrError(_lib.E_BAD_ARG, f"{what}: a prefix view cannot be changed")
+        if any(getattr(v, "_h", None) for v in list(getattr(self, "_views", ()))):
+            raise _lib.InnrError(_lib.E_BAD_ARG, f"{what}: the corpus has an open prefix view (close it first)")
+
+    def _changed(self) -> None:
+        self._n = int(load().innr_batch_num_vectors(self._h))
+
+    def _rows_arg(self, rows, what: str, np_dtype, torch_dtype: str):
+        """(pointer or None, n, the tensor or array kept alive, on the device?) of row-major rows [n][dimension]"""
+        if self._d == 0:
+            raise InnrPanic(f"{what}: the corpus has dimension 0")
+        if hasattr(rows, "is_cuda") and rows.is_cuda:
+            import torch
+            t = rows.to(getattr(torch, torch_dtype)).contiguous().reshape(-1, self._d)
+            return (C.c_void_p(t.data_ptr()) if t.numel() else None), int(t.shape[0]), t, True
+        a = np.ascontiguousarray(rows, dtype=np_dtype)
+        if a.size % self._d:
+            raise InnrPanic(f"{what}: {a.size} values are no whole number of rows of dimension {self._d}")
+        a = a.reshape(-1, self._d)
+        return (_vp(a) if a.size else None), int(a.shape[0]), a, False
+
+    def _append(self, what: str, rows, np_dtype, torch_dtype: str, host_fn: str) -> None:
+        self._before_change(what)
+        p, n, alive, dev = self._rows_arg(rows, what, np_dtype, torch_dtype)
+        if dev:
+            self._ctx.bind_torch_stream()  # the rows were produced on torch's stream
+        check(getattr(load(), host_fn + "_dev" if dev else host_fn)(self._h, p, n, self._d))
+        self._changed()
+
+    def _update(self, what: str, indices, rows, np_dtype, torch_dtype: str, host_fn: str) -> None:
+        self._before_change(what)
+        p, n, alive, dev = self._rows_arg(rows, what, np_dtype, torch_dtype)
+        if dev:
+            import torch
+            ids = indices if isinstance(indices, torch.Tensor) else torch.from_numpy(np.asarray(indices, dtype=np.int64))
+            ids = ids.to(device=alive.device, dtype=torch.int64).reshape(-1).contiguous()
+            nids, ip = ids.numel(), (C.c_void_p(ids.data_ptr()) if n else None)
+            self._ctx.bind_torch_stream()
+        else:
+            ids = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+            nids, ip = ids.size, (_vp(ids) if n else None)
+        if nids != n:
+            raise InnrPanic(f"{what}: {nids} indices for {n} rows")
+        check(getattr(load(), host_fn + "_dev" if dev else host_fn)(self._h, ip, p, n, self._d))
+        self._changed()
+
+    def append_codes(self, codes) -> None:
+        """The code rows (row-major (n, dimension) uint8: NumPy, or a CUDA tensor, which stays on the device) become documents
+        len() .. len() + n - 1; the others keep their indices. In place while the store's padding (N rounded up to 1024) has
+        room, else the store is copied once into a larger one."""
+        self._append("append_codes", codes, np.uint8, "uint8", "innr_batch_append_codes")
+
+    def append(self, rows) -> None:
+        """append_codes(quantize_u8(rows, self.params)) with the rows (float32, NumPy or a CUDA tensor) quantised on the device:
+        values outside [offset, offset + alpha] clamp, NaN becomes code 0."""
+        self._append("append", rows, np.float32, "float32", "innr_batch_append_quantized")
+
+    def update_codes(self, indices, codes) -> None:
+        """Document indices[j] (GLOBAL index, any order) becomes codes[j]. An index outside the corpus, or one named twice in a
+        call, raises InnrError and nothing is written. NumPy arrays, or CUDA tensors (int64 indices), which stay on the device."""
+        self._update("update_codes", indices, codes, np.uint8, "uint8", "innr_batch_update_codes")
+
+    def update_rows(self, indices, rows) -> None:
+        """update_codes(indices, quantize_u8(rows, self.params)) with the float32 rows quantised on the device."""
+        self._update("update_rows", indices, rows, np.float32, "float32", "innr_batch_update_quantized")
+
+    def keep(self, mask) -> int:
+        """Only the documents with mask[i] != 0 stay (mask: len() bytes or bools, NumPy or a CUDA tensor), in index order:
+        document i's new local index is the number of kept documents below it. Returns the new len(); the memory of the removed
+        documents is given back. A mask that keeps everything changes nothing."""
+        self._before_change("keep")
+        out_n = C.c_size_t(0)
+        if hasattr(mask, "is_cuda") and mask.is_cuda:
+            import torch
+            m = (mask != 0).to(torch.uint8).reshape(-1).contiguous()
+            if m.numel() != self._n:
+                raise InnrPanic(f"keep: a mask of {m.numel()} entries for {self._n} documents")
+            self._ctx.bind_torch_stream()
+            check(load().innr_batch_keep_codes_dev(self._h, C.c_void_p(m.data_ptr()) if self._n else None, C.byref(out_n)))
+        else:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+            if m.size != self._n:
+                raise InnrPanic(f"keep: a mask of {m.size} entries for {self._n} documents")
+            check(load().innr_batch_keep_codes(self._h, _vp(m) if self._n else None, C.byref(out_n)))
+        self._changed()
+        return self._n
+
+    def remove(self, indices) -> int:
+        """keep() with a mask built on the host: the documents named by GLOBAL index (duplicates allowed) go, the others stay."""
+        ids = np.asarray(indices, dtype=np.int64).reshape(-1) - self._base
+        if ids.size and (ids.min() < 0 or ids.max() >= self._n):
+            raise IndexError(f"remove: an index lies outside [{self._base}, {self._base + self._n})")
+        mask = np.ones(self._n, dtype=np.uint8)
+        mask[ids] = 0
+        return self.keep(mask)
 
     def codes(self) -> np.ndarray:
         """Codes back on the host as (n, dim) rows."""
@@ -382,6 +488,7 @@ class QuantizedCorpus(_lib.BatchMemoryMixin):
         check(load().innr_batch_prefix_view(self._h, int(prefix_dims), C.byref(h)))
         v = QuantizedCorpus(h, self._n, min(int(prefix_dims), self._d), self.params, self._ctx)
         v._parent = self
+        v._base = self._base
         if not hasattr(self, "_views"):
             self._views = weakref.WeakSet()
         self._views.add(v)

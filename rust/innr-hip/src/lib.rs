@@ -124,6 +124,16 @@ pub mod ffi {
         pub fn innr_batch_update_rows_dev(b: *mut InnrBatch, d_idx: *const u64, d_rows: *const f32, n: usize, d: usize) -> c_int;
         pub fn innr_batch_keep_rows(b: *mut InnrBatch, mask: *const u8, out_n: *mut usize) -> c_int;
         pub fn innr_batch_keep_rows_dev(b: *mut InnrBatch, d_mask: *const u8, out_n: *mut usize) -> c_int;
+        pub fn innr_batch_append_codes(b: *mut InnrBatch, codes: *const u8, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_append_codes_dev(b: *mut InnrBatch, d_codes: *const u8, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_update_codes(b: *mut InnrBatch, idx: *const u64, codes: *const u8, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_update_codes_dev(b: *mut InnrBatch, d_idx: *const u64, d_codes: *const u8, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_keep_codes(b: *mut InnrBatch, mask: *const u8, out_n: *mut usize) -> c_int;
+        pub fn innr_batch_keep_codes_dev(b: *mut InnrBatch, d_mask: *const u8, out_n: *mut usize) -> c_int;
+        pub fn innr_batch_append_quantized(b: *mut InnrBatch, rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_append_quantized_dev(b: *mut InnrBatch, d_rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_update_quantized(b: *mut InnrBatch, idx: *const u64, rows: *const f32, n: usize, d: usize) -> c_int;
+        pub fn innr_batch_update_quantized_dev(b: *mut InnrBatch, d_idx: *const u64, d_rows: *const f32, n: usize, d: usize) -> c_int;
         pub fn innr_dot_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_cosine_f32(a: *const f32, b: *const f32, n: usize) -> f32;
         pub fn innr_l2sq_f32(a: *const f32, b: *const f32, n: usize) -> f32;
@@ -687,6 +697,47 @@ pub mod scalar {
                                                                std::ptr::null_mut()) });
             }
             (0..q).map(|j| (off[j] as usize..off[j + 1] as usize).map(|i| (idx[i] as usize, sc[i])).collect()).collect()
+        }
+        // ---- changing the corpus in place (innr_batch_append_codes / _update_codes / _keep_codes and the _quantized variants).
+        // `&mut self`, as VerticalBatch's: nothing that borrows the corpus is alive while it changes -- the rule the C ABI leaves
+        // to its caller. Everything derived from the store (the int8 copy, the kept selection) is dropped.
+        fn changed(&mut self) { self.n = unsafe { ffi::innr_batch_num_vectors(self.h) }; }
+        fn whole_rows(&self, len: usize) -> usize {
+            let n = if self.dim == 0 { 0 } else { len / self.dim };
+            assert_eq!(len, n * self.dim, "the length is no multiple of the dimension");
+            n
+        }
+        /// `codes` (row-major, a whole number of rows) become documents `len() ..`; the others keep their indices
+        pub fn append_codes(&mut self, codes: &[u8]) {
+            let n = self.whole_rows(codes.len());
+            check(unsafe { ffi::innr_batch_append_codes(self.h, codes.as_ptr(), n, self.dim) });
+            self.changed();
+        }
+        /// `append_codes(quantize_u8(rows))` under the corpus' own params, quantised on the device
+        pub fn append(&mut self, rows: &[f32]) {
+            let n = self.whole_rows(rows.len());
+            check(unsafe { ffi::innr_batch_append_quantized(self.h, rows.as_ptr(), n, self.dim) });
+            self.changed();
+        }
+        /// document `indices[j]` (GLOBAL index, any order, no duplicates) becomes `codes[j * dimension ..]`
+        pub fn update_codes(&mut self, indices: &[u64], codes: &[u8]) {
+            assert_eq!(codes.len(), indices.len() * self.dim);
+            check(unsafe { ffi::innr_batch_update_codes(self.h, indices.as_ptr(), codes.as_ptr(), indices.len(), self.dim) });
+            self.changed();
+        }
+        /// `update_codes(indices, quantize_u8(rows))` under the corpus' own params, quantised on the device
+        pub fn update_rows(&mut self, indices: &[u64], rows: &[f32]) {
+            assert_eq!(rows.len(), indices.len() * self.dim);
+            check(unsafe { ffi::innr_batch_update_quantized(self.h, indices.as_ptr(), rows.as_ptr(), indices.len(), self.dim) });
+            self.changed();
+        }
+        /// only the documents with `mask[i] != 0` stay, in index order; returns the new `len()`
+        pub fn keep(&mut self, mask: &[u8]) -> usize {
+            assert_eq!(mask.len(), self.n);
+            let mut n = 0usize;
+            check(unsafe { ffi::innr_batch_keep_codes(self.h, mask.as_ptr(), &mut n) });
+            self.changed();
+            n
         }
         pub fn len(&self) -> usize { self.n }
         pub fn is_empty(&self) -> bool { self.n == 0 }
